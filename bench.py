@@ -4,6 +4,7 @@ Benchmark of the hot path on MI355X: synthesized frames/sec at 1024x1024 config-
     python bench.py --gpus 1 --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs
 
 Workload = BASELINE.json configs[1]: FFHQ config-f 1024x1024, random-init weights (seed 0),
 batched random-z synthesis. One step = one batch of `--batch` z vectors (already resident in HBM)
@@ -11,6 +12,9 @@ batched random-z synthesis. One step = one batch of `--batch` z vectors (already
 libgance_hip.so. With N > 1 every rank runs its own batches (frames shard embarrassingly, weak
 scaling) and the finished frames are gathered into rank 0 over RCCL, in frame order, overlapped
 with the next step.
+
+With --dump-outputs DIR, rank 0 writes the frames of the last timed step (every rank's, in frame order) to DIR as
+float32 .npy files after the timed region: see dump_outputs(). Inputs are seeded, so two builds compare file by file.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- the dominant kernel (modulated conv on the fp32 matrix cores) timed with HIP
@@ -147,6 +151,36 @@ def measured_traffic(step_name: str, resolution: int, batch: int):
             note = "from %s" % record.get("source", "profiles/traffic_latest.json")
             return entry.get("hbm_bytes_per_launch"), note + (" -- STALE: the kernels changed since that PMC pass" if stale else "")
     return None, "profiles/traffic_latest.json does not hold this launch"
+
+
+DUMP_SAMPLE_SIZE = 1 << 21  # values of the seeded sample over the whole step's frames (8 MB float32 + 16 MB of float64 positions)
+
+
+def dump_outputs(directory: Path, frames: torch.Tensor) -> dict:
+    """
+    What the timed path returned in a step: uint8 NHWC frames. Written as float32 (the values exactly), < 64 MB in all:
+      frame_first.npy, frame_last.npy -- the first and the last frame of the step in full, [H, W, 3]
+      frames_sample.npy               -- DUMP_SAMPLE_SIZE values at fixed positions of the flattened [N, H, W, 3] frames
+      frames_sample_index.npy         -- those flat positions (float64, exact), sorted; drawn with seed 0 from the frames' size
+    """
+    host = frames.cpu().numpy()
+    flat = host.reshape(-1)
+    count = min(DUMP_SAMPLE_SIZE, flat.size)
+    index = np.sort(np.random.default_rng(0).choice(flat.size, size=count, replace=False))
+    arrays = {
+        "frame_first": host[0].astype(np.float32),
+        "frame_last": host[-1].astype(np.float32),
+        "frames_sample": flat[index].astype(np.float32),
+        "frames_sample_index": index.astype(np.float64),
+    }
+    directory.mkdir(parents=True, exist_ok=True)
+    for name, array in arrays.items():
+        np.save(directory / f"{name}.npy", array)
+    return {
+        "dir": str(directory), "frames_shape": list(host.shape), "frames_dtype": str(host.dtype),
+        "files": {f"{name}.npy": list(array.shape) for name, array in arrays.items()},
+        "bytes": int(sum(array.nbytes for array in arrays.values())),
+    }
 
 
 def cpu_baseline(resolution: int, variables, budget_seconds: float = 15.0) -> dict:
@@ -500,7 +534,7 @@ def main() -> int:
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=20)
     parser.add_argument("--warmup", type=int, default=3)
-    parser.add_argument("--batch", type=int, default=64, help="frames per step per GPU (the engine's maximum; 32: -2 %, 16: -8 %)")
+    parser.add_argument("--batch", type=int, default=64, help="frames per step per GPU (the engine's maximum; 32: -2 %%, 16: -8 %%)")
     parser.add_argument("--resolution", type=int, default=1024)
     parser.add_argument("--no-cpu-baseline", action="store_true")
     parser.add_argument(
@@ -529,7 +563,16 @@ def main() -> int:
         "fewer copy kernels holding CUs while a gather overlaps the synthesis, for longer; 0 = RCCL's default (the first A/B on a node)",
     )
     parser.add_argument("--batch-sweep", default="1,4,8,16,32,64", help="batch sizes of extras.batch_sweep (SURVEY.md section 8(d) config 2); empty: skip")
+    parser.add_argument(
+        "--dump-outputs", type=Path, default=None, metavar="DIR",
+        help="synthesis workload: after the timed steps, write the frames of the last one to DIR as float32 .npy (first and last "
+        "frame in full + a seeded sample of the whole step, < 64 MB; see dump_outputs), e.g. bench_outputs",
+    )
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.workload != "synthesis":
+        parser.error("--dump-outputs dumps the synthesis workload's frames (--workload synthesis)")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -618,6 +661,10 @@ def main() -> int:
         elapsed_t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(elapsed_t, op=dist.ReduceOp.MAX)
         elapsed = float(elapsed_t.item())
+    # the frames of the last timed step, on the host before the untimed step below reuses a buffer (it writes the other slot)
+    last_frames = None
+    if args.dump_outputs is not None and rank == 0:
+        last_frames = (gathered if world_size > 1 else frames)[(args.steps - 1) & 1].cpu()
     timed = [s for s in engine.steps() if s.name.startswith(dominant_name)]
     dominant_name = timed[0].name
     dominant = hip_lib.StepInfo(dominant_name, sum(s.ms for s in timed) / len(timed), timed[0].flops, timed[0].bytes)
@@ -719,6 +766,8 @@ def main() -> int:
                 ),
             },
         }
+        if last_frames is not None:
+            result["dumped_outputs"] = dump_outputs(args.dump_outputs, last_frames)
         if world_size == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(resolution, variables)
     engine.close()

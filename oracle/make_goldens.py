@@ -310,6 +310,45 @@ def read_wav_cases() -> None:
     print("wrote read_wav.npz")
 
 
+def fresh_seed_case() -> None:
+    """
+    `alpha_blend_projection_file` on a seed no blend case covers (audio seed 99, 4 networks, amplitude range (-1, 1)): the
+    spectrogram and the network indices in full, the projected latents as the sha256 of their float32 bytes (they must
+    match bit for bit), the rows of the blend that are copies of them by number, the blended rows as a strided sample +
+    statistics.
+    """
+    import hashlib  # pylint: disable=import-outside-toplevel
+
+    from gance.data_into_network_visualization import visualization_inputs as vi  # pylint: disable=import-outside-toplevel,import-error
+    from gance.vector_sources.vector_types import MatricesLabel  # pylint: disable=import-outside-toplevel,import-error
+
+    num_frames, vector_length, stride = 90, 512, 11
+    audio = synthetic.synthetic_audio(num_frames, vector_length, seed=99)
+    latents = synthetic.synthetic_final_latents(num_frames // 3, vector_length, seed=5)
+    result = vi.alpha_blend_projection_file(
+        final_latents_matrices_label=MatricesLabel(latents, vector_length, "x"), alpha=0.4, fft_roll_enabled=True,
+        fft_amplitude_range=(-1, 1), blend_depth=10, time_series_audio_vectors=audio, vector_length=vector_length,
+        network_indices=[0, 1, 2, 3],
+    )
+    projected = np.ascontiguousarray(result.b_vectors.data)
+    combined_full = np.asarray(result.combined.data)
+    copies = np.array([row for row in range(combined_full.shape[0]) if np.array_equal(combined_full[row], projected[row])], dtype=np.int64)
+    blended = sampled(np.delete(combined_full, copies, axis=0), stride)
+    arrays = {
+        "meta": np.array([stride], dtype=np.int64),
+        "spectrogram": np.asarray(result.a_vectors.data),
+        "combined_shape": np.array(combined_full.shape, dtype=np.int64),
+        "combined_copy_rows": copies,
+        "blended_sample": blended["sample"],
+        "blended_stats": blended["stats"],
+        "projected_digest": np.array([hashlib.sha256(projected.tobytes()).hexdigest(), str(projected.dtype), str(projected.shape)]),
+        "network_indices": np.asarray(result.network_indices.result.data),
+    }
+    name = "blend_n90_seed99_roll_k4"
+    np.savez_compressed(GOLDEN_DIR / f"{name}.npz", **arrays)
+    print(f"wrote {name}.npz  ({(GOLDEN_DIR / (name + '.npz')).stat().st_size / 1024:.0f} KiB)")
+
+
 def main() -> None:
     ref_stubs.install()
     GOLDEN_DIR.mkdir(parents=True, exist_ok=True)
@@ -318,6 +357,9 @@ def main() -> None:
         return
     if len(sys.argv) > 1 and sys.argv[1] == "read_wav":
         read_wav_cases()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "fresh_seed":
+        fresh_seed_case()
         return
     unit_cases()
     standalone_cases()
@@ -329,6 +371,7 @@ def main() -> None:
     blend_case("blend_n1800_seed7_roll_k3", 1800, 7, True, 3, 257)
     noise_case("noise_n60_seed0_roll_k3", 60, 0, True, 3, 7)
     noise_case("noise_n600_seed5_noroll_k2", 600, 5, False, 2, 97)
+    fresh_seed_case()
     overlay_cases()
 
 

@@ -16,8 +16,8 @@ they restate two third-party leaves whose arithmetic is pure indexing / one form
     same layout so that numpy takes the same (pairwise) summation path in float32.
 
 Every other stubbed module is an empty placeholder: none of them is touched by the arithmetic.
-Nothing from /root/reference is copied; this file is only used by oracle/make_goldens.py and by
-tests that are skipped when /root/reference is absent (it never travels to the GPU box).
+Nothing from /root/reference is copied; this file is only used by oracle/make_goldens.py (the
+tests read the fixtures it writes, never the reference).
 """
 
 import sys

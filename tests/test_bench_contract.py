@@ -88,3 +88,24 @@ def test_metric_labels_of_the_sharded_product_stream_measurements() -> None:
         text = bench.sharded(label, 8)
         assert text.endswith("frame-sharded over 8 GPUs") and "ONE GPU" not in text and "on one GPU" not in text
     assert "2160" in bench.sharded(bench.METRIC_CONFIG_3, 8)
+
+
+def test_dump_outputs_writes_float_arrays_of_the_step_within_the_budget(tmp_path) -> None:
+    """`--dump-outputs`: float32 / float64 .npy files only, the same files for the same frames, the values where the index says."""
+    import numpy as np  # pylint: disable=import-outside-toplevel
+    import torch  # pylint: disable=import-outside-toplevel
+
+    bench = _bench_module()
+    frames = torch.from_numpy(np.random.RandomState(5).randint(0, 256, size=(3, 16, 16, 3)).astype(np.uint8))
+    record = bench.dump_outputs(tmp_path / "a", frames)
+    bench.dump_outputs(tmp_path / "b", frames)
+    assert record["frames_shape"] == [3, 16, 16, 3] and sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(record["files"])
+    for name in record["files"]:
+        first, second = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert first.dtype in (np.float32, np.float64) and np.array_equal(first, second)
+    flat = frames.numpy().reshape(-1)
+    index = np.load(tmp_path / "a" / "frames_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "frames_sample.npy"), flat[index].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "frame_last.npy"), frames.numpy()[-1].astype(np.float32))
+    # the default workload (64 frames of 1024 x 1024 x 3): two float32 frames + the sample and its float64 positions
+    assert 2 * 1024 * 1024 * 3 * 4 + bench.DUMP_SAMPLE_SIZE * (4 + 8) <= 64 * 2**20

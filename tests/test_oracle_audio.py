@@ -1,14 +1,15 @@
 """
 CPU tests pinning the audio -> latent ORACLE (oracle/audio_ref.py) against golden vectors captured
-from the reference's own code (oracle/make_goldens.py; fixtures in tests/golden/), and against
-the live reference when /root/reference is mounted (build container only).
+from the reference's own code (oracle/make_goldens.py; fixtures in tests/golden/).
 """
+
+import hashlib
 
 import numpy as np
 import pytest
 
 from gance_amd import synthetic
-from oracle import audio_ref, ref_stubs
+from oracle import audio_ref
 
 BLEND_CASES = [
     "blend_n60_seed0_roll_k3",
@@ -145,23 +146,25 @@ def test_rms_known_answer_shape_of_reference_test() -> None:
     assert np.isclose(rms[0], np.sqrt(np.mean(audio[:1000].astype(np.float64) ** 2)), rtol=1e-6)
 
 
-@pytest.mark.skipif(not ref_stubs.reference_available(), reason="/root/reference only exists in the build container")
-def test_live_reference_agrees_on_fresh_inputs() -> None:
-    """Beyond the committed goldens: a seed that no fixture covers, straight against the reference."""
-    ref_stubs.install()
-    from gance.data_into_network_visualization import visualization_inputs as vi  # pylint: disable=import-error
-    from gance.vector_sources.vector_types import MatricesLabel  # pylint: disable=import-error
-
+def test_live_reference_agrees_on_fresh_inputs(golden_dir) -> None:
+    """
+    Beyond the blend cases: a seed, amplitude range and network count that no other fixture covers, against what the
+    reference returned for it (tests/golden/blend_n90_seed99_roll_k4.npz, oracle/make_goldens.py fresh_seed_case).
+    """
+    golden = np.load(golden_dir / "blend_n90_seed99_roll_k4.npz")
     num_frames, L = 90, 512
     audio = synthetic.synthetic_audio(num_frames, L, seed=99)
     latents = synthetic.synthetic_final_latents(num_frames // 3, L, seed=5)
-    want = vi.alpha_blend_projection_file(
-        final_latents_matrices_label=MatricesLabel(latents, L, "x"), alpha=0.4, fft_roll_enabled=True,
-        fft_amplitude_range=(-1, 1), blend_depth=10, time_series_audio_vectors=audio, vector_length=L,
-        network_indices=[0, 1, 2, 3],
-    )
     got = audio_ref.alpha_blend_projection_file(latents, 0.4, True, (-1, 1), 10, audio, L, [0, 1, 2, 3])
-    np.testing.assert_allclose(got.spectrogram, want.a_vectors.data, **FLOAT_TOL)
-    np.testing.assert_allclose(got.combined, want.combined.data, **FLOAT_TOL)
-    assert np.array_equal(got.projected, want.b_vectors.data)
-    assert np.array_equal(got.network_indices, want.network_indices.result.data)
+    np.testing.assert_allclose(got.spectrogram, golden["spectrogram"], **FLOAT_TOL)
+    projected = np.ascontiguousarray(got.projected)
+    digest, dtype, shape = (str(v) for v in golden["projected_digest"])
+    assert (str(projected.dtype), str(projected.shape)) == (dtype, shape)
+    assert hashlib.sha256(projected.tobytes()).hexdigest() == digest
+    # the rows past the blend depth are the projected latents themselves (in the reference, bit for bit); the others blended
+    combined, copies = np.asarray(got.combined), golden["combined_copy_rows"]
+    assert combined.shape == tuple(golden["combined_shape"]) and len(copies) > 0
+    for row in copies:
+        assert np.array_equal(combined[row], projected[row])
+    check_stage(golden, "blended", np.delete(combined, copies, axis=0), int(golden["meta"][0]))
+    assert np.array_equal(got.network_indices, golden["network_indices"])
