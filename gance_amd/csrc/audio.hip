@@ -130,10 +130,11 @@ __device__ __forceinline__ double savgol_at(Load x, int i, int n, const double* 
     return acc;
 }
 
-// numpy float32 pairwise summation (add.reduce over a contiguous run), exact operation order.
+// numpy float32 pairwise summation of one contiguous run of at most kNumpyReduceBlock values, exact operation order.
+// Recursive, as numpy's pairwise_sum: halves at multiples of 8 down to runs of <= 128, so at most 6 levels deep for a
+// full block.
 template <typename Load>
 __device__ float pairwise_sum_f32(Load a, int lo, int n) {
-    // explicit stack instead of recursion: (offset, length) pairs, results combined left to right
     if (n < 8) {
         float res = 0.f;
         for (int i = 0; i < n; ++i) res = __fadd_rn(res, a(lo + i));
@@ -155,6 +156,17 @@ __device__ float pairwise_sum_f32(Load a, int lo, int n) {
     const float left = pairwise_sum_f32(a, lo, n2);
     const float right = pairwise_sum_f32(a, lo + n2, n - n2);
     return __fadd_rn(left, right);
+}
+
+// numpy's reduction iterator hands the add loop at most np.getbufsize() = 8192 values per call: add.reduce (and so
+// pandas' float32 Series.mean()) over a longer run sums each 8192-value block pairwise and adds the block sums to the
+// running total one after another.
+constexpr int kNumpyReduceBlock = 8192;
+template <typename Load>
+__device__ float numpy_sum_f32(Load a, int n) {
+    float total = 0.f;
+    for (int lo = 0; lo < n; lo += kNumpyReduceBlock) total = __fadd_rn(total, pairwise_sum_f32(a, lo, min(kNumpyReduceBlock, n - lo)));
+    return total;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -288,7 +300,7 @@ __global__ __launch_bounds__(512) void smooth_kernel(const double* __restrict__ 
     }
 }
 
-// a7: float32 RMS per frame, numpy pairwise order (librosa hop is 512 whatever L is). Generic form: one thread per frame.
+// a7: float32 RMS per frame, numpy's add.reduce order (librosa hop is 512 whatever L is). Generic form: one thread per frame.
 __global__ void rms_kernel(const float* __restrict__ audio, size_t num_samples, int L, int n_frames,
                            float* __restrict__ rms) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,7 +310,7 @@ __global__ void rms_kernel(const float* __restrict__ audio, size_t num_samples, 
         const float v = frame[i];
         return __fmul_rn(v, v);
     };
-    const float total = pairwise_sum_f32(sq, 0, L);
+    const float total = numpy_sum_f32(sq, L);  // frames longer than kNumpyReduceBlock are summed blockwise as well
     // np.mean: the float32 sum divided by the count in float32 (exact when L is a power of two); correctly
     // rounded float32 sqrt: sqrt in float64 then one rounding (53 >= 2*24+2 bits: the double rounding is innocuous)
     rms[t] = (float)sqrt((double)__fdiv_rn(total, (float)L));
@@ -349,7 +361,7 @@ __global__ void rolling_max_kernel(const float* __restrict__ in, int n, int size
     out[i] = nan ? NAN : best;
 }
 
-// a8 + a9: one thread walks the per-frame series: float32 mean (fill value), pandas rolling mean
+// a8 + a9: one thread walks the per-frame series: float32 mean (fill value, numpy's blocked order), pandas rolling mean
 // (Kahan add/remove), savgol, min/max, linear remap, rint, and (for the roll) the running sum mod L.
 struct ChainArgs {
     const float* rms;
@@ -390,7 +402,7 @@ __global__ __launch_bounds__(kChainThreads) void reduce_chain_kernel(ChainArgs a
     const float* const series = staged ? rms_lds : a.rms;
     if (tid == 64) {  // wavefront 1: fill value = float32 mean of the raw series
         auto r = [&](int i) { return series[i]; };
-        fill_shared = (double)__fdiv_rn(pairwise_sum_f32(r, 0, n), (float)n);
+        fill_shared = (double)__fdiv_rn(numpy_sum_f32(r, n), (float)n);
     }
     if (tid == 0) {  // wavefront 0: pandas roll_mean, fixed window, min_periods = window (head entries set below)
         int nobs = 0, neg_ct = 0, same = 0;

@@ -91,13 +91,27 @@ def compute_spectrogram_smooth_scale(audio: np.ndarray, vector_length: int, ampl
 # ----------------------------------------------------------------------------------------------
 # a7  RMS per frame                                 gance/vector_sources/vector_reduction.py:22-35
 # ----------------------------------------------------------------------------------------------
+# numpy's reduction iterator hands the add loop at most np.getbufsize() = 8192 values per call
+NUMPY_REDUCE_BLOCK = 8192
+
+
 def numpy_pairwise_sum_f32(values: np.ndarray) -> np.float32:
     """
-    numpy's float32 add.reduce over a contiguous run (pairwise summation, block 128, 8 lanes):
-    the order librosa's `np.mean(np.abs(x) ** 2, axis=0)` sums each frame in. Restated so the HIP
-    kernel can reproduce the float32 RMS bit for bit.
+    numpy's float32 add.reduce over a contiguous run: the order librosa's `np.mean(np.abs(x) ** 2, axis=0)`
+    sums each frame in, and pandas' float32 `Series.mean()` sums a series in. The reduction iterator
+    feeds the run in blocks of NUMPY_REDUCE_BLOCK values, each block is summed pairwise
+    (_pairwise_sum_f32) and added to the running total one after another. Restated so the HIP kernel
+    can reproduce it bit for bit.
     """
     a = np.asarray(values, dtype=np.float32)
+    total = np.float32(0.0)
+    for start in range(0, len(a), NUMPY_REDUCE_BLOCK):
+        total = np.float32(total + _pairwise_sum_f32(a[start : start + NUMPY_REDUCE_BLOCK]))
+    return total
+
+
+def _pairwise_sum_f32(a: np.ndarray) -> np.float32:
+    """numpy's float32 pairwise summation of one block (block 128, 8 lanes)."""
     n = len(a)
     if n < 8:
         res = np.float32(0.0)
@@ -121,7 +135,7 @@ def numpy_pairwise_sum_f32(values: np.ndarray) -> np.float32:
         return res
     n2 = n // 2
     n2 -= n2 % 8
-    return np.float32(numpy_pairwise_sum_f32(a[:n2]) + numpy_pairwise_sum_f32(a[n2:]))
+    return np.float32(_pairwise_sum_f32(a[:n2]) + _pairwise_sum_f32(a[n2:]))
 
 
 def compute_raw_rms(audio: np.ndarray, vector_length: int) -> np.ndarray:

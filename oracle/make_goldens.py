@@ -1,7 +1,7 @@
 """
 ORACLE tooling (build container only): capture golden vectors from the REFERENCE's own code.
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python oracle/make_goldens.py
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python oracle/make_goldens.py [standalone | read_wav | fresh_seed | long]
 
 Imports gance.data_into_network_visualization.visualization_inputs / gance.apply_spectrogram /
 gance.vector_sources.* from /root/reference with the leaf stubs of oracle/ref_stubs.py and writes
@@ -349,6 +349,15 @@ def fresh_seed_case() -> None:
     print(f"wrote {name}.npz  ({(GOLDEN_DIR / (name + '.npz')).stat().st_size / 1024:.0f} KiB)")
 
 
+def long_cases() -> None:
+    """
+    A song-length blend (9000 frames: 2.5 minutes at 60 fps). Past 8192 frames pandas' float32 `Series.mean()` (the
+    fill value of the rolling mean's NaN head) sums in numpy's buffered blocks of 8192 values; seed 11 is one whose
+    last bit depends on that order. Written on its own (`make_goldens.py long`) so the smaller fixtures keep their bytes.
+    """
+    blend_case("blend_n9000_seed11_roll_k3", 9000, 11, True, 3, 2053)
+
+
 def main() -> None:
     ref_stubs.install()
     GOLDEN_DIR.mkdir(parents=True, exist_ok=True)
@@ -361,6 +370,9 @@ def main() -> None:
     if len(sys.argv) > 1 and sys.argv[1] == "fresh_seed":
         fresh_seed_case()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "long":
+        long_cases()
+        return
     unit_cases()
     standalone_cases()
     read_wav_cases()
@@ -372,6 +384,7 @@ def main() -> None:
     noise_case("noise_n60_seed0_roll_k3", 60, 0, True, 3, 7)
     noise_case("noise_n600_seed5_noroll_k2", 600, 5, False, 2, 97)
     fresh_seed_case()
+    long_cases()
     overlay_cases()
 
 

@@ -25,6 +25,7 @@ BLEND_CASES = [
     "blend_n60_seed2_roll_k1",
     "blend_n240_seed3_roll_k3",
     "blend_n1800_seed7_roll_k3",
+    "blend_n9000_seed11_roll_k3",  # past numpy's 8192-value reduction block
 ]
 
 

@@ -17,6 +17,7 @@ BLEND_CASES = [
     "blend_n60_seed2_roll_k1",
     "blend_n240_seed3_roll_k3",
     "blend_n1800_seed7_roll_k3",
+    "blend_n9000_seed11_roll_k3",
 ]
 FLOAT_TOL = dict(rtol=1e-10, atol=1e-10)
 
@@ -120,10 +121,22 @@ def test_array_helpers_match_the_reference_goldens(golden_dir) -> None:
 
 
 def test_pairwise_sum_restatement_is_numpy_bit_for_bit() -> None:
+    import pandas as pd
+
+    # numpy feeds add.reduce in buffers of this many values; the restatement (and the HIP kernel) assume 8192
+    assert np.getbufsize() == audio_ref.NUMPY_REDUCE_BLOCK == 8192
     rng = np.random.RandomState(0)
-    for n in (1, 7, 8, 9, 100, 128, 129, 512, 1000, 1800, 4097):
+    orders_differ = []
+    for n in (1, 7, 8, 9, 100, 128, 129, 512, 1000, 1800, 4097, 8192, 8193, 9000, 15361, 16385, 20000, 100000):
         values = (rng.randn(n) * rng.rand() * 10).astype(np.float32)
-        assert audio_ref.numpy_pairwise_sum_f32(values) == np.add.reduce(values)
+        total = audio_ref.numpy_pairwise_sum_f32(values)
+        assert total == np.add.reduce(values), n
+        # pandas' float32 mean (the rolling average's fill value) is that sum over the count, in float32
+        assert np.float32(total / np.float32(n)) == pd.Series(values).mean(), n
+        if audio_ref._pairwise_sum_f32(values) != total:  # pylint: disable=protected-access
+            orders_differ.append(n)
+    # one pairwise tree over the whole series is numpy's order only up to one block: the cases above separate them
+    assert orders_differ and min(orders_differ) > 8192, orders_differ
 
 
 def test_rolling_mean_restatement_is_pandas_bit_for_bit() -> None:
