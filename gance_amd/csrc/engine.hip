@@ -618,11 +618,12 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
         ConvForm form{};
         // the network's last conv absorbs its ToRGB when one block holds all channels of a pixel
         // (BM = Cout = 32, i.e. the 1024^2 generator): neither its activation nor the fp32 image is
-        // written, only the uint8 frame (GANCE_TUNE_FUSE_RGB=0 turns this off)
+        // written, only the uint8 frame (GANCE_TUNE_FUSE_RGB=0 turns this off) -- so not where a debug tap reads that activation:
+        // gance_engine_debug_read_activation would return whatever an earlier call left in the buffer
         static const bool fuse_enabled = [] { const char* v = std::getenv("GANCE_TUNE_FUSE_RGB"); return !(v && std::atoi(v) == 0); }();
         const auto& tile = gance::kConvTiles[p.tile_id];
         form.fused_rgb = fuse_enabled && c.res_log2 == e->res_log2 && limit == num_convs && p.nsplit == 1 &&
-                         p.m_tiles == 1 && tile.TB == 1 && tile.BM == 32 && have_y_then;
+                         p.m_tiles == 1 && tile.TB == 1 && tile.BM == 32 && have_y_then && e->debug_stop_after <= 0;
         // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry with the ToRGB product
         // in its epilogue (GANCE_TUNE_LAST_WINO64 = 0 / 1; measured: see DESIGN.md §3)
         static const int last_wino64 = [] { const char* v = std::getenv("GANCE_TUNE_LAST_WINO64"); return v ? std::atoi(v) : 1; }();

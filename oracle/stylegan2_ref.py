@@ -21,7 +21,7 @@ transposed conv), so agreement between the two is evidence, not tautology.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
 
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -157,6 +157,38 @@ def truncate(dlatents: torch.Tensor, variables: Variables, psi: Optional[float])
     return avg + (dlatents - avg) * psi
 
 
+class ConvLayerRef(NamedTuple):
+    """The fields of a modulated 3x3 conv layer that synthesis_layer reads (gance_amd.stylegan2.spec.ConvLayer has them too)."""
+
+    layer_idx: int  # dlatent row, noise buffer index
+    scope: str  # variable scope under G_synthesis/, e.g. "1024x1024/Conv0_up"
+    up: bool
+
+
+def synthesis_layer(
+    x: torch.Tensor,
+    dlatents: torch.Tensor,
+    variables: Variables,
+    conv,
+    noise_override: Optional[Dict[int, torch.Tensor]] = None,
+) -> torch.Tensor:
+    """
+    One conv layer of `G_synthesis_stylegan2` (its inner `layer()`): modulated 3x3 conv (stride-2 transposed + FIR when
+    `conv.up`), the stored noise buffer times noise_strength, bias, leaky ReLU x sqrt(2). `conv` is a spec.ConvLayer or a
+    ConvLayerRef; `dlatents` [B, W, 512] (row conv.layer_idx is read). g_synthesis calls this for every conv layer, so a
+    layer checked in isolation is checked against exactly the arithmetic of the whole chain.
+    """
+    dtype = x.dtype
+    scope = f"G_synthesis/{conv.scope}"
+    x = modulated_conv2d_layer(x, dlatents[:, conv.layer_idx], variables, scope, 3, up=conv.up)
+    if noise_override is not None and conv.layer_idx in noise_override:
+        noise = noise_override[conv.layer_idx].to(dtype)
+    else:
+        noise = _t(variables, f"G_synthesis/noise{conv.layer_idx}", dtype)
+    x = x + noise * _t(variables, f"{scope}/noise_strength", dtype)
+    return apply_bias_act(x, _t(variables, f"{scope}/bias", dtype), "lrelu")
+
+
 def g_synthesis(
     dlatents: torch.Tensor,
     variables: Variables,
@@ -176,13 +208,7 @@ def g_synthesis(
     batch = dlatents.shape[0]
 
     def layer(x: torch.Tensor, layer_idx: int, scope: str, up: bool) -> torch.Tensor:
-        x = modulated_conv2d_layer(x, dlatents[:, layer_idx], variables, scope, 3, up=up)
-        if noise_override is not None and layer_idx in noise_override:
-            noise = noise_override[layer_idx].to(dtype)
-        else:
-            noise = _t(variables, f"G_synthesis/noise{layer_idx}", dtype)
-        x = x + noise * _t(variables, f"{scope}/noise_strength", dtype)
-        return apply_bias_act(x, _t(variables, f"{scope}/bias", dtype), "lrelu")
+        return synthesis_layer(x, dlatents, variables, ConvLayerRef(layer_idx, scope, up), noise_override)
 
     def torgb(x: torch.Tensor, y: Optional[torch.Tensor], res: int) -> torch.Tensor:
         scope = f"G_synthesis/{2**res}x{2**res}/ToRGB"
@@ -191,7 +217,7 @@ def g_synthesis(
         return t if y is None else y + t
 
     x = _t(variables, "G_synthesis/4x4/Const/const", dtype).repeat(batch, 1, 1, 1)
-    x = layer(x, 0, "G_synthesis/4x4/Conv", up=False)
+    x = layer(x, 0, "4x4/Conv", up=False)
     if collect is not None:
         collect.append(x)
     if stop_after == 1:
@@ -199,12 +225,12 @@ def g_synthesis(
     y = torgb(x, None, 2)
     for res in range(3, res_log2 + 1):
         side = 2 ** res
-        x = layer(x, res * 2 - 5, f"G_synthesis/{side}x{side}/Conv0_up", up=True)
+        x = layer(x, res * 2 - 5, f"{side}x{side}/Conv0_up", up=True)
         if collect is not None:
             collect.append(x)
         if stop_after == res * 2 - 4:
             return x
-        x = layer(x, res * 2 - 4, f"G_synthesis/{side}x{side}/Conv1", up=False)
+        x = layer(x, res * 2 - 4, f"{side}x{side}/Conv1", up=False)
         if collect is not None:
             collect.append(x)
         if stop_after == res * 2 - 3:

@@ -56,3 +56,17 @@ def test_role_split_up_kernel_fits_two_waves_per_simd_without_scratch() -> None:
     assert result.returncode == 0, result.stdout + result.stderr
     assert "upfirr_fused_kernel" in result.stdout
 
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not Path("/opt/rocm/bin/hipcc").exists(), reason="needs hipcc")
+def test_split_operand_up_kernels_wait_for_their_weight_dma_by_count() -> None:
+    """
+    The split-operand up kernels (upfir_split.hip) order the next chunk's weight LDS-DMA before its fragments are read with one
+    hand-counted `s_waitcnt vmcnt(24)`: a load the compiler moves across it makes a stale-weight race that a parity test may never
+    catch. tools/check_upfirs_isa.py cross-compiles and checks, per kernel: no scratch, the 1044 MFMAs, the inline wait once per
+    chunk parity, and exactly 24 vector-memory instructions on every path from the last weight DMA to it.
+    """
+    result = subprocess.run([sys.executable, str(REPO_ROOT / "tools" / "check_upfirs_isa.py")], capture_output=True, text=True, timeout=900)
+    assert result.returncode == 0, result.stdout + result.stderr
+    for name in ("upfirs_fused_kernel", "upfirs_fused_noise_kernel", "upfirs_fused_pre_kernel", "upfirs_fused_pre_noise_kernel"):
+        assert name in result.stdout

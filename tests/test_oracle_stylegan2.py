@@ -122,3 +122,27 @@ def test_fp32_oracle_tracks_fp64_oracle(net32) -> None:
     a = ref.synthesize_w(dl, net32, 32, dtype=torch.float64)
     b = ref.synthesize_w(dl, net32, 32, dtype=torch.float32)
     assert float((a - b.double()).abs().max()) < 1e-4
+
+
+def test_one_layer_continues_the_chain_bit_for_bit() -> None:
+    """
+    synthesis_layer (one conv layer in isolation: the layer-wise GPU tests feed it the kernel's own input) applied to the chain
+    stopped after layer n - 1 equals the chain stopped after layer n exactly, in fp64, for every conv layer of a 64^2 network with
+    noise and biases on: up and stride-1 layers, and a noise override.
+    """
+    resolution = 64
+    spec = sg2_spec.make_spec(resolution)
+    variables = sg2_spec.make_random_variables(resolution, seed=4, perturb=True)
+    assert any(np.abs(variables[f"G_synthesis/{c.scope}/noise_strength"]).max() > 0 for c in spec.convs)
+    assert any(np.abs(variables[f"G_synthesis/{c.scope}/bias"]).max() > 0 for c in spec.convs)
+    dl = torch.from_numpy(np.random.RandomState(6).randn(2, spec.num_layers, 512)).double()
+    override = {3: torch.from_numpy(np.random.RandomState(8).randn(1, 1, 16, 16))}
+    with torch.no_grad():
+        chain: list = []
+        ref.g_synthesis(dl, variables, resolution, noise_override=override, collect=chain)
+        assert len(chain) == len(spec.convs) and sum(c.up for c in spec.convs) == 4
+        for n in range(2, len(spec.convs) + 1):
+            conv = spec.convs[n - 1]
+            assert torch.equal(ref.g_synthesis(dl, variables, resolution, noise_override=override, stop_after=n), chain[n - 1])
+            got = ref.synthesis_layer(chain[n - 2], dl, variables, conv, noise_override=override)
+            assert torch.equal(got, chain[n - 1]), f"conv layer {n} ({conv.scope})"
