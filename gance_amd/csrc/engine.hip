@@ -209,8 +209,6 @@ struct gance_workspace {
     std::vector<float*> act;      // per conv layer: zero-bordered output [Bmax][cout][res+2][res+8]
     std::vector<float*> tplanes;  // per up layer: [4 cls][max_units][cout][H+3][W+8] (else nullptr)
     float* slabs = nullptr;       // split-K scratch of the small stride-1 convs (dense)
-    void* x_units = nullptr;  // an up layer's input split into bf16 parts (upfir_split_roles.hip: launch_upfirr_split_activation)
-    size_t x_units_bytes = 0;
     float *up_packed = nullptr, *up_prod = nullptr;  // the GEMM forms' operand images and products (gemm_forms.hip: scatter-form up layers, Winograd at 8x8 / 16x16)
     float* ybuf[2] = {nullptr, nullptr};
     float* rgb_coef = nullptr;  // [Bmax][8 m tiles][16][64]: A operands of a ToRGB product fused into a Winograd conv epilogue
@@ -239,7 +237,6 @@ struct gance_workspace {
         for (float* ptr : act) hipFree(ptr);
         for (float* ptr : tplanes) hipFree(ptr);
         hipFree(slabs);
-        hipFree(x_units);
         hipFree(up_packed);
         hipFree(up_prod);
         hipFree(ybuf[0]);
@@ -288,12 +285,10 @@ struct gance_engine {
     std::vector<size_t> winogemm_w;  // weight image of the Winograd F(4x4,3x3) GEMM form of the stride-1 layers at 8x8, 16x16 (gemm_forms.hip; else SIZE_MAX)
     std::vector<size_t> upgemm_w;  // weight image of the scatter-form GEMM of the two smallest up layers (gemm_forms.hip; else SIZE_MAX)
     size_t up_packed_floats = 0, up_prod_floats = 0;
-    size_t x_units_bytes = 0;  // the largest split input image of an up layer that can take the role-split form
-    int gemm_bf16 = 0;  // experiment (GANCE_TUNE_GEMM_BF16X6 when the engine is created): the GEMM forms on the 16-bit matrix cores from split operands: 1 = bf16 x 3 (six terms), 2 = fp16 x 2 (three terms)
+    int gemm_bf16 = 0;  // experiment (GANCE_TUNE_GEMM_BF16X6 when the engine is created): 1 = the GEMM forms on the bf16 matrix cores from split operands, bf16 x 3 (six terms); any non-zero value selects it (a stale 2, the removed fp16 x 2 mode, too)
     std::vector<size_t> upfir16x_w;  // ... and for that geometry's pair form (F(2,2) along x: 15 MFMAs per pair of columns instead of 18)
     std::vector<size_t> upfirs_w;    // split-operand form of the fused up kernel (upfir_split.hip: three bf16 parts per value, six terms, fp32 accumulation)
     int upfir_split = 1;  // GANCE_TUNE_UPFIR_SPLIT when the engine is created: 0 never, 1 (default) where a launch fills the chip without row segments, 2 wherever supported
-    int upfir_split_roles = 0;  // GANCE_TUNE_UPFIR_SPLIT_ROLES when the engine is created: 0 (default) the one-role kernel (upfir_split.hip); 1 the experiment with matrix and vector waves (upfir_split_roles.hip + a split pass over its input: slower than the one-role kernel once that pass is paid for)
     int upfir_split_max_res = 1024;  // GANCE_TUNE_UPFIR_SPLIT_MAXRES: the largest OUTPUT side that takes the split form in mode 1 (measured: DESIGN.md section 3; 512 until the staging went to 16-byte loads)
     int num_cus = 256;
     std::vector<float> conv_ns;
@@ -658,28 +653,27 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
     // Whether up layer idx runs as the fused kernel (transposed conv + FIR in one launch): where it is supported and fills
     // the chip; GANCE_TUNE_UPFIR = 0 / 1 / 2 overrides the engine flags (never / auto / always). Decided here because the
     // layer BEFORE it has to know: fed by a 16x16x4 Winograd launch the fused kernel takes its input pre-scaled by its style.
-    auto up_runs_fused = [&](int idx, gance::UpFirArgs* plan) -> bool {
+    // split: the split-operand form (launch_upfir_split); fp32: the fp32-MFMA forms (launch_upfir16_fused / launch_upfir_fused)
+    enum class UpFused { no, fp32, split };
+    auto up_runs_fused = [&](int idx, gance::UpFirArgs* plan) -> UpFused {
         const ConvLayerHost& c = e->convs[idx];
         const int H = (1 << c.res_log2) / 2;
         static const int upfir_env = [] { const char* v = std::getenv("GANCE_TUNE_UPFIR"); return v ? std::atoi(v) : -1; }();
         const int upfir_mode = upfir_env >= 0 ? upfir_env
                                               : ((e->cfg.flags & GANCE_FLAG_SPLIT_UPFIR) ? 0 : ((e->cfg.flags & GANCE_FLAG_FORCE_FUSED_UPFIR) ? 2 : 1));
-        if (!c.up || upfir_mode == 0 || (e->upfir_w[idx] == SIZE_MAX && e->upfir16_w[idx] == SIZE_MAX)) return false;
+        if (!c.up || upfir_mode == 0 || (e->upfir_w[idx] == SIZE_MAX && e->upfir16_w[idx] == SIZE_MAX)) return UpFused::no;
         gance::UpFirArgs u{};
         u.Cin = c.cin;
         // the split-operand form (upfir_split.hip; a block sweeps the image's height, or a row segment of it where whole images would leave
         // CUs idle: upfirs_plan): where its launch has blocks for 9/16 of the CUs
         if (e->upfirs_w[idx] != SIZE_MAX && upfir_mode != 0) {
-            const bool roles = e->upfir_split_roles != 0 && gance::upfirr_supported(c.cin, c.cout, H, H);
-            if (roles) gance::upfirr_plan(B, c.cout, H, H, e->num_cus, &u);
-            else gance::upfirs_plan(B, c.cout, H, H, e->num_cus, &u);
+            gance::upfirs_plan(B, c.cout, H, H, e->num_cus, &u);
             // (9/16: measured without row segments, 16 blocks per frame at every layer -- whole calls of 8 / 9 / 10 / 11 frames ran at 1053 / 842 / 909 / 940
             // frames/s in the fp32 forms, at 953 / ~1000 / 1045 / 1106 in this one; with row segments 1 ... 8 frames per call take it too wherever 16-row
             // segments reach that many blocks: 645 / 895 / 899 / 1080 / 934 / 1055 / 1136 / 1202 frames/s against 614 / 817 / 861 / 960 / - / 980 / - / 1047)
             if (e->upfir_split == 2 || (u.total_blocks >= e->num_cus * 9 / 16 && 2 * H <= e->upfir_split_max_res)) {
-                u.pair_form = roles ? 3 : 2;  // (marks the plan: the caller launches launch_upfir_split_roles / launch_upfir_split)
                 if (plan != nullptr) *plan = u;
-                return true;
+                return UpFused::split;
             }
             u = gance::UpFirArgs{};
             u.Cin = c.cin;
@@ -691,7 +685,7 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
         const int steps_per_seg = u.rows_per_seg / u.step_rows;
         if (plan != nullptr) *plan = u;
         // (the narrow strip geometries -- inputs 32 and 16 wide -- have one or two steps per image: never cut into segments)
-        return upfir_mode == 2 || (u.total_blocks >= e->num_cus * 3 / 4 && (u.segs == 1 || steps_per_seg >= 4));
+        return (upfir_mode == 2 || (u.total_blocks >= e->num_cus * 3 / 4 && (u.segs == 1 || steps_per_seg >= 4))) ? UpFused::fp32 : UpFused::no;
     };
     static const bool prescale_up = [] { const char* v = std::getenv("GANCE_TUNE_PRESCALE_UP"); return !(v && std::atoi(v) == 0); }();
     bool x_prescaled = false;  // x_in carries the style of the layer about to read it
@@ -771,7 +765,7 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                 // the next layer's style rides on this launch's stores when that layer is a fused up kernel — and only when this
                 // launch also does the ToRGB channel sum (from the plain values): torgb_kernel would otherwise read the scaled ones
                 const float* const s_next_up =
-                    (rgb_part && (form.wino64 || form.wino43) && c.cout % 64 == 0 && prescale_up && li + 1 < limit && up_runs_fused(li + 1, nullptr))
+                    (rgb_part && (form.wino64 || form.wino43) && c.cout % 64 == 0 && prescale_up && li + 1 < limit && up_runs_fused(li + 1, nullptr) != UpFused::no)
                         ? e->ws->styles + e->conv_s_off[li + 1]
                         : nullptr;
                 x_prescaled = s_next_up != nullptr;
@@ -817,9 +811,9 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
             x_prescaled = false;
             {
                 gance::UpFirArgs u{};
-                if (up_runs_fused(li, &u)) {
-                    const bool roles_form = u.pair_form == 3;
-                    const bool split_form = u.pair_form == 2 || roles_form;
+                const UpFused fused = up_runs_fused(li, &u);
+                if (fused != UpFused::no) {
+                    const bool split_form = fused == UpFused::split;
                     const bool geometry16 = !split_form && e->upfir16_w[li] != SIZE_MAX;
                     const bool pair_form = geometry16 && e->upfir16x_w[li] != SIZE_MAX && input_prescaled;
                     u.pair_form = pair_form ? 1 : 0;
@@ -842,25 +836,16 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                     u.x_b_stride = x_b_stride;
                     u.s_next = s_next;
                     u.input_prescaled = input_prescaled ? 1 : 0;
-                    u.x_units = e->ws->x_units;
                     // ("convTFp": upfir_fused_pre_kernel, the input arrives multiplied by this layer's style)
                     // (a trailing "/16": the 16-channel, two-blocks-per-CU geometry, upfir16_fused*_kernel; "/16x": its pair form)
                     // ("/s3": the split-operand form, upfirs_fused*_kernel: bf16 x 3 parts, six product terms, fp32 accumulation)
-                    // ("/s3r": the same products with the block's work in two roles, upfirr_fused*_kernel: matrix waves and vector waves)
                     std::snprintf(name, sizeof(name), input_prescaled ? "convTFp%d_%dx%d_%d->%d%s" : "convTF%d_%dx%d_%d->%d%s", c.layer_idx, res, res, c.cin,
-                                  c.cout, roles_form ? "/s3r" : split_form ? "/s3" : (pair_form ? "/16x" : (geometry16 ? "/16" : "")));
-                    if (roles_form) {
-                        // the layer's input times its style (unless the producer multiplied it in), split into three bf16 parts per value
-                        char split_name[64];
-                        std::snprintf(split_name, sizeof(split_name), "split%d_%dx%d_%d", c.layer_idx, H, W, c.cin);
-                        StepScope scope(e, stream, split_name, 0.0, 10.0 * (double)B * c.cin * (H + 2) * (W + 8));
-                        GANCE_HIP_CHECK(gance::launch_upfirr_split_activation(x_in, x_b_stride, input_prescaled ? nullptr : u.s, u.s_stride, e->ws->x_units, B, c.cin, H, W, stream));
-                    }
+                                  c.cout, split_form ? "/s3" : (pair_form ? "/16x" : (geometry16 ? "/16" : "")));
                     {
                         const double flops = 2.0 * 9 * (double)c.cin * c.cout * H * W * B;
                         const double bytes = 4.0 * ((double)B * c.cin * H * W + (double)B * c.cout * res * res + 9.0 * c.cin * c.cout);
                         StepScope scope(e, stream, name, flops, bytes);
-                        GANCE_HIP_CHECK(roles_form ? gance::launch_upfir_split_roles(u, stream) : split_form ? gance::launch_upfir_split(u, stream)
+                        GANCE_HIP_CHECK(split_form ? gance::launch_upfir_split(u, stream)
                                                    : (geometry16 ? gance::launch_upfir16_fused(u, stream) : gance::launch_upfir_fused(u, stream)));
                     }
                     x_in = x_out;
@@ -990,8 +975,6 @@ int acquire_workspace(gance_engine* e) {
         if (it != g_workspaces.end())
             if (auto alive = it->second.lock()) {
                 e->ws = alive;
-                // (a workspace made by an engine without the role-split experiment has no room for its input image: this engine goes without it too)
-                if (e->x_units_bytes > alive->x_units_bytes) e->upfir_split_roles = 0;
                 return GANCE_OK;
             }
     }
@@ -1027,8 +1010,6 @@ int acquire_workspace(gance_engine* e) {
         if (ok && c.up)
             ok = alloc((void**)&ws->tplanes[i], (size_t)4 * e->t_units[i] * c.cout * t_plane((1 << c.res_log2) / 2) * sizeof(float), true);
     }
-    ok = ok && alloc((void**)&ws->x_units, std::max<size_t>(16, e->x_units_bytes), false);
-    ws->x_units_bytes = e->x_units_bytes;
     ok = ok && alloc((void**)&ws->up_packed, std::max<size_t>(1, e->up_packed_floats) * sizeof(float), false) &&
          alloc((void**)&ws->up_prod, std::max<size_t>(1, e->up_prod_floats) * sizeof(float), false);
     ok = ok && alloc((void**)&ws->slabs, e->slab_floats * sizeof(float), false) &&
@@ -1126,11 +1107,9 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     gance_engine* e = new gance_engine();
     {  // (read per engine, not once per process: a test creates engines with and without it)
         const char* v = std::getenv("GANCE_TUNE_GEMM_BF16X6");
-        e->gemm_bf16 = v != nullptr ? std::max(0, std::min(2, std::atoi(v))) : 0;
+        e->gemm_bf16 = v != nullptr && std::atoi(v) != 0 ? 1 : 0;
         const char* const split = std::getenv("GANCE_TUNE_UPFIR_SPLIT");
         e->upfir_split = split != nullptr ? std::max(0, std::min(2, std::atoi(split))) : 1;
-        const char* const roles = std::getenv("GANCE_TUNE_UPFIR_SPLIT_ROLES");
-        if (roles != nullptr) e->upfir_split_roles = std::atoi(roles) != 0 ? 1 : 0;
         const char* const split_res = std::getenv("GANCE_TUNE_UPFIR_SPLIT_MAXRES");
         if (split_res != nullptr) e->upfir_split_max_res = std::atoi(split_res);
     }
@@ -1273,7 +1252,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
             // (the experiment's 256-row block tiles need Cout to be a multiple of 256: a 128-channel layer of a reduced network keeps the fp32 GEMM)
             const int split_mode = c.cout % 256 == 0 ? e->gemm_bf16 : 0;
             e->winogemm_w[i] = reserve(gance::winogemm_weight_floats(c.cin, c.cout) * (split_mode ? 3 : 2) / 2);
-            if (split_mode) gance::winogemm_arrange_weights_split(scaled.data(), c.cin, c.cout, split_mode, &pool[e->winogemm_w[i]]);
+            if (split_mode) gance::winogemm_arrange_weights_split(scaled.data(), c.cin, c.cout, &pool[e->winogemm_w[i]]);
             else gance::winogemm_arrange_weights(scaled.data(), c.cin, c.cout, &pool[e->winogemm_w[i]]);
         }
         e->upgemm_w.push_back(SIZE_MAX);
@@ -1283,7 +1262,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
             // (the experiment's 256-row block tiles need 9 Cout to be a multiple of 256: the 128-channel layer keeps the fp32 GEMM)
             const int split_mode = (9 * c.cout) % 256 == 0 ? e->gemm_bf16 : 0;
             e->upgemm_w[i] = reserve(gance::upgemm_weight_floats(c.cin, c.cout) * (split_mode ? 3 : 2) / 2);
-            if (split_mode) gance::upgemm_arrange_weights_split(scaled.data(), c.cin, c.cout, kUpTapWeight, split_mode, &pool[e->upgemm_w[i]]);
+            if (split_mode) gance::upgemm_arrange_weights_split(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upgemm_w[i]]);
             else gance::upgemm_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upgemm_w[i]]);
         }
         e->upfirs_w.push_back(SIZE_MAX);
@@ -1388,12 +1367,6 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
             e->up_packed_floats = std::max(e->up_packed_floats, gance::winogemm_packed_floats(samples, c.cin, 2 * H, 2 * H) * 3 / 2);
             e->up_prod_floats = std::max(e->up_prod_floats, gance::winogemm_prod_floats(samples, c.cout, 2 * H, 2 * H));
         }
-    }
-    // the split input image of the up layers that can take the role-split form (whatever this engine's knobs say: the workspace is shared)
-    for (int i = 0; i < nconv; ++i) {
-        const ConvLayerHost& c = e->convs[i];
-        const int H = (1 << c.res_log2) / 2;
-        if (c.up && e->upfir_split_roles != 0 && gance::upfirr_supported(c.cin, c.cout, H, H)) e->x_units_bytes = std::max(e->x_units_bytes, gance::upfirr_units_bytes(Bmax, c.cin, H, H));
     }
     e->y_floats = (size_t)3 * config->resolution * config->resolution * Bmax;
     // partial ToRGB images of the Winograd conv launches whose pixels span several channel tiles: [Cout / 64][Bmax][3][R][R]

@@ -199,7 +199,6 @@ struct UpFirArgs {
     const float* s_next;
     int input_prescaled;  // x arrives multiplied by this layer's own style (its producer was given s_next): no style scale in the K loop
     int pair_form;        // upfir16 only: w is the pair-form image (upfir16x_arrange_weights): F(2,2) along x, 15 MFMAs per pair of columns instead of 18
-    const void* x_units;  // upfir_split_roles only: x times the layer's style, split into bf16 parts (launch_upfirr_split_activation's image)
 };
 bool upfir_supported(int cin, int cout, int H, int W);
 size_t upfir_weight_floats(int cin, int cout);
@@ -227,17 +226,6 @@ void upfirs_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int cin
 void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* args);
 hipError_t launch_upfir_split(const UpFirArgs& args, hipStream_t stream);
 
-// The split-operand form with the work of a block in two roles (upfir_split_roles.hip): four matrix waves (MFMAs only) and four
-// vector waves (staging, split, FIR epilogue of the step before) per block, two waves per SIMD, 4 position rows per step. Same
-// weight image as upfir_split.hip (upfirs_arrange_weights); the plan sets step_rows = 4.
-bool upfirr_supported(int cin, int cout, int H, int W);
-void upfirr_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* args);
-hipError_t launch_upfir_split_roles(const UpFirArgs& args, hipStream_t stream);
-// ... and its input image: x (times the style s, or s == nullptr) as three bf16 parts per value in 16-byte units of 8 channels,
-// [B][Cin / 32][H + 2][part * 4 + k-group][W + 8]: upfirr_units_bytes(B, Cin, H, W) bytes
-size_t upfirr_units_bytes(int B, int cin, int H, int W);
-hipError_t launch_upfirr_split_activation(const float* x, long long x_b_stride, const float* s, int s_stride, void* out, int B, int cin, int H, int W, hipStream_t stream);
-
 // The two smallest up layers (4x4 -> 8x8, 8x8 -> 16x16) in scatter form (gemm_forms.hip): pack (x * style -> the GEMM's B image),
 // ONE dense GEMM P[tap slot * Cout + co][b H W + position] (M = 9 Cout, K = Cin), gather (taps of a class, x demod) into the parity
 // planes the FIR pass reads. Replaces the transposed-conv launch where the position grid tiles badly (81 of 256 tile slots).
@@ -252,7 +240,7 @@ struct UpGemmArgs {
     long long x_b_stride, cls_stride, unit_stride;
     int B, Cin, Cout, H, W, s_stride, d_stride;
     int n_tiles;  // upgemm_n_tiles(B, H, W)
-    int bf16_split;  // experiment (0 off): 1 = three bf16 parts per value, six product terms; 2 = two fp16 parts, three terms. w is upgemm_arrange_weights_split's image
+    int bf16_split;  // experiment (0 off): 1 = three bf16 parts per value, six product terms. w is upgemm_arrange_weights_split's image
 };
 // GEMM columns (samples x input positions) of a layer with `cout` channels that the engine's product buffer holds: 9 x 512 x `columns_512`
 // floats (engine.hip upgemm_buffer_columns(): 16384 = 302 MB = 16 frames at 32x32 (512 channels), 8 at 64x64 (256 channels), 4 at 128x128 (128))
@@ -263,7 +251,7 @@ int upgemm_n_tiles(int B, int H, int W);
 size_t upgemm_packed_floats(int B, int cin, int H, int W);
 size_t upgemm_prod_floats(int B, int cout, int H, int W);
 void upgemm_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int cin, int cout, const int* up_tap_weight, float* w_out);
-void upgemm_arrange_weights_split(const float* w_in, int cin, int cout, const int* up_tap_weight, int mode, void* w_out /* 1.5 x upgemm_weight_floats floats */);
+void upgemm_arrange_weights_split(const float* w_in, int cin, int cout, const int* up_tap_weight, void* w_out /* 1.5 x upgemm_weight_floats floats */);
 hipError_t launch_upgemm(const UpGemmArgs& args, hipStream_t stream);
 
 // The stride-1 layers at 8x8 and 16x16 in Winograd F(4x4, 3x3) GEMM form (gemm_forms.hip): input transform into 36 B images, the
@@ -283,7 +271,7 @@ struct WinoGemmArgs {
     int noise_b_stride;
     int B, Cin, Cout, H, W, s_stride, d_stride;
     int n_tiles;  // winogemm_n_tiles(B, H, W)
-    int bf16_split;  // experiment (0 off, 1 bf16 x 3, 2 fp16 x 2): w is winogemm_arrange_weights_split's image
+    int bf16_split;  // experiment (0 off, 1 bf16 x 3): w is winogemm_arrange_weights_split's image
 };
 constexpr int kWinoGemmMaxColumns = 1024;  // GEMM columns (samples x 4x4 tiles) the engine's buffers hold: 64 frames at 16x16, 4 at 64x64, 1 at 128x128
 bool winogemm_supported(int cin, int cout, int H, int W);
@@ -292,7 +280,7 @@ int winogemm_n_tiles(int B, int H, int W);
 size_t winogemm_packed_floats(int B, int cin, int H, int W);
 size_t winogemm_prod_floats(int B, int cout, int H, int W);
 void winogemm_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int cin, int cout, float* w_out);
-void winogemm_arrange_weights_split(const float* w_in, int cin, int cout, int mode, void* w_out /* 1.5 x winogemm_weight_floats floats */);
+void winogemm_arrange_weights_split(const float* w_in, int cin, int cout, void* w_out /* 1.5 x winogemm_weight_floats floats */);
 hipError_t launch_winogemm(const WinoGemmArgs& args, hipStream_t stream);
 
 // ---- aux_kernels.hip ----

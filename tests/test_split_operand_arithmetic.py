@@ -1,5 +1,5 @@
 """
-The arithmetic of the split-operand up kernels (gance_amd/csrc/upfir_split.hip, upfir_split_roles.hip), restated in numpy and pinned on
+The arithmetic of the split-operand up kernels (gance_amd/csrc/upfir_split.hip), restated in numpy and pinned on
 the CPU: why six bf16 x bf16 part products per fp32 product are "fp32 arithmetic" in the contract's sense.
 
 * x = x0 + x1 + x2 EXACTLY, each part the round-to-nearest-even bfloat16 of what is left -- for every finite float32 whose parts stay

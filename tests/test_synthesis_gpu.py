@@ -231,18 +231,17 @@ def test_fused_upsampling_layer_matches_oracle_layerwise(library, resolution: in
 
 
 @pytest.mark.parametrize(
-    "resolution,batch,noise,conv_form,roles",
+    "resolution,batch,noise,conv_form,private_workspace",
     [
         (128, 3, True, "auto", 0),
         (256, 2, True, "winograd43", 0),
         (256, 3, False, "winograd43", 0),
         (256, 2, True, "direct", 0),
         (512, 1, True, "winograd43", 0),
-        (256, 2, True, "winograd43", 1),
         (256, 3, False, "direct", 1),
     ],
 )
-def test_split_operand_up_layers_match_oracle_layerwise(library, resolution: int, batch: int, noise: bool, conv_form: str, roles: int, monkeypatch) -> None:
+def test_split_operand_up_layers_match_oracle_layerwise(library, resolution: int, batch: int, noise: bool, conv_form: str, private_workspace: int, monkeypatch) -> None:
     """
     Conv0_up with its K loop on the bf16 matrix cores from SPLIT operands (upfir_split.hip: every fp32 value as three bf16
     parts, the six largest part products, fp32 accumulation), forced at a small batch (GANCE_TUNE_UPFIR_SPLIT=2; the default takes
@@ -250,18 +249,15 @@ def test_split_operand_up_layers_match_oracle_layerwise(library, resolution: int
     oracle, every term on. Inputs 64 ... 256 wide: one, two and four strips (recomputed halo columns from the per-chunk side
     buffer), 2 ... 16 chunks of 32 input channels, pre-scaled input ("winograd43": the F(4x4,3x3) launch before it folds the style
     into its stores) and plain input (the style multiplied in while staging), with and without noise.
-    `roles` 1: the experiment GANCE_TUNE_UPFIR_SPLIT_ROLES (upfir_split_roles.hip: the same products with a block's work in two wave
-    roles -- matrix waves and vector waves -- behind a pass that splits the layer's input; launch names end in "/s3r"), same bar.
+    `private_workspace` 1: the engine allocates a workspace of its own (GANCE_FLAG_PRIVATE_WORKSPACE) instead of joining the shared one.
     """
     monkeypatch.setenv("GANCE_TUNE_UPFIR_SPLIT", "2")  # (read when the engine is created)
-    monkeypatch.setenv("GANCE_TUNE_UPFIR_SPLIT_ROLES", str(roles))
     spec = sg2_spec.make_spec(resolution)
     variables = sg2_spec.make_random_variables(resolution, seed=3, perturb=True)
     if not noise:
         variables = {name: (np.zeros_like(value) if name.endswith("/noise_strength") else value) for name, value in variables.items()}
     dlatents = np.random.RandomState(5).randn(batch, spec.num_layers, 512).astype(np.float32)
-    # (the experiment's input image lives in the workspace: an engine that joined a workspace made without it would go without it too)
-    engine = hip_lib.Engine(variables, resolution, max_batch=batch, up_form="fused", conv_form=conv_form, profile=True, private_workspace=bool(roles))
+    engine = hip_lib.Engine(variables, resolution, max_batch=batch, up_form="fused", conv_form=conv_form, profile=True, private_workspace=bool(private_workspace))
 
     def layers_of_the_oracle():
         collected: list = []
@@ -269,7 +265,7 @@ def test_split_operand_up_layers_match_oracle_layerwise(library, resolution: int
             ref.g_synthesis(torch.from_numpy(dlatents).double(), variables, resolution, collect=collected)
         return collected
 
-    wants = _oracle_once(("split_up_layerwise", resolution, batch, noise), layers_of_the_oracle)  # (shared by the two kernels: same seeds)
+    wants = _oracle_once(("split_up_layerwise", resolution, batch, noise), layers_of_the_oracle)  # (shared by the conv forms: same seeds)
     try:
         worst = 0.0
         for n, conv in enumerate(spec.convs, start=1):
@@ -281,7 +277,7 @@ def test_split_operand_up_layers_match_oracle_layerwise(library, resolution: int
             worst = max(worst, rel)
             assert rel < 2e-5, f"conv layer {n} ({conv.scope}): rel err {rel}"
         engine.synthesize_w(dlatents)
-        split = [step.name for step in engine.steps() if step.name.endswith("/s3r" if roles else "/s3")]
+        split = [step.name for step in engine.steps() if step.name.endswith("/s3")]
         assert len(split) == int(np.log2(resolution)) - 6, split  # every up layer whose input is >= 64 wide
         print(f"\nsplit-operand up layers at {resolution}^2, batch {batch}: worst layer {worst:.2e} of its range")
     finally:
@@ -320,7 +316,7 @@ def test_split_operand_up_layer_keeps_the_fp32_exponent_range(library, log2_scal
         print(f"\nsplit-operand up layer, weights x 2^{log2_scale}: range {np.abs(want).max():.3e}, rel err {rel:.2e}")
         assert rel < 2e-5, f"weights x 2^{log2_scale}: rel err {rel}"
         engine.synthesize_w(dlatents)
-        assert any(step.name.endswith(("/s3", "/s3r")) for step in engine.steps())
+        assert any(step.name.endswith("/s3") for step in engine.steps())
     finally:
         engine.close()
 
@@ -335,8 +331,9 @@ def test_smallest_up_layers_in_scatter_form_match_oracle_layerwise(library, reso
     The stride-1 layers at 8x8 / 16x16 of these networks run in the Winograd GEMM form from 64 columns up (the same GEMM kernel).
     (64, 2) and (128, 1): calls too small for the fused F(4x4,3x3) kernel to fill the chip take the Winograd GEMM form at 32x32 ... 128x128 too
     (up to 1024 GEMM columns: what one frame per call -- the reference's call pattern -- runs on).
-    `split` 1 / 2: the experiment GANCE_TUNE_GEMM_BF16X6 (the same products on the 16-bit matrix cores from operands split into three
-    bf16 parts, six product terms -- or two fp16 parts, three terms --, fp32 accumulation) must meet the SAME bars.
+    `split` 1: the experiment GANCE_TUNE_GEMM_BF16X6 (the same products on the bf16 matrix cores from operands split into three
+    bf16 parts, six product terms, fp32 accumulation) must meet the SAME bars. `split` 2, the value of a removed fp16 x 2 mode, must
+    too: any non-zero value selects bf16 x 3.
     """
     if split:
         monkeypatch.setenv("GANCE_TUNE_GEMM_BF16X6", str(split))  # (read when the engine is created)
@@ -685,9 +682,9 @@ STRESS_RELATIVE_TOLERANCE = 1e-4
 @pytest.mark.parametrize("conv_form,split_mode", [("direct", 0), ("winograd", 0), ("winograd43", 0), ("winograd43", 2)])
 def test_stress_network_256_layerwise_and_image(library, conv_form: str, split_mode: int, monkeypatch) -> None:
     """
-    ... `split_mode` 1 / 2: the experiment GANCE_TUNE_GEMM_BF16X6 on the layers this call runs as dense GEMMs (Winograd at 32^2 / 64^2, the
-    scatter form of four up layers at two frames per call): fp32 products from three bf16 / two fp16 parts per operand. The stress
-    network is where fp16's exponent range would show (|style| ~ 10, weight scales over 10^+-1).
+    ... `split_mode` 2: the experiment GANCE_TUNE_GEMM_BF16X6 on the layers this call runs as dense GEMMs (Winograd at 32^2 / 64^2, the
+    scatter form of four up layers at two frames per call): fp32 products from three bf16 parts per operand. (2 was a removed fp16 x 2
+    mode; any non-zero value selects bf16 x 3, so a stale setting meets the same bars.)
     """
     resolution, batch = 256, 2
     spec = sg2_spec.make_spec(resolution)
