@@ -5,6 +5,7 @@ Benchmark of the hot path on MI355X: synthesized frames/sec at 1024x1024 config-
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs
+    python bench.py --gpus 1 --steps K --warmup W --full
 
 Workload = BASELINE.json configs[1]: FFHQ config-f 1024x1024, random-init weights (seed 0),
 batched random-z synthesis. One step = one batch of `--batch` z vectors (already resident in HBM)
@@ -16,11 +17,17 @@ with the next step.
 With --dump-outputs DIR, rank 0 writes the frames of the last timed step (every rank's, in frame order) to DIR as
 float32 .npy files after the timed region: see dump_outputs(). Inputs are seeded, so two builds compare file by file.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     -- the dominant kernel (modulated conv on the fp32 matrix cores) timed with HIP
-                  events on the launch stream during the timed region
+Prints ONE JSON line on rank 0 (the headline: metric, value, unit, higher_is_better, dtype, ms_per_step) with
+  roofline     -- the dominant kernel timed with HIP events on the launch stream during the timed region
+
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs, the line. What takes runs of its own
+waits for --full, which adds to the same line:
+  roofline.all_conv_launches, roofline.whole_path_frac
+               -- from one more, untimed, step with every launch bracketed (--print-steps runs it too)
   cpu_baseline -- the CPU oracle (oracle/stylegan2_ref.py, torch fp32, all host cores) on a
                   bounded sample of the same workload; rank 0, N = 1 only. Baseline, not target.
+  extras       -- the product-stream configurations, the one-frame latency and the batch sweep (N = 1), or
+                  the N-rank product-stream configurations (N > 1); see main()
 """
 
 import argparse
@@ -536,14 +543,19 @@ def main() -> int:
     parser.add_argument("--warmup", type=int, default=3)
     parser.add_argument("--batch", type=int, default=64, help="frames per step per GPU (the engine's maximum; 32: -2 %%, 16: -8 %%)")
     parser.add_argument("--resolution", type=int, default=1024)
-    parser.add_argument("--no-cpu-baseline", action="store_true")
+    parser.add_argument(
+        "--full", action="store_true",
+        help="synthesis workload: also measure what takes runs of its own (all-conv roofline figures, cpu_baseline, extras); "
+        "off: only the headline line",
+    )
+    parser.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     parser.add_argument(
         "--all-terms", action="store_true",
         help="random weights with every noise strength and bias non-zero (StyleGAN2's own init has them at zero and the engine skips "
         "absent noise): what a trained network costs; not the contract line",
     )
-    parser.add_argument("--no-extras", action="store_true", help="skip the extra measurements (configs[2], 3 networks, 2160 output, one-frame latency) a 1-GPU run adds to the line")
-    parser.add_argument("--print-steps", action="store_true", help="per-launch table on stderr")
+    parser.add_argument("--no-extras", action="store_true", help="with --full: skip the extra measurements (configs[2], 3 networks, 2160 output, one-frame latency) a 1-GPU run adds to the line")
+    parser.add_argument("--print-steps", action="store_true", help="per-launch table of one more, untimed, step on stderr")
     parser.add_argument(
         "--workload", choices=["synthesis", "blend"], default="synthesis",
         help="synthesis = BASELINE configs[1] (the contract line); blend = configs[2]: 30 s synthetic WAV -> "
@@ -562,7 +574,7 @@ def main() -> int:
         help="N > 1 GPUs: cap RCCL at this many channels (NCCL_MAX_NCHANNELS = NCCL_MIN_NCHANNELS = N, set before the process group exists): "
         "fewer copy kernels holding CUs while a gather overlaps the synthesis, for longer; 0 = RCCL's default (the first A/B on a node)",
     )
-    parser.add_argument("--batch-sweep", default="1,4,8,16,32,64", help="batch sizes of extras.batch_sweep (SURVEY.md section 8(d) config 2); empty: skip")
+    parser.add_argument("--batch-sweep", default="1,4,8,16,32,64", help="with --full: batch sizes of extras.batch_sweep (SURVEY.md section 8(d) config 2); empty: skip")
     parser.add_argument(
         "--dump-outputs", type=Path, default=None, metavar="DIR",
         help="synthesis workload: after the timed steps, write the frames of the last one to DIR as float32 .npy (first and last "
@@ -669,23 +681,28 @@ def main() -> int:
     dominant_name = timed[0].name
     dominant = hip_lib.StepInfo(dominant_name, sum(s.ms for s in timed) / len(timed), timed[0].flops, timed[0].bytes)
 
-    # one more, untimed, step with every launch bracketed: the per-launch table and the all-conv figure
-    engine.set_profiling(True)
-    step(args.steps)
-    fence()
-    steps_info = engine.steps()
-    conv_steps = [s for s in steps_info if s.flops > 0 and s.name.startswith("conv")]
-    conv_ms = sum(s.ms for s in conv_steps)
-    conv_flops = sum(s.flops for s in conv_steps)
-    # Winograd F(2x2,3x3) launches ("convW..."): flops above are the ALGORITHMIC (direct-form) ones; the
-    # matrix cores execute 4/9 of them
-    executed_flops = sum(s.flops * executed_fraction(s.name) for s in conv_steps if not s.name.endswith(SPLIT_SUFFIXES))  # on the fp32 matrix pipe
+    # --full / --print-steps: one more, untimed, step with every launch bracketed: the per-launch table and the all-conv figure.
+    # Otherwise the launch names (the dtype) come from the last warm-up step, bracketed the same way at the same batch: the same forms.
+    launch_table = args.full or args.print_steps
+    conv_steps = warm_steps
+    if launch_table or not warm_steps:
+        engine.set_profiling(True)
+        step(args.steps)
+        fence()
+        steps_info = engine.steps()
+        conv_steps = [s for s in steps_info if s.flops > 0 and s.name.startswith("conv")]
     split_steps = [s for s in conv_steps if s.name.endswith(SPLIT_SUFFIXES)]
-    # matrix-pipe time the step's products need at the pipes' peaks (each launch on its own pipe) -- over the wall time: the utilisation
-    pipe_seconds = sum(s.flops * executed_fraction(s.name) / (matrix_peak(s.name) * 1e12) for s in conv_steps)
-    winograd_launches = sum(1 for s in conv_steps if s.name.startswith(("convW", "convV")))
-    winograd43_launches = sum(1 for s in conv_steps if s.name.startswith("convV"))
-    total_ms = sum(s.ms for s in steps_info)
+    if launch_table:
+        conv_ms = sum(s.ms for s in conv_steps)
+        conv_flops = sum(s.flops for s in conv_steps)
+        # Winograd F(2x2,3x3) launches ("convW..."): flops above are the ALGORITHMIC (direct-form) ones; the
+        # matrix cores execute 4/9 of them
+        executed_flops = sum(s.flops * executed_fraction(s.name) for s in conv_steps if not s.name.endswith(SPLIT_SUFFIXES))  # on the fp32 matrix pipe
+        # matrix-pipe time the step's products need at the pipes' peaks (each launch on its own pipe) -- over the wall time: the utilisation
+        pipe_seconds = sum(s.flops * executed_fraction(s.name) / (matrix_peak(s.name) * 1e12) for s in conv_steps)
+        winograd_launches = sum(1 for s in conv_steps if s.name.startswith(("convW", "convV")))
+        winograd43_launches = sum(1 for s in conv_steps if s.name.startswith("convV"))
+        total_ms = sum(s.ms for s in steps_info)
     if args.print_steps and rank == 0:
         for info in steps_info:
             tflops = info.flops / (info.ms * 1e-3) / 1e12 if info.ms > 0 else 0.0
@@ -744,35 +761,37 @@ def main() -> int:
                     "algorithmic_achieved": round(dominant.bytes / (dominant.ms * 1e-3) / 1e9, 1),
                     "algorithmic_frac": round(dominant.bytes / (dominant.ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 },
-                "all_conv_launches": {
-                    # executed matrix-core flops of all conv launches over their summed durations (Winograd launches
-                    # count 4/9 of their direct-form flops: that is what runs)
-                    "frac": round(pipe_seconds / (conv_ms * 1e-3), 4),
-                    "frac_note": "time the launches' executed products need at the dense peak of the matrix pipe each runs on (fp32 MFMA 157.3 TFLOP/s; "
-                    "the %d split-operand launches: bf16 MFMA 2516.6 TFLOP/s, six part products per fp32 product) over their measured time" % len(split_steps),
-                    "fp32_pipe_achieved": round(executed_flops / (sum(s.ms for s in conv_steps if not s.name.endswith(SPLIT_SUFFIXES)) * 1e-3) / 1e12, 3),
-                    "bf16_pipe_achieved": round(sum(6.0 * s.flops for s in split_steps) / (sum(s.ms for s in split_steps) * 1e-3) / 1e12, 3) if split_steps else None,
-                    "algorithmic_direct_form": round(conv_flops / (conv_ms * 1e-3) / 1e12, 3),
-                    "share_of_step_time": round(conv_ms / total_ms, 4),
-                    "winograd_launches": winograd_launches,
-                    "note": "%d of the %d conv launches run in Winograd form (%d of them F(4x4,3x3): 1/4 of their direct-form flops executed; the others F(2x2,3x3): 4/9); "
-                    "algorithmic_direct_form prices every launch as a direct convolution and may exceed the peak" % (winograd_launches, len(conv_steps), winograd43_launches),
-                },
-                # the whole step (mapping, styles, ToRGB, uint8 included) against the matrix peak: executed flops of a
-                # step over its wall time; and the same in direct-form flops, the work a direct implementation would do
-                "whole_path_frac": round(pipe_seconds / (elapsed / args.steps), 4),
+                # the whole step (mapping, styles, ToRGB, uint8 included) in direct-form flops, the work a direct implementation would do,
+                # over its wall time against the fp32 matrix peak
                 "whole_path_direct_form_frac": round(
                     (fps / world_size) * ALGORITHMIC_GFLOP_PER_FRAME_1024 * (resolution / 1024) ** 2 / 1e3 / FP32_MFMA_PEAK_TFLOPS, 4
                 ),
             },
         }
+        if launch_table:
+            result["roofline"]["all_conv_launches"] = {
+                # executed matrix-core flops of all conv launches over their summed durations (Winograd launches
+                # count 4/9 of their direct-form flops: that is what runs)
+                "frac": round(pipe_seconds / (conv_ms * 1e-3), 4),
+                "frac_note": "time the launches' executed products need at the dense peak of the matrix pipe each runs on (fp32 MFMA 157.3 TFLOP/s; "
+                "the %d split-operand launches: bf16 MFMA 2516.6 TFLOP/s, six part products per fp32 product) over their measured time" % len(split_steps),
+                "fp32_pipe_achieved": round(executed_flops / (sum(s.ms for s in conv_steps if not s.name.endswith(SPLIT_SUFFIXES)) * 1e-3) / 1e12, 3),
+                "bf16_pipe_achieved": round(sum(6.0 * s.flops for s in split_steps) / (sum(s.ms for s in split_steps) * 1e-3) / 1e12, 3) if split_steps else None,
+                "algorithmic_direct_form": round(conv_flops / (conv_ms * 1e-3) / 1e12, 3),
+                "share_of_step_time": round(conv_ms / total_ms, 4),
+                "winograd_launches": winograd_launches,
+                "note": "%d of the %d conv launches run in Winograd form (%d of them F(4x4,3x3): 1/4 of their direct-form flops executed; the others F(2x2,3x3): 4/9); "
+                "algorithmic_direct_form prices every launch as a direct convolution and may exceed the peak" % (winograd_launches, len(conv_steps), winograd43_launches),
+            }
+            # the whole step against the matrix peaks: the executed flops of a step over its wall time
+            result["roofline"]["whole_path_frac"] = round(pipe_seconds / (elapsed / args.steps), 4)
         if last_frames is not None:
             result["dumped_outputs"] = dump_outputs(args.dump_outputs, last_frames)
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(resolution, variables)
     engine.close()
     extras = None
-    if not args.no_extras and world_size == 1:
+    if args.full and not args.no_extras and world_size == 1:
         # measured beside the contract line, same process, same GPU (each is also reachable alone: --workload blend)
         extras = {
             "config_2_blend_stream": guarded(product_stream_measurement, METRIC_CONFIG_2, resolution, batch, 1, None, device, not args.no_cpu_baseline),
@@ -783,7 +802,7 @@ def main() -> int:
         }
         if args.batch_sweep and not args.all_terms:
             extras["batch_sweep"] = guarded(batch_sweep, resolution, variables, device, [int(b) for b in args.batch_sweep.split(",") if int(b) <= batch])
-    elif not args.no_extras and not rehearsal_skips_extras():
+    elif args.full and not args.no_extras and not rehearsal_skips_extras():
         # N GPUs: BASELINE.json configs[3] (2160^2 output, frame-sharded, both drains) and configs[4] (three networks + overlay gate) through
         # the product stream, collectively, beside the weak-scaling line. A watchdog guarantees the contract line: should a
         # collective of the extras hang (a rank lost), rank 0 prints the line without them and every rank leaves.

@@ -1,10 +1,13 @@
 """
 bench.py's host-side bookkeeping (no GPU): how a launch of the engine's step table maps to a kernel and to the flops
-the matrix cores execute, and that the committed traffic record answers for the launches that can be dominant.
+the matrix cores execute, and that the committed traffic record answers for the launches that can be dominant. On the GPU:
+what a plain run and a --full run print.
 """
 import importlib.util
 import json
 from pathlib import Path
+
+import pytest
 
 REPO_ROOT = Path(__file__).resolve().parent.parent
 
@@ -109,3 +112,33 @@ def test_dump_outputs_writes_float_arrays_of_the_step_within_the_budget(tmp_path
     assert np.array_equal(np.load(tmp_path / "a" / "frame_last.npy"), frames.numpy()[-1].astype(np.float32))
     # the default workload (64 frames of 1024 x 1024 x 3): two float32 frames + the sample and its float64 positions
     assert 2 * 1024 * 1024 * 3 * 4 + bench.DUMP_SAMPLE_SIZE * (4 + 8) <= 64 * 2**20
+
+
+def _bench_line(*arguments: str) -> dict:
+    import subprocess  # pylint: disable=import-outside-toplevel
+    import sys  # pylint: disable=import-outside-toplevel
+
+    result = subprocess.run(
+        [sys.executable, str(REPO_ROOT / "bench.py"), *arguments], capture_output=True, text=True, cwd=REPO_ROOT, timeout=300, check=False
+    )
+    assert result.returncode == 0, result.stderr[-2000:]
+    return json.loads(result.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone_and_full_adds_the_launch_table() -> None:
+    """
+    A plain run is set-up, warm-up, the timed steps and the line: no cpu_baseline, no extras, no all-conv figures. Its dtype
+    comes from the launch names of the last warm-up step; a --full run takes them from its extra, untimed step.
+    """
+    plain = _bench_line("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["higher_is_better"] is True and plain["unit"] == "frames/s" and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - 16 * 1e3 / plain["ms_per_step"]) < 1e-3 * plain["value"]
+    assert "cpu_baseline" not in plain and "extras" not in plain
+    assert "all_conv_launches" not in plain["roofline"] and "whole_path_frac" not in plain["roofline"]
+    assert plain["roofline"]["launches_averaged"] >= 2
+    full = _bench_line("--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline", "--no-extras")
+    assert full["dtype"] == plain["dtype"]
+    assert full["roofline"]["all_conv_launches"]["winograd_launches"] > 0 and full["roofline"]["whole_path_frac"] > 0

@@ -6,7 +6,7 @@ batches=$1
 shift
 for cfg in "$@"; do
   wino=${cfg%,*}; up=${cfg#*,}
-  GANCE_TUNE_WINOGEMM=$wino GANCE_TUNE_UPGEMM=$up python bench.py --no-cpu-baseline --steps 5 --warmup 2 --batch-sweep $batches 2>/dev/null | python -c "
+  GANCE_TUNE_WINOGEMM=$wino GANCE_TUNE_UPGEMM=$up python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --batch-sweep $batches 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); bs=r['extras']['batch_sweep']['by_batch']
 print('wino $wino up $up:', {b: bs[b]['frames_per_s'] for b in bs})"

@@ -29,7 +29,7 @@ cp $(find $out/${tag}_audio_trace -name "*kernel_stats.csv" | head -1) $out/${ta
 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --print-steps > $out/${tag}_bench.json 2> $out/${tag}_steps.txt
 python3 tools/make_traffic_record.py ${tag} $out && cp profiles/traffic_latest.json $out/${tag}_traffic_latest.json
 # the un-profiled default line last: its roofline.traffic then comes from THIS set's record
-python3 bench.py --steps 20 --warmup 3 --print-steps > $out/${tag}_bench.json 2> $out/${tag}_steps.txt
+python3 bench.py --steps 20 --warmup 3 --full --print-steps > $out/${tag}_bench.json 2> $out/${tag}_steps.txt
 # the raw traces are large: keep the summaries only
 rm -rf $out/${tag}_trace $out/${tag}_audio_trace $out/${tag}_pmc_fetch $out/${tag}_pmc_write $out/${tag}_pmc_sq $out/${tag}_pmc_valu
 head -5 $out/${tag}_kernel_stats.csv; cat $out/${tag}_bench.json | head -c 600

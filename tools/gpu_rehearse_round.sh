@@ -16,7 +16,7 @@ run2 29519 tools/rehearse_stream_ranks.py --check /tmp/rehearsal_b >> $out/${tag
 grep -E "ranks on one GPU|single rank|FAILED" $out/${tag}_rehearsal_2ranks_overlay.log
 unset GANCE_REHEARSAL
 # bench.py as the driver launches it on a node, two ranks on this one GPU: the weak-scaling line + the N-rank extras (configs[3] both drains, configs[4] + overlay)
-GANCE_BENCH_REHEARSAL=1 run2 29520 bench.py --gpus 2 --steps 3 --warmup 1 --batch 32 > $out/${tag}_rehearsal_bench_2ranks.json 2> $out/${tag}_rehearsal_bench_2ranks.err || echo "FAILED bench --gpus 2"
+GANCE_BENCH_REHEARSAL=1 run2 29520 bench.py --gpus 2 --steps 3 --warmup 1 --batch 32 --full > $out/${tag}_rehearsal_bench_2ranks.json 2> $out/${tag}_rehearsal_bench_2ranks.err || echo "FAILED bench --gpus 2"
 python - <<PY
 import json
 line = open("$out/${tag}_rehearsal_bench_2ranks.json").read().strip().splitlines()[-1]
