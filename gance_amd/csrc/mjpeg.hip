@@ -1,0 +1,664 @@
+// Baseline JPEG (JFIF, 4:2:2, standard Huffman tables, one restart interval per MCU row) of uint8 frames in HBM:
+// gance_jpeg_encode_bounds and gance_jpeg_encode_u8 of include/gance_hip.h. The arithmetic is libjpeg's "islow" path, so
+// libjpeg decodes our files to exactly the pixels it decodes from its own encode at the same quality:
+//
+//   RGB -> YCbCr        jccolor.c rgb_ycc_convert: 16-bit fixed point, Y rounded half up, Cb/Cr with ONE_HALF - 1
+//   4:2:2 downsampling  jcsample.c h2v1_downsample: (a + b + bias) >> 1, bias 0 / 1 on even / odd output columns
+//   forward DCT         jfdctint.c jpeg_fdct_islow: Loeffler-Ligtenberg-Moschytz, CONST_BITS 13, PASS1_BITS 2
+//   quantisation        jcdctmgr.c: sign(c) * ((|c| + d/2) / d) with d = 8 q, exact (multiply-high by ceil(2^32 / d))
+//   quality scaling     jcparam.c jpeg_quality_scaling + jpeg_add_quant_table (force_baseline)
+//   Huffman coding      jchuff.c encode_one_block with the Annex K tables, restart markers as emit_restart
+//
+// Four launches, all on the caller's stream, deterministic (no atomics, no order-dependent reduction):
+//   1. mjpeg_transform_kernel  one thread per 8x8 block: colour, downsampling, DCT, quantisation -> int16 zigzag
+//   2. mjpeg_huffman_kernel    one thread per block: its Huffman bits (DC as a difference to the previous block of the
+//                              same component inside the MCU row) into a private 52-word slot + the bit count
+//   3. mjpeg_segment_kernel    one workgroup per restart segment (one MCU row of one frame): scan of the bit counts,
+//                              every output word gathered from the blocks that overlap it, 1-padding, 0xFF 0x00
+//                              stuffing by a second scan, bytes into the segment's slot
+//   4. mjpeg_frame_layout_kernel, mjpeg_frame_offsets_kernel, mjpeg_pack_kernel   block scans of the segment sizes
+//                              per frame and of the frame sizes, then header + segments + RSTn + EOI per frame, frames
+//                              back to back
+// Every buffer is sized for the worst case (a block is at most 1660 bits before stuffing), so nothing can truncate.
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/gance_hip.h"
+#include "kernels.h"
+
+namespace gance_mjpeg {
+
+constexpr int kMaxSide = 8192;            // segments of up to 2048 blocks: their bit offsets fit the segment kernel's LDS
+constexpr int kMaxBlockBits = 1660;       // 16 + 11 (DC) + 63 x (16 + 10) (AC)
+constexpr int kBlockWords = 52;           // ceil(1660 / 32)
+constexpr int kSegmentThreads = 256;
+constexpr int kMaxSegmentBlocks = 4 * (kMaxSide / 16);
+constexpr int kHeaderCapacity = 640;
+
+// ---- tables ----------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int natural_of_zigzag(int i) {
+    constexpr int order[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return order[i];
+}
+
+// Annex K.1 quantisation tables, natural order
+constexpr int kBaseQuant[2][64] = {
+    {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24,  40,  57,
+     69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35,  55,  64,
+     81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+     99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// Annex K.3 Huffman tables: code counts per length 1..16, then the symbols
+constexpr uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr uint8_t kDcValues[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+constexpr uint8_t kAcLumaValues[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14,
+    0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09,
+    0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a,
+    0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65,
+    0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88,
+    0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9,
+    0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca,
+    0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea,
+    0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+constexpr uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+constexpr uint8_t kAcChromaValues[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32,
+    0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16,
+    0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39,
+    0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64,
+    0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86,
+    0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7,
+    0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8,
+    0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9,
+    0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+// Encoder view of a table (jchuff.c jpeg_make_c_derived_tbl): code and length per symbol (length 0 = unused)
+struct HuffTable {
+    uint16_t code[256];
+    uint8_t size[256];
+};
+struct HuffTables {
+    HuffTable dc[2], ac[2];  // [0] luma, [1] chroma
+};
+
+constexpr HuffTable derive(const uint8_t* bits, const uint8_t* values) {
+    HuffTable table{};
+    int code = 0, k = 0;
+    for (int length = 1; length <= 16; ++length) {
+        for (int i = 0; i < bits[length - 1]; ++i, ++k) {
+            table.code[values[k]] = (uint16_t)code++;
+            table.size[values[k]] = (uint8_t)length;
+        }
+        code <<= 1;
+    }
+    return table;
+}
+
+constexpr HuffTables make_tables() {
+    return HuffTables{{derive(kDcLumaBits, kDcValues), derive(kDcChromaBits, kDcValues)},
+                      {derive(kAcLumaBits, kAcLumaValues), derive(kAcChromaBits, kAcChromaValues)}};
+}
+
+__constant__ HuffTables kHuff = make_tables();
+
+// Quantisation of one quality, natural order: d / 2 and ceil(2^32 / d) with d = 8 q (the islow DCT's output is 8x)
+struct QuantArgs {
+    uint32_t half[2][64];
+    uint32_t magic[2][64];
+};
+
+// Table entries at `quality` (jpeg_set_quality with force_baseline), natural order
+static void scaled_table(int component, int quality, int out[64]) {
+    const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;
+    for (int i = 0; i < 64; ++i) {
+        long v = ((long)kBaseQuant[component][i] * scale + 50) / 100;
+        out[i] = (int)(v < 1 ? 1 : (v > 255 ? 255 : v));
+    }
+}
+
+static QuantArgs make_quant(int quality) {
+    QuantArgs args{};
+    for (int c = 0; c < 2; ++c) {
+        int table[64];
+        scaled_table(c, quality, table);
+        for (int i = 0; i < 64; ++i) {
+            const uint64_t d = 8ull * table[i];
+            args.half[c][i] = (uint32_t)(d / 2);
+            // exact for every dividend below 2^16 (|c| + d/2 < 2^15 here): ceil(2^32/d) d - 2^32 < d <= 2^16
+            args.magic[c][i] = (uint32_t)(((1ull << 32) + d - 1) / d);
+        }
+    }
+    return args;
+}
+
+struct Header {
+    uint8_t bytes[kHeaderCapacity];
+    int length;
+};
+
+// SOI, APP0 (JFIF 1.01, aspect 1:1), DQT x2 (zigzag), SOF0 (Y 2x1, Cb 1x1, Cr 1x1), DHT x4, DRI, SOS
+static Header make_header(int side, int quality) {
+    Header h{};
+    int n = 0;
+    auto put = [&](int v) { h.bytes[n++] = (uint8_t)v; };
+    auto put16 = [&](int v) { put(v >> 8); put(v & 0xFF); };
+    put16(0xFFD8);
+    put16(0xFFE0); put16(16);
+    for (char c : {'J', 'F', 'I', 'F', '\0'}) put(c);
+    put(1); put(1); put(0); put16(1); put16(1); put(0); put(0);
+    for (int c = 0; c < 2; ++c) {
+        int table[64];
+        scaled_table(c, quality, table);
+        put16(0xFFDB); put16(67); put(c);
+        for (int i = 0; i < 64; ++i) put(table[natural_of_zigzag(i)]);
+    }
+    put16(0xFFC0); put16(17); put(8); put16(side); put16(side); put(3);
+    put(1); put(0x21); put(0);
+    put(2); put(0x11); put(1);
+    put(3); put(0x11); put(1);
+    const uint8_t* bits[4] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
+    const uint8_t* values[4] = {kDcValues, kAcLumaValues, kDcValues, kAcChromaValues};
+    const int classes[4] = {0x00, 0x10, 0x01, 0x11};
+    for (int t = 0; t < 4; ++t) {
+        int count = 0;
+        for (int i = 0; i < 16; ++i) count += bits[t][i];
+        put16(0xFFC4); put16(2 + 1 + 16 + count); put(classes[t]);
+        for (int i = 0; i < 16; ++i) put(bits[t][i]);
+        for (int i = 0; i < count; ++i) put(values[t][i]);
+    }
+    put16(0xFFDD); put16(4); put16(side / 16);
+    put16(0xFFDA); put16(12); put(3);
+    put(1); put(0x00);
+    put(2); put(0x11);
+    put(3); put(0x11);
+    put(0); put(63); put(0);
+    h.length = n;
+    return h;
+}
+
+// ---- sizes -------------------------------------------------------------------------------------------------------
+struct Layout {
+    int64_t mcu_cols, mcu_rows, segment_blocks, segments, blocks;
+    int64_t segment_capacity;                       // stuffed bytes of a worst-case segment, rounded to 16
+    int64_t coef_bytes, bits_bytes, bitlen_bytes, slot_bytes, size_bytes, dst_bytes;
+    int64_t workspace_bytes, frame_capacity, out_capacity;
+};
+
+static int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
+
+static Layout layout_of(int64_t batch, int64_t side) {
+    Layout l{};
+    l.mcu_cols = side / 16;
+    l.mcu_rows = side / 8;
+    l.segment_blocks = 4 * l.mcu_cols;  // Y0 Y1 Cb Cr per MCU
+    l.segments = batch * l.mcu_rows;
+    l.blocks = l.segments * l.segment_blocks;
+    l.segment_capacity = round16(2 * ((l.segment_blocks * kMaxBlockBits + 7) / 8));  // every byte 0xFF, each stuffed
+    l.coef_bytes = round16(l.blocks * 64 * 2);
+    l.bits_bytes = round16(l.blocks * kBlockWords * 4);
+    l.bitlen_bytes = round16(l.blocks * 4);
+    l.slot_bytes = l.segments * l.segment_capacity;
+    l.size_bytes = round16(l.segments * 4);
+    l.dst_bytes = round16(l.segments * 4);
+    l.workspace_bytes = l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes + l.size_bytes + l.dst_bytes;
+    // header + segments + (rows - 1) RST markers + EOI
+    l.frame_capacity = kHeaderCapacity + l.mcu_rows * (2 * ((l.segment_blocks * kMaxBlockBits + 7) / 8)) + 2 * l.mcu_rows;
+    l.out_capacity = batch * l.frame_capacity;
+    return l;
+}
+
+// ---- 1. transform ------------------------------------------------------------------------------------------------
+constexpr int kConstBits = 13, kPass1Bits = 2;
+constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
+              FIX_0_899976223 = 7373, FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137,
+              FIX_1_961570560 = 16069, FIX_2_053119869 = 16819, FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+
+__host__ __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// jpeg_fdct_islow on one row / column: 8 values at stride `step`; `pass` 0 = rows, 1 = columns
+template <int pass>
+__host__ __device__ __forceinline__ void fdct_1d(int* d, int step) {
+    const int tmp0 = d[0 * step] + d[7 * step], tmp7 = d[0 * step] - d[7 * step];
+    const int tmp1 = d[1 * step] + d[6 * step], tmp6 = d[1 * step] - d[6 * step];
+    const int tmp2 = d[2 * step] + d[5 * step], tmp5 = d[2 * step] - d[5 * step];
+    const int tmp3 = d[3 * step] + d[4 * step], tmp4 = d[3 * step] - d[4 * step];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    constexpr int odd_shift = pass == 0 ? kConstBits - kPass1Bits : kConstBits + kPass1Bits;
+    if (pass == 0) {
+        d[0 * step] = (tmp10 + tmp11) * (1 << kPass1Bits);
+        d[4 * step] = (tmp10 - tmp11) * (1 << kPass1Bits);
+    } else {
+        d[0 * step] = descale(tmp10 + tmp11, kPass1Bits);
+        d[4 * step] = descale(tmp10 - tmp11, kPass1Bits);
+    }
+    int z1 = (tmp12 + tmp13) * FIX_0_541196100;
+    d[2 * step] = descale(z1 + tmp13 * FIX_0_765366865, odd_shift);
+    d[6 * step] = descale(z1 - tmp12 * FIX_1_847759065, odd_shift);
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * FIX_1_175875602;
+    const int t4 = tmp4 * FIX_0_298631336, t5 = tmp5 * FIX_2_053119869, t6 = tmp6 * FIX_3_072711026,
+              t7 = tmp7 * FIX_1_501321110;
+    z1 *= -FIX_0_899976223;
+    z2 *= -FIX_2_562915447;
+    z3 = z3 * -FIX_1_961570560 + z5;
+    z4 = z4 * -FIX_0_390180644 + z5;
+    d[7 * step] = descale(t4 + z1 + z3, odd_shift);
+    d[5 * step] = descale(t5 + z2 + z4, odd_shift);
+    d[3 * step] = descale(t6 + z2 + z3, odd_shift);
+    d[1 * step] = descale(t7 + z1 + z4, odd_shift);
+}
+
+__host__ __device__ __forceinline__ int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+// Cb (cr = false) or Cr of one pixel
+__host__ __device__ __forceinline__ int chroma(int r, int g, int b, bool cr) {
+    const int v = cr ? 32768 * r - 27439 * g - 5329 * b : -11059 * r - 21709 * g + 32768 * b;
+    return (v + (128 << 16) + 32767) >> 16;
+}
+
+// Block `kind` (0 / 1 = left / right Y, 2 = Cb, 3 = Cr) of the MCU at (mcu_row, mcu_col) of `frame` [side][side][3]:
+// level-shifted samples, DCT, quantisation; out[64] in zigzag order. `frame` rows are 16-byte aligned (side % 16 == 0).
+__host__ __device__ inline void transform_block(const uint8_t* __restrict__ frame, int side, int mcu_row, int mcu_col, int kind,
+                                                const QuantArgs& quant, int16_t* __restrict__ out) {
+    int d[64];
+    const int y0 = mcu_row * 8;
+    if (kind < 2) {
+        const int x0 = mcu_col * 16 + kind * 8;
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+            const uint2* row = (const uint2*)(frame + ((size_t)(y0 + y) * side + x0) * 3);  // 24 bytes, 8-byte aligned
+            uint8_t px[24];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint2 v = row[i];
+                for (int j = 0; j < 4; ++j) px[i * 8 + j] = (uint8_t)(v.x >> (8 * j)), px[i * 8 + 4 + j] = (uint8_t)(v.y >> (8 * j));
+            }
+#pragma unroll
+            for (int x = 0; x < 8; ++x) d[y * 8 + x] = luma(px[3 * x], px[3 * x + 1], px[3 * x + 2]) - 128;
+        }
+    } else {
+        const int x0 = mcu_col * 16;
+        const bool cr = kind == 3;
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+            const uint4* row = (const uint4*)(frame + ((size_t)(y0 + y) * side + x0) * 3);  // 48 bytes, 16-byte aligned
+            uint8_t px[48];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint4 v = row[i];
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                for (int k = 0; k < 4; ++k)
+                    for (int j = 0; j < 4; ++j) px[i * 16 + k * 4 + j] = (uint8_t)(w[k] >> (8 * j));
+            }
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                const int a = chroma(px[6 * x], px[6 * x + 1], px[6 * x + 2], cr);
+                const int b = chroma(px[6 * x + 3], px[6 * x + 4], px[6 * x + 5], cr);
+                d[y * 8 + x] = ((a + b + (x & 1)) >> 1) - 128;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) fdct_1d<0>(d + 8 * i, 1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) fdct_1d<1>(d + i, 8);
+    const int c = kind < 2 ? 0 : 1;
+#pragma unroll
+    for (int z = 0; z < 64; ++z) {
+        const int n = natural_of_zigzag(z);
+        const int v = d[n];
+        const uint32_t a = (uint32_t)(v < 0 ? -v : v) + quant.half[c][n];
+        const int q = (int)(((uint64_t)a * quant.magic[c][n]) >> 32);
+        out[z] = (int16_t)(v < 0 ? -q : q);
+    }
+}
+
+// Block index g (within the whole call) <-> (segment, position in the segment). Blocks of a segment are in MCU order:
+// MCU m holds positions 4m (Y left), 4m + 1 (Y right), 4m + 2 (Cb), 4m + 3 (Cr). Threads are numbered kind-major
+// inside a segment so that a wave works on one kind of block (one code path, adjacent pixels).
+__global__ void __launch_bounds__(256) mjpeg_transform_kernel(const uint8_t* __restrict__ frames, int side, int64_t mcu_rows,
+                                                              int64_t mcu_cols, int64_t blocks, QuantArgs quant,
+                                                              int16_t* __restrict__ coef) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= blocks) return;
+    const int64_t segment_blocks = 4 * mcu_cols;
+    const int64_t segment = t / segment_blocks;
+    const int within = (int)(t - segment * segment_blocks);
+    const int kind = within / (int)mcu_cols, mcu = within % (int)mcu_cols;
+    const int64_t frame = segment / mcu_rows;
+    const int row = (int)(segment - frame * mcu_rows);
+    int16_t out[64];
+    transform_block(frames + frame * side * side * 3, side, row, mcu, kind, quant, out);
+    uint4* dst = (uint4*)(coef + (segment * segment_blocks + 4 * mcu + kind) * 64);
+    const uint4* src = (const uint4*)out;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dst[i] = src[i];
+}
+
+// ---- 2. Huffman bits of one block ----------------------------------------------------------------------------------
+struct BitWriter {
+    uint64_t acc = 0;
+    int pending = 0, total = 0, word = 0;
+    uint32_t* out;
+    __host__ __device__ explicit BitWriter(uint32_t* o) : out(o) {}
+    __host__ __device__ __forceinline__ void put(uint32_t bits, int size) {  // size <= 16
+        acc = (acc << size) | (bits & ((1u << size) - 1));
+        pending += size;
+        total += size;
+        if (pending >= 32) {
+            pending -= 32;
+            out[word++] = (uint32_t)(acc >> pending);
+        }
+    }
+    __host__ __device__ __forceinline__ void finish() {
+        if (pending > 0) out[word++] = (uint32_t)(acc << (32 - pending));
+    }
+};
+
+__host__ __device__ __forceinline__ int bit_length(uint32_t v) { return v == 0 ? 0 : 32 - __builtin_clz(v); }
+
+// jchuff.c encode_one_block on a zigzag-ordered block. The AC loop walks the nonzero coefficients through a bit mask
+// (a loop over a runtime index of a local array would put the block in scratch); their values are re-read from
+// `block`, which is cached. `words` receives the bits MSB first; returns the bit count (<= kMaxBlockBits).
+__host__ __device__ inline int huffman_block(const int16_t* __restrict__ block, int previous_dc, const HuffTable& dc,
+                                             const HuffTable& ac, uint32_t* __restrict__ words) {
+    uint64_t nonzero = 0;
+    int dc_value = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint4 v = ((const uint4*)block)[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i == 0 && j == 0) dc_value = (int16_t)(w[0] & 0xFFFF);
+            nonzero |= (uint64_t)((w[j] & 0xFFFF) != 0) << (8 * i + 2 * j);
+            nonzero |= (uint64_t)((w[j] >> 16) != 0) << (8 * i + 2 * j + 1);
+        }
+    }
+    nonzero &= ~1ull;  // AC only
+    BitWriter w(words);
+    int temp = dc_value - previous_dc, temp2 = temp;
+    if (temp < 0) temp = -temp, --temp2;
+    int nbits = bit_length((uint32_t)temp);
+    w.put(dc.code[nbits], dc.size[nbits]);
+    if (nbits) w.put((uint32_t)temp2, nbits);
+    int last = 0;
+    while (nonzero) {
+        const int k = __builtin_ctzll(nonzero);
+        nonzero &= nonzero - 1;
+        int run = k - last - 1;
+        last = k;
+        while (run > 15) {
+            w.put(ac.code[0xF0], ac.size[0xF0]);
+            run -= 16;
+        }
+        temp = block[k];
+        temp2 = temp;
+        if (temp < 0) temp = -temp, --temp2;
+        nbits = bit_length((uint32_t)temp);
+        const int symbol = (run << 4) + nbits;
+        w.put(ac.code[symbol], ac.size[symbol]);
+        w.put((uint32_t)temp2, nbits);
+    }
+    if (last < 63) w.put(ac.code[0], ac.size[0]);
+    w.finish();
+    return w.total;
+}
+
+// Position `p` in a segment -> the position of the previous block of the same component (-1: the segment's first)
+__host__ __device__ __forceinline__ int previous_of(int p) {
+    const int mcu = p >> 2, kind = p & 3;
+    if (kind == 1) return p - 1;
+    if (mcu == 0) return -1;
+    return kind == 0 ? p - 3 : p - 4;
+}
+
+__global__ void __launch_bounds__(256) mjpeg_huffman_kernel(const int16_t* __restrict__ coef, int64_t mcu_cols, int64_t blocks,
+                                                            uint32_t* __restrict__ bits, int* __restrict__ bit_counts) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= blocks) return;
+    const int64_t segment_blocks = 4 * mcu_cols;
+    const int64_t segment = t / segment_blocks;
+    const int within = (int)(t - segment * segment_blocks);
+    const int kind = within / (int)mcu_cols, mcu = within % (int)mcu_cols;
+    const int p = 4 * mcu + kind;
+    const int64_t g = segment * segment_blocks + p;
+    const int previous = previous_of(p);
+    const int previous_dc = previous < 0 ? 0 : coef[(segment * segment_blocks + previous) * 64];
+    const int c = kind < 2 ? 0 : 1;
+    bit_counts[g] = huffman_block(coef + g * 64, previous_dc, kHuff.dc[c], kHuff.ac[c], bits + g * kBlockWords);
+}
+
+// ---- 3. one restart segment ----------------------------------------------------------------------------------------
+// Bits [32 w, 32 w + 32) of the segment, given the blocks' bit offsets (offsets[n] = total): OR of the overlapping
+// blocks' bits, then 1-padding past the end.
+__host__ __device__ inline uint32_t segment_word(const uint32_t* __restrict__ bits, const int* __restrict__ offsets, int n, int w) {
+    const int lo = 32 * w;
+    // last block starting at or before `lo` (offsets strictly increase: a block has >= 4 bits)
+    int a = 0, b = n - 1;
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (offsets[mid] <= lo) a = mid;
+        else b = mid - 1;
+    }
+    uint32_t v = 0;
+    for (int k = a; k < n && offsets[k] < lo + 32; ++k) {
+        const uint32_t* s = bits + (size_t)k * kBlockWords;
+        const int length = offsets[k + 1] - offsets[k];
+        const int rel = lo - offsets[k];  // position of the word's first bit inside the block
+        uint32_t part;
+        int used;  // bits of the word, from its MSB, that the block's bits reach
+        if (rel >= 0) {
+            const int i = rel >> 5, sh = rel & 31;
+            part = s[i] << sh;
+            if (sh && (i + 1) * 32 < length) part |= s[i + 1] >> (32 - sh);
+            used = length - rel;
+        } else {
+            part = s[0] >> (-rel);
+            used = length - rel;
+        }
+        if (used < 32) part &= ~0u << (32 - used);
+        v |= part;
+    }
+    const int remaining = offsets[n] - lo;
+    if (remaining < 32) v |= ~0u >> remaining;
+    return v;
+}
+
+template <typename T>
+__device__ T block_exclusive_scan(T value, T* scratch, T* total) {
+    const int tid = threadIdx.x;
+    scratch[tid] = value;
+    __syncthreads();
+    for (int d = 1; d < kSegmentThreads; d <<= 1) {
+        const T add = tid >= d ? scratch[tid - d] : 0;
+        __syncthreads();
+        scratch[tid] += add;
+        __syncthreads();
+    }
+    const T inclusive = scratch[tid];
+    *total = scratch[kSegmentThreads - 1];
+    __syncthreads();
+    return inclusive - value;
+}
+
+__global__ void __launch_bounds__(kSegmentThreads) mjpeg_segment_kernel(const uint32_t* __restrict__ bits, const int* __restrict__ bit_counts,
+                                                                        int segment_blocks, int64_t segment_capacity,
+                                                                        uint8_t* __restrict__ slots, int* __restrict__ segment_sizes) {
+    __shared__ int offsets[kMaxSegmentBlocks + 1];
+    __shared__ int scratch[kSegmentThreads];
+    const int64_t segment = blockIdx.x;
+    const int tid = threadIdx.x;
+    const uint32_t* seg_bits = bits + segment * segment_blocks * kBlockWords;
+    int carry = 0;
+    for (int base = 0; base < segment_blocks; base += kSegmentThreads) {
+        const int k = base + tid;
+        const int count = k < segment_blocks ? bit_counts[segment * segment_blocks + k] : 0;
+        int sum;
+        const int before = block_exclusive_scan(count, scratch, &sum);
+        if (k < segment_blocks) offsets[k] = carry + before;
+        carry += sum;
+    }
+    if (tid == 0) offsets[segment_blocks] = carry;
+    __syncthreads();
+    const int total_bits = carry;
+    const int bytes = (total_bits + 7) / 8, words = (bytes + 3) / 4;
+    uint8_t* out = slots + segment * segment_capacity;
+    int stuffed = 0;  // 0x00 bytes inserted before the current tile
+    for (int base = 0; base < words; base += kSegmentThreads) {
+        const int w = base + tid;
+        uint32_t v = 0;
+        int valid = 0, ff = 0;
+        if (w < words) {
+            v = segment_word(seg_bits, offsets, segment_blocks, w);
+            valid = min(4, bytes - 4 * w);
+            for (int j = 0; j < valid; ++j) ff += ((v >> (24 - 8 * j)) & 0xFF) == 0xFF;
+        }
+        int sum;
+        int position = 4 * w + stuffed + block_exclusive_scan(ff, scratch, &sum);
+        for (int j = 0; j < valid; ++j) {
+            const uint8_t byte = (uint8_t)(v >> (24 - 8 * j));
+            out[position++] = byte;
+            if (byte == 0xFF) out[position++] = 0;
+        }
+        stuffed += sum;
+    }
+    if (tid == 0) segment_sizes[segment] = bytes + stuffed;
+}
+
+// ---- 4. frame layout and packing -----------------------------------------------------------------------------------
+// One workgroup per frame: where each segment lands relative to its frame (a block scan of the segment sizes, each + 2
+// for the RSTn or EOI after it), and the frame's size into offsets[frame + 1].
+__global__ void __launch_bounds__(kSegmentThreads) mjpeg_frame_layout_kernel(const int* __restrict__ segment_sizes, int mcu_rows,
+                                                                              int header_bytes, int* __restrict__ segment_dst,
+                                                                              int64_t* __restrict__ offsets) {
+    __shared__ int scratch[kSegmentThreads];
+    const int64_t frame = blockIdx.x;
+    int carry = header_bytes;  // a frame is < 2^31 bytes: at most 1024 rows of < 850 000 bytes (side <= 8192)
+    for (int base = 0; base < mcu_rows; base += kSegmentThreads) {
+        const int r = base + threadIdx.x;
+        const int size = r < mcu_rows ? segment_sizes[frame * mcu_rows + r] + 2 : 0;
+        int sum;
+        const int before = block_exclusive_scan(size, scratch, &sum);
+        if (r < mcu_rows) segment_dst[frame * mcu_rows + r] = carry + before;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) offsets[frame + 1] = carry;
+}
+
+// One workgroup: the frame sizes in offsets[1 .. batch] scanned in place into the frames' positions, offsets[0] = 0.
+__global__ void __launch_bounds__(kSegmentThreads) mjpeg_frame_offsets_kernel(int batch, int64_t* __restrict__ offsets) {
+    __shared__ int64_t scratch[kSegmentThreads];
+    int64_t carry = 0;
+    for (int base = 0; base < batch; base += kSegmentThreads) {
+        const int f = base + threadIdx.x;
+        const int64_t size = f < batch ? offsets[f + 1] : 0;
+        int64_t sum;
+        const int64_t before = block_exclusive_scan(size, scratch, &sum);
+        if (f < batch) offsets[f + 1] = carry + before + size;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) offsets[0] = 0;
+}
+
+__global__ void __launch_bounds__(256) mjpeg_pack_kernel(const uint8_t* __restrict__ slots, int64_t segment_capacity,
+                                                         const int* __restrict__ segment_sizes, const int* __restrict__ segment_dst,
+                                                         const int64_t* __restrict__ offsets, int mcu_rows, Header header,
+                                                         uint8_t* __restrict__ out) {
+    const int64_t segment = blockIdx.x;
+    const int64_t frame = segment / mcu_rows;
+    const int row = (int)(segment - frame * mcu_rows);
+    const int size = segment_sizes[segment];
+    const uint8_t* src = slots + segment * segment_capacity;
+    uint8_t* dst = out + offsets[frame] + segment_dst[segment];
+    for (int i = threadIdx.x; i < size; i += blockDim.x) dst[i] = src[i];
+    if (threadIdx.x == 0) {
+        dst[size] = 0xFF;
+        dst[size + 1] = row == mcu_rows - 1 ? 0xD9 : 0xD0 + (row & 7);
+    }
+    if (row == 0) {
+        uint8_t* head = out + offsets[frame];
+        for (int i = threadIdx.x; i < header.length; i += blockDim.x) head[i] = header.bytes[i];
+    }
+}
+
+static int fail(int code, const std::string& message) { return gance::set_last_error(code, message); }
+
+static int check_sizes(int32_t batch, int32_t side) {
+    if (batch < 1) return fail(GANCE_ERR_INVALID_ARGUMENT, "batch must be >= 1");
+    if (side < 16 || side > kMaxSide || side % 16 != 0)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "side must be a multiple of 16 in [16, " + std::to_string(kMaxSide) + "], got " +
+                                                    std::to_string(side));
+    return GANCE_OK;
+}
+
+}  // namespace gance_mjpeg
+
+extern "C" {
+
+int gance_jpeg_encode_bounds(int32_t batch, int32_t side, uint64_t* workspace_bytes, uint64_t* out_capacity) {
+    using namespace gance_mjpeg;
+    if (workspace_bytes == nullptr || out_capacity == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_bounds");
+    if (const int status = check_sizes(batch, side)) return status;
+    const Layout l = layout_of(batch, side);
+    *workspace_bytes = (uint64_t)l.workspace_bytes;
+    *out_capacity = (uint64_t)l.out_capacity;
+    return GANCE_OK;
+}
+
+int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, int32_t quality, void* d_workspace,
+                         uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream_ptr) {
+    using namespace gance_mjpeg;
+    if (d_frames == nullptr || d_workspace == nullptr || d_out == nullptr || d_offsets == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_u8");
+    if (const int status = check_sizes(batch, side)) return status;
+    if (quality < 1 || quality > 100) return fail(GANCE_ERR_INVALID_ARGUMENT, "quality must be in [1, 100], got " + std::to_string(quality));
+    if ((uintptr_t)d_frames % 16 != 0 || (uintptr_t)d_workspace % 16 != 0)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "frames and workspace must be 16-byte aligned");
+    const Layout l = layout_of(batch, side);
+    if (workspace_bytes < (uint64_t)l.workspace_bytes)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                                    std::to_string(l.workspace_bytes) + " needed (gance_jpeg_encode_bounds)");
+    if (out_capacity < (uint64_t)l.out_capacity)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "output capacity of " + std::to_string(out_capacity) + " bytes, " +
+                                                    std::to_string(l.out_capacity) + " needed (gance_jpeg_encode_bounds)");
+    int device_count = 0;
+    if (hipGetDeviceCount(&device_count) != hipSuccess || device_count == 0)
+        return fail(GANCE_ERR_NO_DEVICE, "no HIP device visible; libgance_hip has no CPU path");
+    gance::DeviceGuard guard(gance::device_of_pointer(d_frames));  // launch where the frames live
+    if (guard.status() != hipSuccess) return fail(GANCE_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.status()));
+
+    char* ws = (char*)d_workspace;
+    int16_t* coef = (int16_t*)ws;
+    uint32_t* bits = (uint32_t*)(ws + l.coef_bytes);
+    int* bit_counts = (int*)(ws + l.coef_bytes + l.bits_bytes);
+    uint8_t* slots = (uint8_t*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes);
+    int* segment_sizes = (int*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes);
+    int* segment_dst = (int*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes + l.size_bytes);
+    const Header header = make_header(side, quality);
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    const unsigned grid = (unsigned)((l.blocks + 255) / 256);
+    mjpeg_transform_kernel<<<grid, 256, 0, stream>>>(d_frames, side, l.mcu_rows, l.mcu_cols, l.blocks, make_quant(quality), coef);
+    mjpeg_huffman_kernel<<<grid, 256, 0, stream>>>(coef, l.mcu_cols, l.blocks, bits, bit_counts);
+    mjpeg_segment_kernel<<<(unsigned)l.segments, kSegmentThreads, 0, stream>>>(bits, bit_counts, (int)l.segment_blocks, l.segment_capacity,
+                                                                               slots, segment_sizes);
+    mjpeg_frame_layout_kernel<<<(unsigned)batch, kSegmentThreads, 0, stream>>>(segment_sizes, (int)l.mcu_rows, header.length, segment_dst,
+                                                                               d_offsets);
+    mjpeg_frame_offsets_kernel<<<1, kSegmentThreads, 0, stream>>>(batch, d_offsets);
+    mjpeg_pack_kernel<<<(unsigned)l.segments, 256, 0, stream>>>(slots, l.segment_capacity, segment_sizes, segment_dst, d_offsets,
+                                                                (int)l.mcu_rows, header, d_out);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(GANCE_ERR_HIP, std::string("mjpeg launch: ") + hipGetErrorString(err));
+    return GANCE_OK;
+}
+
+}  // extern "C"

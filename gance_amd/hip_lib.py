@@ -204,6 +204,15 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
     ),
     "gance_debug_resample_filter": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_uint64]),
+    "gance_jpeg_encode_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_jpeg_encode_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_vec_rms_rolling_max": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p],
@@ -710,6 +719,33 @@ def overlay_boxes_device(  # pylint: disable=too-many-arguments
         lib.gance_overlay_boxes_u8(
             d_foreground, d_background, d_out, num_frames, side, boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
             boxes.shape[0], stream or None,
+        ),
+    )
+
+
+def jpeg_encode_bounds(batch: int, side: int) -> Tuple[int, int]:
+    """(workspace bytes, output capacity) of one `jpeg_encode_device` call of `batch` frames of side `side`.
+    :raises ValueError: side not a multiple of 16 in [16, 8192], or batch < 1."""
+    lib = load_library()
+    workspace, capacity = ctypes.c_uint64(), ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_jpeg_encode_bounds(batch, side, ctypes.byref(workspace), ctypes.byref(capacity)))
+    return int(workspace.value), int(capacity.value)
+
+
+def jpeg_encode_device(  # pylint: disable=too-many-arguments
+    d_frames: int, batch: int, side: int, quality: int, d_workspace: int, workspace_bytes: int, d_out: int, out_capacity: int,
+    d_offsets: int, stream: int = 0,
+) -> None:
+    """
+    Baseline JPEG (4:2:2, standard tables, one restart interval per MCU row) of uint8 frames [batch][side][side][3] in HBM:
+    frame b's file lands at d_out[offsets[b]:offsets[b + 1]], offsets int64 [batch + 1] on the device. Asynchronous on `stream`.
+    :raises ValueError: bad side, quality outside 1..100, workspace or capacity below `jpeg_encode_bounds`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_jpeg_encode_u8(
+            d_frames, batch, side, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
         ),
     )
 

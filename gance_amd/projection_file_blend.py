@@ -11,8 +11,9 @@ projection-file-blend end to end: WAV(s) + projection file + network(s) -> frame
   (perceptual hashes and the overlay write are HIP kernels; the landmark detector is external); the stream stays
   lazy with the overlay on, as the reference's iterator chain does (gance/projection_file_blend.py:223-275): the
   run-length filter only ever holds back the frames of a run that is still shorter than `track_length`;
-* video encoding (ffmpeg / x264) and the matplotlib debug video are out of scope here: frames are
-  returned / written as a `.npy` uint8 array [N][S][S][3], and asking for the debug video raises
+* the video is Motion-JPEG in an OpenDML AVI with the WAVs muxed in (`output_format="avi"`), encoded in HBM by the HIP
+  JPEG encoder and written by gance_amd/video/mjpeg_avi.py, instead of x264 through ffmpeg; `output_format="npy"` (the
+  default) writes the raw frames as a `.npy` uint8 array [N][S][S][3]. Asking for the debug video raises
   NotImplementedError.
 """
 
@@ -39,6 +40,7 @@ from gance_amd.projection import projection_file_reader
 from gance_amd.overlay import overlay_common, overlay_eye_tracking
 from gance_amd.vector_sources import music, vector_reduction
 from gance_amd.vector_sources.vector_sources_common import underlying_length
+from gance_amd.video import mjpeg_avi
 
 
 def _common_output_side(networks: MultiNetwork, indices: np.ndarray, output_side_length: Optional[int]) -> int:
@@ -462,7 +464,87 @@ class _StreamingOverlay:
         return self._release(final=True)
 
 
-def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements
+class EncodedFrames:
+    """A chunk of JPEG-encoded frames of side `side` on the host: frame i is the JFIF file data[offsets[i]:offsets[i + 1]]."""
+
+    def __init__(self, data: np.ndarray, offsets: np.ndarray, side: int) -> None:
+        self.data, self.offsets, self.side = data, offsets, side
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def frame(self, index: int) -> np.ndarray:
+        """The JFIF file of frame `index` of the chunk (a view)."""
+        return self.data[self.offsets[index] : self.offsets[index + 1]]
+
+
+class _EncodedHostRing:
+    """
+    HostRing (frame_sharding) for encoded chunks: `push` encodes nothing itself; it takes a chunk's JPEG bytes + offsets in
+    HBM, waits for the offsets (the byte count), starts the copy of only the compressed bytes into a pinned slot, and
+    returns the PREVIOUS chunk (first, EncodedFrames) once its copy has landed. Slots grow to the largest chunk seen.
+    A returned chunk stays valid until `push` has been called `slots - 1` more times.
+    """
+
+    def __init__(self, slots: int = 3) -> None:
+        self._data: List[Optional[torch.Tensor]] = [None] * slots
+        self._offsets: List[Optional[torch.Tensor]] = [None] * slots
+        self._next = 0
+        self._pending = None  # (first, count, bytes, slot, event, side)
+
+    def _finish(self):
+        if self._pending is None:
+            return None
+        first, count, size, slot, event, side = self._pending
+        self._pending = None
+        event.synchronize()
+        return first, EncodedFrames(self._data[slot][:size].numpy(), self._offsets[slot][: count + 1].numpy(), side)
+
+    def push(  # pylint: disable=too-many-arguments
+        self, first: int, data: torch.Tensor, offsets: torch.Tensor, side: int, reader_stream
+    ) -> Tuple[int, Optional[tuple]]:
+        """Start draining one encoded chunk; returns (bytes it moves to the host, previous chunk or None)."""
+        done = self._finish()
+        slot = self._next
+        self._next = (self._next + 1) % len(self._data)
+        count = int(offsets.shape[0]) - 1
+        if self._offsets[slot] is None or self._offsets[slot].shape[0] < count + 1:
+            self._offsets[slot] = torch.empty((count + 1,), dtype=torch.int64, pin_memory=True)
+        with torch.cuda.stream(reader_stream):
+            self._offsets[slot][: count + 1].copy_(offsets, non_blocking=True)
+            sized = torch.cuda.Event()
+            sized.record(reader_stream)
+            sized.synchronize()  # the chunk's byte count (the encode itself has run by now)
+            size = int(self._offsets[slot][count])
+            if self._data[slot] is None or self._data[slot].shape[0] < size:
+                self._data[slot] = torch.empty((size + size // 4,), dtype=torch.uint8, pin_memory=True)
+            self._data[slot][:size].copy_(data[:size], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(reader_stream)
+        self._pending = (first, count, size, slot, event, side)
+        return size + 8 * (count + 1), done
+
+    def flush(self):
+        """The last chunk pushed (first, EncodedFrames), or None."""
+        return self._finish()
+
+
+def encode_into_ring(  # pylint: disable=too-many-arguments
+    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream
+) -> Iterator[Tuple[int, Optional[tuple]]]:
+    """
+    Encode device frames [n, S, S, 3] on the reader stream, at most `piece_frames` per encoder call, and push each piece into
+    the ring. Yields (bytes moved to the host, the chunk the push finished or None) after EVERY push, so the consumer
+    takes a finished chunk before the next push can reuse its slot.
+    """
+    side = int(frames.shape[1])
+    for start in range(0, int(frames.shape[0]), piece_frames):
+        with torch.cuda.stream(reader_stream):
+            data, offsets = torch.ops.gance.jpeg_encode(frames[start : start + piece_frames], quality)
+        yield ring.push(first + start, data, offsets, side, reader_stream)
+
+
+def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements,too-many-branches
     wav: List[str],
     network_paths: List[Path],
     frames_to_visualize: Optional[int],
@@ -479,6 +561,7 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     timings: Optional[Dict[str, object]] = None,
     drain: str = "rank0",
     on_total: Optional[Callable[[int], None]] = None,
+    jpeg_quality: Optional[int] = None,
 ) -> Iterator[Tuple[int, int, np.ndarray]]:
     """
     The frame stream of the reference's pipeline (gance/projection_file_blend.py:343 hands an iterator of frames to
@@ -500,11 +583,23 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     (its run-length filter needs the ordered stream in one place).
     :param on_total: called once on every rank with the total frame count as soon as it is known, rank 0 first and the
     other ranks after rank 0's call has returned (so rank 0 can create an output file the others then open).
+    :param jpeg_quality: None (default): chunks of raw frames as above. 1..100: rank 0 encodes every released chunk (after
+    the overlay stage, if any) on the reader stream with torch.ops.gance.jpeg_encode, at most `frames_per_call` frames per
+    call, and drains only the offsets and the compressed bytes to a pinned host ring: the generator yields
+    (first_frame_index, total_frames, EncodedFrames) and raw frames never reach the host; timings["bytes_to_host"] counts
+    the compressed bytes. Needs drain="rank0" and an output side that is a multiple of 16.
     """
     if drain not in frame_sharding.DRAIN_MODES:
         raise ValueError(f"drain must be one of {frame_sharding.DRAIN_MODES}, got {drain!r}")
     if drain == "per-rank" and overlay is not None:
         raise ValueError("the eye-tracking overlay needs the ordered stream on rank 0: drain=\"rank0\"")
+    if jpeg_quality is not None:
+        if drain != "rank0":
+            raise ValueError("the JPEG encode runs on rank 0 after the gather: drain=\"rank0\"")
+        if not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
+        if output_side_length is not None and int(output_side_length) % 16 != 0:
+            raise ValueError(f"the JPEG encoder needs an output side that is a multiple of 16, got {output_side_length}")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world_size = dist.get_world_size() if dist.is_initialized() else 1
     device = torch.device("cuda", torch.cuda.current_device())
@@ -570,30 +665,51 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
                 else [False] * num_frames
             )
             stage = _StreamingOverlay(inputs.target_images, inputs.frame_multiplier, overlay, skip_mask, num_frames, side, device)
+        if jpeg_quality is not None and side % 16 != 0:
+            raise ValueError(f"the JPEG encoder needs an output side that is a multiple of 16, got {side}")
         ring = None
         bytes_to_host = 0
+
+        def drain_chunk(ready_first: int, ready_frames: torch.Tensor, reader_stream):
+            """
+            Drains one released chunk into the ring and yields every chunk whose copy has landed, each RIGHT AFTER the
+            push that returned it: a ring slot is reused `slots - 1` pushes later, and an encoded chunk of
+            world_size * frames_per_call frames takes world_size pushes.
+            """
+            nonlocal bytes_to_host
+            if jpeg_quality is None:
+                bytes_to_host += ready_frames.numel()
+                done = ring.push(ready_first, ready_frames, reader_stream)
+                if done is not None:
+                    yield done
+                return
+            for moved, done in encode_into_ring(ring, ready_first, ready_frames, int(jpeg_quality), frames_per_call, reader_stream):
+                bytes_to_host += moved
+                if done is not None:
+                    yield done
+
         for first, frames, reader_stream in frame_sharding.ordered_device_chunks(
             synthesize_piece, num_frames, frames_per_call, (side, side, 3), device, drain=drain
         ):
             if ring is None:
-                ring = frame_sharding.HostRing((1 if drain == "per-rank" else world_size) * frames_per_call, (side, side, 3), device, slots=3)
+                ring = (
+                    frame_sharding.HostRing((1 if drain == "per-rank" else world_size) * frames_per_call, (side, side, 3), device, slots=3)
+                    if jpeg_quality is None
+                    else _EncodedHostRing(slots=3)
+                )
             if stage is None:
                 ready = [(first, frames)]
             else:
                 with torch.cuda.stream(reader_stream):  # (the chunk view may only be read on the reader stream)
                     ready = stage.push(first, frames)
             for ready_first, ready_frames in ready:
-                done = ring.push(ready_first, ready_frames, reader_stream)
-                bytes_to_host += ready_frames.numel()
-                if done is not None:
+                for done in drain_chunk(ready_first, ready_frames, reader_stream):
                     yield done[0], num_frames, done[1]
         if stage is not None:
             with torch.cuda.stream(reader_stream):
                 ready = stage.flush()
             for ready_first, ready_frames in ready:
-                done = ring.push(ready_first, ready_frames, reader_stream)
-                bytes_to_host += ready_frames.numel()
-                if done is not None:
+                for done in drain_chunk(ready_first, ready_frames, reader_stream):
                     yield done[0], num_frames, done[1]
             LOGGER.info(f"Eye tracking overlay written on {stage.overlays_written} of {num_frames} frames")
         if ring is not None:
@@ -674,10 +790,13 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     bbox_distance: Optional[float],
     track_length: Optional[int],
     drain: Optional[str] = None,
+    *,
+    output_format: str = "npy",
+    jpeg_quality: int = 90,
 ) -> None:
     """
     Same parameter list as the reference API (gance/projection_file_blend.py:56-76). Frames are
-    written to `output_path` as a `.npy` uint8 array (no video encoder here).
+    written to `output_path` as a `.npy` uint8 array (`output_format="npy"`, the default), or as a video.
     :raises ValueError: the reference's own checks (music mask without overlay, invalid projection file,
     non-integer fps ratio).
     :raises NotImplementedError: debug video requested (out of scope), or the overlay requested
@@ -685,7 +804,23 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     :param drain: (not a parameter of the reference) how frames reach the output file under `torch.distributed`:
     "rank0" = gathered over RCCL and written by rank 0; "per-rank" = every rank writes the pieces it synthesised into
     the same memory-mapped file over its own PCIe link. Default: GANCE_STREAM_DRAIN, else "rank0"; the overlay forces "rank0".
+    :param output_format: (not a parameter of the reference) "npy": the raw frames, `.npy` appended to `output_path` if it
+    is missing. "avi": what write_source_to_disk_forward + add_wavs_to_video write (video_common.py:67-79, 301-376) as
+    Motion-JPEG: frames encoded in HBM on rank 0 (torch.ops.gance.jpeg_encode at `jpeg_quality`), an OpenDML AVI at
+    `output_path` exactly, the WAVs concatenated as its audio stream (gance_amd/video/mjpeg_avi.py); forces drain="rank0".
+    :raises ValueError: (also) an unknown output_format, or "avi" with an output side that is not a multiple of 16 (checked
+    before any synthesis; with output_side_length None the networks' own side, checked once they are loaded).
     """
+    if output_format not in ("npy", "avi"):
+        raise ValueError(f"output_format must be \"npy\" or \"avi\", got {output_format!r}")
+    encode = output_format == "avi"
+    if encode:
+        # (output_side_length None: the networks' own side, checked by the stream once the networks are loaded)
+        if output_side_length is not None and int(output_side_length) % 16 != 0:
+            raise ValueError(f"the Motion-JPEG writer needs an output side that is a multiple of 16, got {output_side_length}")
+        if not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
+        mjpeg_avi.frame_rate_fraction(output_fps)  # (a rate AVI cannot hold is refused before any work)
     drain = drain or os.environ.get("GANCE_STREAM_DRAIN", "rank0")
     overlay_enabled = all(param is not None for param in (phash_distance, bbox_distance, track_length))
     overlay_music_mask_enabled = all(
@@ -702,7 +837,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         if overlay_enabled
         else None
     )
-    if overlay is not None:
+    if overlay is not None or encode:
         drain = "rank0"
     # frame chunks go straight from the pinned ring into the (memory-mapped) output file: nothing holds the video
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -714,18 +849,38 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         state["total"] = total
         if output_path is None or (rank != 0 and drain != "per-rank"):
             return
-        if rank == 0:
+        if encode:
+            if output_side_length is not None:
+                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, output_side_length, output_fps, wavs=wav)
+            else:  # the side is the networks': the writer opens with the first chunk
+                mjpeg_avi.read_concatenated_wavs(wav)  # (mismatched WAVs are refused before synthesis starts)
+                state["avi_side_pending"] = True
+        elif rank == 0:
             state["writer"] = np.lib.format.open_memmap(
                 _npy_path(output_path), mode="w+", dtype=np.uint8, shape=(total, output_side_length, output_side_length, 3)
             )
         elif total > 0:
             state["writer"] = np.load(_npy_path(output_path), mmap_mode="r+")
 
-    for first, _total, frames in projection_file_blend_frame_chunks(
-        wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled,
-        fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=open_output,
-    ):
-        if state["writer"] is not None:
-            state["writer"][first : first + len(frames)] = frames
-    if state["writer"] is not None:
+    try:
+        for first, _total, frames in projection_file_blend_frame_chunks(
+            wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled,
+            fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=open_output,
+            jpeg_quality=int(jpeg_quality) if encode else None,
+        ):
+            if encode and state.get("avi_side_pending") and state["writer"] is None:
+                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, frames.side, output_fps, wavs=wav)
+            if state["writer"] is None:
+                continue
+            if encode:  # (chunks arrive in frame order on rank 0)
+                for index in range(len(frames)):
+                    state["writer"].add_frame(frames.frame(index))
+            else:
+                state["writer"][first : first + len(frames)] = frames
+        if encode and state.get("avi_side_pending") and state["writer"] is None:  # no frames: an empty video
+            state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, 0, output_fps, wavs=wav)
+    finally:
+        if encode and state["writer"] is not None:
+            state["writer"].close()
+    if state["writer"] is not None and not encode:
         state["writer"].flush()

@@ -7,6 +7,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.resize_bicubic(frames, side)           [B, S, S, 3] u8  -> [B, side, side, 3] u8
     torch.ops.gance.synthesize_w_out / synthesize_z_out / resize_bicubic_out   the same, into a caller-owned `out`
     torch.ops.gance.blend(audio, latent_row0, blend)       [samples] f32, [F, L] f32 -> ([N, depth, L] f32, [N] i32)
+    torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
 without synchronising, so the ops compose with torch code and with `torch.distributed` collectives in stream
@@ -219,3 +220,33 @@ def _(audio: torch.Tensor, latent_row0: torch.Tensor, blend_handle: int) -> Tupl
         audio.new_empty((config.num_frames, config.latent_depth, config.vector_length)),
         audio.new_empty((config.num_frames,), dtype=torch.int32),
     )
+
+
+@torch.library.custom_op("gance::jpeg_encode", mutates_args=(), device_types="cuda")
+def jpeg_encode(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    Baseline JPEG of each frame (the video encode of write_source_to_disk_forward, video_common.py:301-376, as Motion-JPEG):
+    `data` [capacity] u8 holds the files back to back, frame b at data[offsets[b]:offsets[b + 1]]; `capacity` is the
+    worst case of the shape (hip_lib.jpeg_encode_bounds), only offsets[-1] bytes are written.
+    """
+    _require_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[1] != frames.shape[2] or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [B, S, S, 3], got {tuple(frames.shape)}")
+    batch, side = int(frames.shape[0]), int(frames.shape[1])
+    workspace_bytes, capacity = hip_lib.jpeg_encode_bounds(batch, side)
+    frames = frames.contiguous()
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
+    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
+    hip_lib.jpeg_encode_device(
+        frames.data_ptr(), batch, side, int(quality), workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity,
+        offsets.data_ptr(), _stream(frames),
+    )
+    return data, offsets
+
+
+@jpeg_encode.register_fake
+def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    batch, side = int(frames.shape[0]), int(frames.shape[1])
+    _, capacity = hip_lib.jpeg_encode_bounds(batch, side)
+    return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)

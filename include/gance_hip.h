@@ -346,6 +346,25 @@ int gance_resample_audio_f64(const double* d_in, uint64_t num_in, double sr_orig
 /* host only: the filter table the resampler interpolates (count must be 32769) */
 int gance_debug_resample_filter(double* h_out, uint64_t count);
 
+/* ---- Motion-JPEG frame encoder -----------------------------------------------------------------
+ * Replaces the video encode of write_source_to_disk_forward (gance/image_sources/video_common.py:301-376:
+ * ffmpeg / x264 crf 18, yuv422p, high_quality=True) whose file add_wavs_to_video (:67-79) then muxes: frames are encoded in HBM as baseline JFIF
+ * files (4:2:2, the Annex K tables scaled by `quality` as libjpeg's jpeg_set_quality does, standard
+ * Huffman tables, one restart interval per MCU row: DRI = side / 16), arithmetic as libjpeg's islow
+ * path, so libjpeg decodes them to exactly the pixels of its own encode at that quality.
+ * gance_jpeg_encode_bounds: host only; the workspace and output capacity one call of (batch, side)
+ * needs. Both are worst-case sizes (a block is at most 1660 bits before 0xFF stuffing): the encoder
+ * cannot truncate. batch >= 1, side a multiple of 16 in [16, 8192].
+ * gance_jpeg_encode_u8: d_frames [batch][side][side][3] uint8 (device, 16-byte aligned); quality 1..100;
+ * d_workspace (device, 16-byte aligned) of workspace_bytes; d_out (device) receives the batch's files
+ * back to back, frame b at [d_offsets[b], d_offsets[b + 1]); d_offsets [batch + 1] int64 (device).
+ * Asynchronous on `stream`; the bytes are the same whatever the batch a frame is encoded in.
+ * Returns GANCE_ERR_INVALID_ARGUMENT before touching a device for a bad side, quality, or a workspace or
+ * capacity below the bounds. */
+int gance_jpeg_encode_bounds(int32_t batch, int32_t side, uint64_t* workspace_bytes, uint64_t* out_capacity);
+int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, int32_t quality, void* d_workspace,
+                         uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
