@@ -289,6 +289,7 @@ struct gance_engine {
     std::vector<size_t> upfir16x_w;  // ... and for that geometry's pair form (F(2,2) along x: 15 MFMAs per pair of columns instead of 18)
     std::vector<size_t> upfirs_w;    // split-operand form of the fused up kernel (upfir_split.hip: three bf16 parts per value, six terms, fp32 accumulation)
     int upfir_split = 1;  // GANCE_TUNE_UPFIR_SPLIT when the engine is created: 0 never, 1 (default) where a launch fills the chip without row segments, 2 wherever supported
+    int upfir_split_narrow = 1;  // GANCE_TUNE_UPFIR_SPLIT_NARROW: the split form's narrow geometries (inputs 32 and 16 wide) in mode 1 and 2 by the fill rule; 0 never
     int upfir_split_max_res = 1024;  // GANCE_TUNE_UPFIR_SPLIT_MAXRES: the largest OUTPUT side that takes the split form in mode 1 (measured: DESIGN.md section 3; 512 until the staging went to 16-byte loads)
     int num_cus = 256;
     std::vector<float> conv_ns;
@@ -671,7 +672,9 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
             // (9/16: measured without row segments, 16 blocks per frame at every layer -- whole calls of 8 / 9 / 10 / 11 frames ran at 1053 / 842 / 909 / 940
             // frames/s in the fp32 forms, at 953 / ~1000 / 1045 / 1106 in this one; with row segments 1 ... 8 frames per call take it too wherever 16-row
             // segments reach that many blocks: 645 / 895 / 899 / 1080 / 934 / 1055 / 1136 / 1202 frames/s against 614 / 817 / 861 / 960 / - / 980 / - / 1047)
-            if (e->upfir_split == 2 || (u.total_blocks >= e->num_cus * 9 / 16 && 2 * H <= e->upfir_split_max_res)) {
+            // (mode 2 forces the wide geometry only; the narrow ones -- 64 / W channel tiles per block -- take the fill rule in both modes)
+            const bool narrow = !gance::upfirs_supported(c.cin, c.cout, H, H);
+            if ((e->upfir_split == 2 && !narrow) || (u.total_blocks >= e->num_cus * 9 / 16 && 2 * H <= e->upfir_split_max_res)) {
                 if (plan != nullptr) *plan = u;
                 return UpFused::split;
             }
@@ -1112,6 +1115,8 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         e->upfir_split = split != nullptr ? std::max(0, std::min(2, std::atoi(split))) : 1;
         const char* const split_res = std::getenv("GANCE_TUNE_UPFIR_SPLIT_MAXRES");
         if (split_res != nullptr) e->upfir_split_max_res = std::atoi(split_res);
+        const char* const split_narrow = std::getenv("GANCE_TUNE_UPFIR_SPLIT_NARROW");
+        e->upfir_split_narrow = split_narrow != nullptr && std::atoi(split_narrow) == 0 ? 0 : 1;
     }
     e->cfg = *config;
     e->num_cus = num_cus > 0 ? num_cus : 256;
@@ -1266,7 +1271,9 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
             else gance::upgemm_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upgemm_w[i]]);
         }
         e->upfirs_w.push_back(SIZE_MAX);
-        if (c.up && e->upfir_split != 0 && upfir16_mode() != 0 && gance::upfirs_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)) {
+        if (c.up && e->upfir_split != 0 && upfir16_mode() != 0 &&
+            (gance::upfirs_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2) ||
+             (e->upfir_split_narrow != 0 && gance::upfirs_narrow_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)))) {
             std::vector<float> scaled(wn);
             for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
             e->upfirs_w[i] = reserve(gance::upfirs_weight_floats(c.cin, c.cout));

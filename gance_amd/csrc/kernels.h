@@ -221,6 +221,8 @@ void upfir16x_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int c
 // product terms, fp32 accumulation -- fp32 accuracy): 16 channels per block, one block per CU, whole image height per block (no row
 // segments), inputs whose width the 64-column strips tile. w points at upfirs_arrange_weights' image (bf16 parts).
 bool upfirs_supported(int cin, int cout, int H, int W);
+// ... and its narrow forms, inputs 32 and 16 wide: a block holds the whole width and 64 / W channel tiles of 16 (same weight image)
+bool upfirs_narrow_supported(int cin, int cout, int H, int W);
 size_t upfirs_weight_floats(int cin, int cout);
 void upfirs_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int cin, int cout, const int* up_tap_weight, float* w_out);
 void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* args);

@@ -38,6 +38,9 @@
 //     18 more MFMAs in that step's last row and one more epilogue pass, no step of its own.
 // A block sweeps the image's whole height, or -- for calls too small to fill the chip with whole images -- a row SEGMENT of it behind one
 // "priming" step (the step above the segment, computed for its last three T rows only: upfirs_plan picks the number of segments).
+// Inputs 32 and 16 wide (the 32^2 and 64^2 layers) run NARROW geometries of the same body (Geo<NT>, NT = 2 / 4): the strip is the whole width,
+// a block holds NT channel tiles and each wave one tile column of its own tile, so a staged row feeds NT tiles; the weight fragments come
+// per wave from global, and of the halo only the right side's dx = -1 taps of classes EE and OE are not zero.
 //
 // Weight image (upfirs_arrange_weights): [channel tile of 16][chunk of 32][tap][part][k-group][row m][8 channels] bf16: a lane's A
 // fragment (row m = lane % 16, k-group = lane / 16) is 16 contiguous bytes, a wave's load 1 KB; MFMA row m = 4 q + r holds channel
@@ -66,6 +69,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -93,26 +97,41 @@ constexpr int kHaloTasks = kRows * kHaloCols * 4;  // (row, column, k-group): 14
 #endif
 constexpr int kDepth = GANCE_UPFIRS_DEPTH;  // patch rows in flight between their global loads and their LDS writes (3 or 6: 8 registers each)
 constexpr int kCarryRows = 3;
-constexpr int kPassCh = 4;          // channels per epilogue pass
+constexpr int kPassCh = 4;          // channels of a channel tile per epilogue pass
 constexpr int kPassRows = 8;        // T rows per pass: four position rows
-constexpr int kTW = 2 * kSW + 4;    // T window row: T columns 2 X0 - 1 .. 2 X0 + 129 (+ pad)
-constexpr int kCG = kSW / 2;        // column groups of 4 output columns
-constexpr int kRG = 64 / kCG;       // row groups of a wave's 64 filter threads
-constexpr int kFR = kPassRows / kRG;  // output rows per filter thread
-constexpr int kWin = kFR + 3;
-constexpr int kCarryFloats = kBM * kCarryRows * kTW;
-constexpr int kStageFloats = kPassCh * kPassRows * kTW;
-constexpr int kNzPieces = 2 * kPassRows * 2 * kSW / 256;  // noise of a step's 16 output rows in 1 KiB DMA pieces
 constexpr float kSqrt2f = 1.4142135623730951f;
 static_assert((2 * kRows) % kDepth == 0 && kDepth + 2 < kRows && kRows % kRing == 0, "ring slots and staging registers rotate with the unrolled rows of a chunk pair");
 
-// LDS (bytes): ring | halo side buffers (two chunks) | T window of a pass | the step's noise | carry | style [Cin] | demod | bias | next style
+// Block geometry: NT channel tiles of 16 x a strip of 64 / NT position columns. NT = 1: the wide layers (inputs 64 and more wide, a
+// wave owns tile column `wave`). NT = 2, 4: the narrow layers (inputs 32 and 16 wide): the strip is the whole width, wave = (channel
+// tile ct, tile column tc) with the same per-wave work, and every staged patch row feeds NT channel tiles.
+template <int NT>
+struct Geo {
+    static constexpr int kSW = 64 / NT;            // position columns per strip
+    static constexpr int kBMB = kBM * NT;          // output channels per block
+    static constexpr int kTC = kSW / 16;           // tile columns = waves per channel tile
+    static constexpr int kPW = 4 / NT;             // positions per main staging lane (two channels each)
+    static constexpr int kTW = 2 * kSW + 4;        // T window row: T columns 2 X0 - 1 .. 2 X0 + 2 kSW + 1 (+ pad)
+    static constexpr int kCG = kSW / 2;            // column groups of 4 output columns
+    static constexpr int kRG = 64 / NT / kCG;      // row groups of a channel's filter threads (NT channels per wave and pass)
+    static constexpr int kFR = kPassRows / kRG;    // output rows per filter thread
+    static constexpr int kWin = kFR + 3;
+    static constexpr int kCarryFloats = kBMB * kCarryRows * kTW;
+    static constexpr int kStageFloats = kPassCh * NT * kPassRows * kTW;
+    static constexpr int kNzPieces = 2 * kPassRows * 2 * kSW / 256;  // noise of a step's 16 output rows in 1 KiB DMA pieces
+    // 16-byte units of a chunk's weight fragments in LDS: [tap][part][lane] (NT = 1; the narrow forms load each wave's own from global)
+    static constexpr int kWUnits = NT == 1 ? 27 * 64 : 0;
+};
+
+// LDS (bytes): ring | halo side buffers (two chunks) | weight fragments | T window of a pass | the step's noise | carry | style [Cin] |
+// demod | bias | next style
 constexpr size_t kRingBytes = (size_t)kRing * kSlotUnits * 16;
 constexpr size_t kHaloBytes = (size_t)2 * kHaloUnits * 16;
-constexpr int kWUnits = 27 * 64;  // 16-byte units of a chunk's weight fragments: [tap][part][lane]
-constexpr size_t kWBytes = (size_t)kWUnits * 16;
+template <int NT>
 constexpr size_t lds_bytes(int cin) {
-    return kRingBytes + kHaloBytes + kWBytes + sizeof(float) * ((size_t)kStageFloats + kNzPieces * 256 + kCarryFloats + cin + 3 * kBM);
+    using G = Geo<NT>;
+    return kRingBytes + kHaloBytes + (size_t)G::kWUnits * 16 +
+           sizeof(float) * ((size_t)G::kStageFloats + G::kNzPieces * 256 + G::kCarryFloats + cin + 3 * G::kBMB);
 }
 
 // transposed-conv tap tables, in the order the weights are stored (engine.hip kUpTapWeight):
@@ -172,24 +191,28 @@ __device__ __forceinline__ void split_unit(const unsigned (&raw)[8], u32x4 (&par
 
 }  // namespace
 
-template <bool kPre, bool kNoise>
+template <int NT, bool kPre, bool kNoise>
 __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
+    using G = Geo<NT>;
+    constexpr int kSW = G::kSW, kBMB = G::kBMB, kTC = G::kTC, kPW = G::kPW, kTW = G::kTW, kCG = G::kCG, kRG = G::kRG, kFR = G::kFR,
+                  kWin = G::kWin, kCarryFloats = G::kCarryFloats, kStageFloats = G::kStageFloats, kNzPieces = G::kNzPieces;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* const ring = reinterpret_cast<u32x4*>(smem_raw);
     u32x4* const halo = ring + kRing * kSlotUnits;
     u32x4* const w_lds = halo + 2 * kHaloUnits;                            // [tap][part][lane]: the weight fragments of the chunk after the one being multiplied
-    float* const stage = reinterpret_cast<float*>(w_lds + kWUnits);        // [4 ch][8 rows][kTW]
+    float* const stage = reinterpret_cast<float*>(w_lds + G::kWUnits);     // [NT tiles][4 ch][8 rows][kTW]
     float* const nz_lds = stage + kStageFloats;                            // [16 output rows][2 kSW]
-    float* const carry = nz_lds + kNzPieces * 256;                         // [16 ch][3 rows][kTW]
+    float* const carry = nz_lds + kNzPieces * 256;                         // [16 NT ch][3 rows][kTW]
     float* const s_lds = carry + kCarryFloats;                             // style [Cin] (absent when the input is pre-scaled)
     float* const d_lds = s_lds + (kPre ? 0 : p.Cin);
-    float* const b_lds = d_lds + kBM;
-    float* const sn_lds = b_lds + kBM;
+    float* const b_lds = d_lds + kBMB;
+    float* const sn_lds = b_lds + kBMB;
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int n16 = lane & 15, kg = lane >> 4;
+    const int ct = NT == 1 ? 0 : wave / kTC, tc = NT == 1 ? wave : wave % kTC;  // this wave's channel tile and tile column
 
     // ---- block -> (sample, strip, channel tile); blocks of one XCD take contiguous ids so that the channel tiles of one strip (same
     // input rows) and neighbouring strips share its L2 ----
@@ -205,7 +228,7 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
     id /= p.strips;
     const int seg = id % p.segs;  // row segment of the image (calls too small to fill the chip with whole images: upfirs_plan)
     const int b = id / p.segs;
-    const int m0 = m_tile * kBM;
+    const int m0 = m_tile * kBMB;
     const int X0 = strip * kSW;
     const int H = p.H, W = p.W;
     const int Hp = H + 2, Wp = W + 8;
@@ -220,16 +243,20 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
     const __amdgpu_buffer_rsrc_t x_rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * p.x_b_stride), 0, p.Cin * Hp * Wp * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const unsigned char*>(p.w) + (size_t)m_tile * chunks * 27 * 1024), 0, chunks * 27 * 1024, 0x00020000);
+        (void*)(reinterpret_cast<const unsigned char*>(p.w) + (size_t)(m_tile * NT + ct) * chunks * 27 * 1024), 0, chunks * 27 * 1024, 0x00020000);
 
     // ---- the stream of patch rows: (step, chunk, row j) in the order they are consumed; the producer runs 2 + kDepth rows ahead,
     // so the row it loads is row (j + 2 + kDepth) % 9 of the consumer's chunk or of the chunk after it: known where the load is written ----
     // per-lane LDS bases: everything that changes with the row, the chunk parity or the part is a compile-time offset from one of them
     // (the instruction's immediate): per-row address registers would not fit beside 144 accumulators and 108 weight registers
-    const int st_pair = lane >> 4, st_g = lane & 15;                              // staging task: channel pair 4 wave + st_pair, columns X0 + 4 st_g .. + 3
+    const int st_pair = lane >> 4, st_g = lane & 15;                              // staging task: channel pair 4 wave + st_pair, columns X0 + kPW st_g .. + kPW - 1
     u32x4* const ring_w = ring + wave * kPlaneStride + ring_column(4 * st_g + st_pair);  // ... after the transpose: the units of position 4 st_g + st_pair, k-group = wave
-    // fragment reads of position 16 wave + n16 (dx = 0) and of the position to its left (dx = -1; left of the strip: the edge column)
-    const int m_pos = 16 * wave + n16;
+    // (narrow strips, two or one positions per lane: NT = 2 ends with half a unit -- channel pairs 2 (st_pair / 2) + 0, 1 of position
+    // 2 st_g + st_pair % 2 -- after one permlane16 swap; NT = 4 writes its one pair of position st_g)
+    unsigned* const ring_wn = reinterpret_cast<unsigned*>(ring + wave * kPlaneStride + ring_column(NT == 2 ? 2 * st_g + (st_pair & 1) : st_g)) +
+                              (NT == 2 ? 2 * (st_pair >> 1) : st_pair);
+    // fragment reads of position 16 tc + n16 (dx = 0) and of the position to its left (dx = -1; left of the strip: the edge column)
+    const int m_pos = 16 * tc + n16;
     const u32x4* const ring_r0 = ring + kg * kPlaneStride + ring_column(m_pos);
     const u32x4* const ring_r1 = ring + kg * kPlaneStride + (m_pos > 0 ? ring_column(m_pos - 1) : kEdgeColumn);
     // column X0 - 1 of a ring row (the dx = -1 fragment of the strip's first lane) is not a main staging task (64 lanes = 64 columns):
@@ -242,24 +269,32 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
     const u32x4* const halo_r = halo + ((n16 & 7) * kHaloCols + 2 * (n16 >> 3)) * kPlanes + kg;  // halo tile slot n16 = (side, position row)
     const u32x4* const halo_f = halo + ((kRows - 1) * kHaloCols + 2 * (n16 >> 3)) * kPlanes + kg;  // ... of position row y' = H: the chunk's last row
     // main staging task of this lane: column X0 + lane, k-group = wave: eight dword loads (buffer row `brow` of the bordered tensor)
-    const int st_voff = (2 * st_pair * Hp * Wp + X0 + 4 + 4 * st_g) * 4;
+    const int st_voff = (2 * st_pair * Hp * Wp + X0 + 4 + kPW * st_g) * 4;
     unsigned st[kDepth][8];
     auto stage_load = [&](unsigned(&dst)[8], int chunk, int brow, bool in_loop = false) {
         if ((GANCE_UPFIRS_ABLATE & 4) && in_loop) return;
         const int soff = ((chunk * kKC + wave * 8) * Hp + brow) * Wp * 4;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_voff, soff + e * HpWp4, 0);  // channel 2 pair + e, four columns
+            if constexpr (kPW == 4) {
+                const u32x4 q4 = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_voff, soff + e * HpWp4, 0);  // channel 2 pair + e, four columns
 #pragma unroll
-            for (int c = 0; c < 4; ++c) dst[2 * c + e] = q4[c];  // (dst[2 c], dst[2 c + 1]: the pair at column c)
+                for (int c = 0; c < 4; ++c) dst[2 * c + e] = q4[c];  // (dst[2 c], dst[2 c + 1]: the pair at column c)
+            } else if constexpr (kPW == 2) {
+                const u32x2 q2 = __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, st_voff, soff + e * HpWp4, 0);
+                dst[e] = q2[0];
+                dst[2 + e] = q2[1];
+            } else {
+                dst[e] = __builtin_amdgcn_raw_buffer_load_b32(x_rsrc, st_voff, soff + e * HpWp4, 0);
+            }
         }
     };
-    // the main tasks hold two channels at four positions (the halo tasks eight channels of one position: scale8)
+    // the main tasks hold two channels at kPW positions (the halo tasks eight channels of one position: scale8)
     auto scale_pair = [&](unsigned(&raw)[8], int chunk) {
         if constexpr (!kPre) {
             const f32x2 s2 = *reinterpret_cast<const f32x2*>(s_lds + chunk * kKC + 8 * wave + 2 * st_pair);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
+            for (int c = 0; c < kPW; ++c) {
                 raw[2 * c] = __builtin_bit_cast(unsigned, __builtin_bit_cast(float, raw[2 * c]) * s2[0]);
                 raw[2 * c + 1] = __builtin_bit_cast(unsigned, __builtin_bit_cast(float, raw[2 * c + 1]) * s2[1]);
             }
@@ -288,20 +323,37 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
     };
     auto stage_store = [&](unsigned(&raw)[8], int slot, int chunk) {
         scale_pair(raw, chunk);
-        u32x4 part[3];
-        split_unit(raw, part);
+        if constexpr (NT == 1) {
+            u32x4 part[3];
+            split_unit(raw, part);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) transpose_rows(part[q]);
+            for (int q = 0; q < 3; ++q) transpose_rows(part[q]);
 #pragma unroll
-        for (int q = 0; q < 3; ++q)
-            if (!(GANCE_UPFIRS_ABLATE & 16)) ring_w[slot * kSlotUnits + q * 4 * kPlaneStride] = part[q];
+            for (int q = 0; q < 3; ++q)
+                if (!(GANCE_UPFIRS_ABLATE & 16)) ring_w[slot * kSlotUnits + q * 4 * kPlaneStride] = part[q];
+        } else {
+            unsigned w[3][kPW];  // [part][position]: the lane's channel pair
+#pragma unroll
+            for (int c = 0; c < kPW; ++c) split_pair(__builtin_bit_cast(float, raw[2 * c]), __builtin_bit_cast(float, raw[2 * c + 1]), w[0][c], w[1][c], w[2][c]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                unsigned* const dst = ring_wn + 4 * (slot * kSlotUnits + q * 4 * kPlaneStride);
+                if constexpr (NT == 2) {
+                    // (lane row r: positions 2 st_g, 2 st_g + 1 of pair r -> pairs 2 (r / 2), 2 (r / 2) + 1 of position 2 st_g + r % 2)
+                    const auto s = __builtin_amdgcn_permlane16_swap(w[q][0], w[q][1], false, false);
+                    *reinterpret_cast<u32x2*>(dst) = u32x2{s[0], s[1]};
+                } else {
+                    *dst = w[q][0];
+                }
+            }
+        }
     };
     auto edge_store = [&](int slot, int hbuf, int hrow) { if (!(GANCE_UPFIRS_ABLATE & 64)) ring_e[slot * kSlotUnits] = halo_e[hbuf * kHaloUnits + (hrow * kHaloCols + 1) * kPlanes]; };
     // halo side buffer of a chunk: task = (row, column, k-group); unit [(row * 4 + column) * 12 + part * 4 + k-group]
     // (every lane has one: the lanes beyond the 144 repeat the first ones -- the same values to the same place, no branch)
     const int h_task = tid < kHaloTasks ? tid : tid - kHaloTasks;
     const int h_col = h_task & 3, h_kg = (h_task >> 2) & 3, h_row = h_task >> 4;
-    const int h_voff = ((h_kg * 8 * Hp + h_row) * Wp + X0 + 2 + (h_col & 1) + (h_col >> 1) * 65) * 4;  // bordered columns of X0 - 2, X0 - 1, X0 + 63, X0 + 64
+    const int h_voff = ((h_kg * 8 * Hp + h_row) * Wp + X0 + 2 + (h_col & 1) + (h_col >> 1) * (kSW + 1)) * 4;  // bordered columns of X0 - 2, X0 - 1, X0 + kSW - 1, X0 + kSW
     u32x4* const halo_w = halo + (h_row * kHaloCols + h_col) * kPlanes + h_kg;
     unsigned hraw[8];
     auto halo_load = [&](int step, int chunk) {
@@ -361,12 +413,14 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
     halo_load(s_first, 0);
     if constexpr (!kPre)
         for (int i = tid; i < p.Cin; i += 256) s_lds[i] = p.s[(size_t)b * p.s_stride + i];
-    if (tid < kBM) {
+    if (tid < kBMB) {
         d_lds[tid] = p.d[(size_t)b * p.d_stride + m0 + tid];
         b_lds[tid] = p.bias[m0 + tid];
         sn_lds[tid] = p.s_next != nullptr ? p.s_next[(size_t)b * p.s_stride + m0 + tid] : 1.0f;
     }
     for (int i = tid; i < kCarryFloats; i += 256) carry[i] = 0.f;
+    if constexpr (NT > 1)  // (T columns 2 X0 - 1 and 2 X0 + 2 kSW + 1 of a narrow strip are outside the image: zero, never written)
+        for (int i = tid; i < kPassCh * NT * kPassRows; i += 256) stage[i * kTW] = stage[i * kTW + 2 * kSW + 2] = stage[i * kTW + 2 * kSW + 3] = 0.f;
 #pragma unroll
     for (int t = 1; t < 9; ++t) load_a3(0, t, A[t]);
     if constexpr (!kPre) lds_barrier();  // (the style vector is read by the first writes)
@@ -406,7 +460,8 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 accf[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // position row y' = H (last step): classes EE, EO
-        f32x4 acch = f32x4{0.f, 0.f, 0.f, 0.f}, acchf = f32x4{0.f, 0.f, 0.f, 0.f};  // halo tile (this wave's class) and its row y' = H
+        // halo tile (this wave's class; narrow strips: classes EE, OE of the right side) and its row y' = H
+        f32x4 acch[NT == 1 ? 1 : 2] = {}, acchf = f32x4{0.f, 0.f, 0.f, 0.f};
 
         auto run_chunk = [&](auto parity, const int chunk) {
             constexpr int ab = decltype(parity)::value;
@@ -420,7 +475,7 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
                 // row j + 5: issue its loads into the registers that row j + 2 leaves. (9 rows per chunk is odd: the fragment buffers
                 // alternate by j + chunk parity; the chunk loop is unrolled by two and a step has an even number of chunks)
                 const int cur = (j + ab) & 1;
-                if (j == 0) weights_dma(n_chunk);
+                if (NT == 1 && j == 0) weights_dma(n_chunk);
                 if (j == 0) halo_load(n_step, n_chunk);
                 if (j == 4) halo_store(n_chunk, ab ^ 1);
                 load_b((j + 1) % kRing, Bf[cur ^ 1]);
@@ -478,14 +533,19 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
                                     __builtin_bit_cast(bf16x8, A[t][kTerms[term][1]]), __builtin_bit_cast(bf16x8, Bf[cur][tap_dx(t)][kTerms[term][0]]),
                                     accf[tap_cls(t)], 0, 0, 0);
                         }
-                        if (wave == tap_cls(t) && !(GANCE_UPFIRS_ABLATE & 64)) {
+                        // (a narrow strip is the image's whole width: its left halo column and the dx = 0 taps of its right one read the
+                        // zero border; what is left are the dx = -1 taps of classes EE and OE on the right side, tile column 0 / 1 of a
+                        // channel tile taking one class each, or the one wave of a tile both)
+                        const int hc = NT == 1 ? 0 : tap_cls(t) >> 1;
+                        const bool halo_mine = NT == 1 ? wave == tap_cls(t) : (tap_dx(t) && (tap_cls(t) & 1) == 0 && (kTC == 1 || tc == hc));
+                        if (halo_mine && !(GANCE_UPFIRS_ABLATE & 64)) {
                             u32x4 hf[3];
 #pragma unroll
                             for (int q = 0; q < 3; ++q) hf[q] = halo_r[ab * kHaloUnits + ((1 - tap_dy(t)) * kHaloCols + 1 - tap_dx(t)) * kPlanes + q * 4];
 #pragma unroll
                             for (int term = 0; term < 6; ++term)
-                                acch = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[t][kTerms[term][1]]),
-                                                                               __builtin_bit_cast(bf16x8, hf[kTerms[term][0]]), acch, 0, 0, 0);
+                                acch[hc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[t][kTerms[term][1]]),
+                                                                                    __builtin_bit_cast(bf16x8, hf[kTerms[term][0]]), acch[hc], 0, 0, 0);
                             if (last_step && tap_dy(t)) {
                                 // (its row y' = H: every slot of a side reads the side's column in the chunk's last row)
 #pragma unroll
@@ -496,10 +556,11 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
                                                                                     __builtin_bit_cast(bf16x8, hf[kTerms[term][0]]), acchf, 0, 0, 0);
                             }
                         }
-                        read_a3(t, A[t]);
+                        if constexpr (NT == 1) read_a3(t, A[t]);
+                        else load_a3(n_chunk, t, A[t]);  // (narrow strips: each wave its own channel tile's, from global; the compiler counts the wait)
                     }
                 }
-                if (j == kRows - 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");  // (the next chunk's weight fragments: see weights_dma)
+                if (NT == 1 && j == kRows - 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");  // (the next chunk's weight fragments: see weights_dma)
                 if (!(GANCE_UPFIRS_ABLATE & 32)) lds_barrier();
             }
         };
@@ -513,19 +574,23 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
         // Ported from upfir16_fused.hip: only the dump differs (a wave holds a tile COLUMN of all rows: half rw = its rows 4 rw .. 4 rw + 3).
         const int elane = fresh_lane();
         const int en16 = elane & 15, eq4 = elane >> 4;
-        const int dump_base = eq4 * (kPassRows * kTW) + 32 * wave + 2 * en16 + 1;
-        const int hpy = wave >> 1, hpx = wave & 1;  // the halo tile's class held by this wave
-        const int fc = wave;
-        const int cg = elane % kCG;
-        const int rg = elane / kCG;
-        const int o_voff = (int)((fc * oplane + (long long)(kFR * rg) * OWp + 4 * cg) * 4);
+        const int dump_base = (4 * ct + eq4) * (kPassRows * kTW) + 32 * tc + 2 * en16 + 1;
+        const int hpy = wave >> 1, hpx = wave & 1;  // the halo tile's class held by this wave (NT = 1)
+        // filter threads: NT stage channels per wave, 64 / NT threads each; stage channel fc = 4 ct + q is block channel 16 ct + 4 g + q
+        const int fsub = NT == 1 ? 0 : elane / (64 / NT), flane = NT == 1 ? elane : elane % (64 / NT);
+        const int fc = NT == 1 ? wave : wave * NT + fsub;
+        const int fch = NT == 1 ? fc : 16 * (fc >> 2) + (fc & 3);  // (+ 4 g)
+        const int cg = flane % kCG;
+        const int rg = flane / kCG;
+        const int o_voff = (int)((fch * oplane + (long long)(kFR * rg) * OWp + 4 * cg) * 4);
 
         auto run_passes = [&](auto flush_tag) {
             constexpr bool kFlush = decltype(flush_tag)::value;
             const int ys = kFlush ? H : y0;  // first position row of the passes
             if (kNoise) {
 #pragma unroll
-                for (int i = 0; i < kNzPieces / 4; ++i) {
+                for (int i = 0; i < (kNzPieces + 3) / 4; ++i) {
+                    if (kNzPieces % 4 != 0 && wave + 4 * i >= kNzPieces) break;
                     const int f = (wave + 4 * i) * 256 + 4 * elane;
                     const int row = f / (2 * kSW), col = f % (2 * kSW);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(nz_rsrc, (lds_ptr_t)(nz_lds + (wave + 4 * i) * 256), 16,
@@ -546,10 +611,15 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
                         // (only T row 2H exists: even row parity; the odd row of the window reads as zero)
 #pragma unroll
                         for (int c = 0; c < 4; ++c) stage[dump_base + (c >> 1) * kTW + (c & 1)] = c < 2 ? accf[c][g] : 0.f;
-                        if (en16 == 0 || en16 == 8) {
-                            const int side = en16 >> 3;
-                            if (hpy == 0 && (side == 1 || hpx == 1)) stage[eq4 * (kPassRows * kTW) + (side ? 2 * kSW + 1 + hpx : 0)] = acchf[g];
-                            if (hpy == 1 && (side == 1 || hpx == 1)) stage[eq4 * (kPassRows * kTW) + kTW + (side ? 2 * kSW + 1 + hpx : 0)] = 0.f;
+                        if constexpr (NT == 1) {
+                            if (en16 == 0 || en16 == 8) {
+                                const int side = en16 >> 3;
+                                if (hpy == 0 && (side == 1 || hpx == 1)) stage[eq4 * (kPassRows * kTW) + (side ? 2 * kSW + 1 + hpx : 0)] = acchf[g];
+                                if (hpy == 1 && (side == 1 || hpx == 1)) stage[eq4 * (kPassRows * kTW) + kTW + (side ? 2 * kSW + 1 + hpx : 0)] = 0.f;
+                            }
+                        } else if (en16 == 8 && tc == 0) {  // (the EE wave of the channel tile: T column 2 W)
+                            stage[(4 * ct + eq4) * (kPassRows * kTW) + 2 * kSW + 1] = acchf[g];
+                            stage[(4 * ct + eq4) * (kPassRows * kTW) + kTW + 2 * kSW + 1] = 0.f;
                         }
                     } else {
 #pragma unroll
@@ -557,13 +627,19 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
 #pragma unroll
                             for (int c = 0; c < 4; ++c) stage[dump_base + (2 * r4 + (c >> 1)) * kTW + (c & 1)] = acc[4 * rw + r4][c][g];
                         const int row = en16 & 7, side = en16 >> 3;
-                        if ((side == 1 || hpx == 1) && row / 4 == rw)
-                            stage[eq4 * (kPassRows * kTW) + (2 * (row % 4) + hpy) * kTW + (side ? 2 * kSW + 1 + hpx : 0)] = acch[g];
+                        if constexpr (NT == 1) {
+                            if ((side == 1 || hpx == 1) && row / 4 == rw)
+                                stage[eq4 * (kPassRows * kTW) + (2 * (row % 4) + hpy) * kTW + (side ? 2 * kSW + 1 + hpx : 0)] = acch[0][g];
+                        } else if (side == 1 && row / 4 == rw) {
+#pragma unroll
+                            for (int h = 0; h < 2; ++h)  // (class EE / OE: T row parity h of column 2 W)
+                                if (kTC == 1 || tc == h) stage[(4 * ct + eq4) * (kPassRows * kTW) + (2 * (row % 4) + h) * kTW + 2 * kSW + 1] = acch[h][g];
+                        }
                     }
                     lds_barrier();
 
                     // -- filter (see upfir16_fused.hip): window row i of row group rg = row R = kFR rg + i of (three carried T rows, the pass's eight) --
-                    const int ch = 4 * g + fc;
+                    const int ch = 4 * g + fch;
                     const float dsc = d_lds[ch] * kSqrt2f;
                     const float kh0 = 0.25f * dsc, kh1 = 0.75f * dsc;
                     const float bias2 = b_lds[ch] * kSqrt2f;
@@ -615,7 +691,7 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
             }
         };
         if (GANCE_UPFIRS_ABLATE & 2) {  // (the accumulators stay alive: a store that never happens)
-            float sum = acch[0] + acchf[0] + accf[0][0] + accf[1][0];
+            float sum = acch[0][0] + acchf[0] + accf[0][0] + accf[1][0];
 #pragma unroll
             for (int r = 0; r < kTH; ++r)
 #pragma unroll
@@ -633,6 +709,11 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
 
 bool upfirs_supported(int cin, int cout, int H, int W) {
     return H == W && W % kSW == 0 && H % kTH == 0 && cin % (2 * kKC) == 0 && cout % kBM == 0 && cin <= 512;
+}
+
+// the narrow forms: inputs 32 and 16 wide, one strip of the whole width, 64 / W channel tiles per block
+bool upfirs_narrow_supported(int cin, int cout, int H, int W) {
+    return H == W && (W == 32 || W == 16) && H % kTH == 0 && cin % (2 * kKC) == 0 && cout % (kBM * (kSW / W)) == 0 && cin <= 512;
 }
 
 size_t upfirs_weight_floats(int cin, int cout) { return (size_t)(cout / kBM) * (cin / kKC) * 27 * 256; }  // (27 KB per channel tile and chunk)
@@ -673,9 +754,20 @@ void upfirs_arrange_weights(const float* w_in, int cin, int cout, const int* up_
 }
 
 void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* a) {
+    a->step_rows = kTH;
+    a->stagger_phases = 1;
+    a->stagger_ticks = 0;
+    a->debug_flags = 0;
+    if (W < kSW) {  // (a narrow strip: blocks of 64 / W channel tiles; an image of two or four steps is never cut into segments)
+        a->m_tiles = cout / (kBM * (kSW / W));
+        a->strips = 1;
+        a->segs = 1;
+        a->rows_per_seg = H;
+        a->total_blocks = B * a->m_tiles;
+        return;
+    }
     a->m_tiles = cout / kBM;
     a->strips = W / kSW;
-    a->step_rows = kTH;
     // Row segments only where whole images leave CUs idle: each costs a priming step of 8 rows, so segments of at least
     // GANCE_UPFIRS_MIN_SEG_ROWS rows, powers of two, until every CU has a block (GANCE_TUNE_UPFIR_SPLIT_SEGS=0: never)
     static const bool segments = [] { const char* v = std::getenv("GANCE_TUNE_UPFIR_SPLIT_SEGS"); return !(v && std::atoi(v) == 0); }();
@@ -690,38 +782,53 @@ void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* a) {
     a->segs = segs;
     a->rows_per_seg = H / segs;
     a->total_blocks = base * segs;
-    a->stagger_phases = 1;
-    a->stagger_ticks = 0;
-    a->debug_flags = 0;
 }
 
-__global__ __launch_bounds__(256, 1) void upfirs_fused_kernel(const UpFirArgs p) { upfirs_body<false, false>(p); }
-__global__ __launch_bounds__(256, 1) void upfirs_fused_noise_kernel(const UpFirArgs p) { upfirs_body<false, true>(p); }
-__global__ __launch_bounds__(256, 1) void upfirs_fused_pre_kernel(const UpFirArgs p) { upfirs_body<true, false>(p); }
-__global__ __launch_bounds__(256, 1) void upfirs_fused_pre_noise_kernel(const UpFirArgs p) { upfirs_body<true, true>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_fused_kernel(const UpFirArgs p) { upfirs_body<1, false, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_fused_noise_kernel(const UpFirArgs p) { upfirs_body<1, false, true>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_fused_pre_kernel(const UpFirArgs p) { upfirs_body<1, true, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_fused_pre_noise_kernel(const UpFirArgs p) { upfirs_body<1, true, true>(p); }
+// the narrow forms: inputs 32 wide (two channel tiles per block) and 16 wide (four)
+__global__ __launch_bounds__(256, 1) void upfirs_w32_fused_kernel(const UpFirArgs p) { upfirs_body<2, false, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w32_fused_noise_kernel(const UpFirArgs p) { upfirs_body<2, false, true>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w32_fused_pre_kernel(const UpFirArgs p) { upfirs_body<2, true, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w32_fused_pre_noise_kernel(const UpFirArgs p) { upfirs_body<2, true, true>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w16_fused_kernel(const UpFirArgs p) { upfirs_body<4, false, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w16_fused_noise_kernel(const UpFirArgs p) { upfirs_body<4, false, true>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w16_fused_pre_kernel(const UpFirArgs p) { upfirs_body<4, true, false>(p); }
+__global__ __launch_bounds__(256, 1) void upfirs_w16_fused_pre_noise_kernel(const UpFirArgs p) { upfirs_body<4, true, true>(p); }
 
 hipError_t launch_upfir_split(const UpFirArgs& args, hipStream_t stream) {
     using Kernel = void (*)(const UpFirArgs);
-    static const Kernel kernels[4] = {upfirs_fused_kernel, upfirs_fused_noise_kernel, upfirs_fused_pre_kernel, upfirs_fused_pre_noise_kernel};  // [pre * 2 + noise]
+    // [geometry: W >= 64, 32, 16][pre * 2 + noise]
+    static const Kernel kernels[3][4] = {
+        {upfirs_fused_kernel, upfirs_fused_noise_kernel, upfirs_fused_pre_kernel, upfirs_fused_pre_noise_kernel},
+        {upfirs_w32_fused_kernel, upfirs_w32_fused_noise_kernel, upfirs_w32_fused_pre_kernel, upfirs_w32_fused_pre_noise_kernel},
+        {upfirs_w16_fused_kernel, upfirs_w16_fused_noise_kernel, upfirs_w16_fused_pre_kernel, upfirs_w16_fused_pre_noise_kernel}};
+    static size_t (*const lds_of[3])(int) = {lds_bytes<1>, lds_bytes<2>, lds_bytes<4>};
     static PerDeviceInt ready;  // the dynamic-LDS opt-in is per device
     int unused = 0;
     const hipError_t e = ready.get(
         [&](int, int* value) {
             *value = 1;
-            for (int i = 0; i < 4; ++i) {
-                const hipError_t err =
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(i >= 2 ? 0 : 512));
-                if (err != hipSuccess) return err;
-            }
+            for (int gi = 0; gi < 3; ++gi)
+                for (int i = 0; i < 4; ++i) {
+                    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[gi][i]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                               (int)lds_of[gi](i >= 2 ? 0 : 512));
+                    if (err != hipSuccess) return err;
+                }
             return hipSuccess;
         },
         &unused);
     if (e != hipSuccess) return e;
-    if (!upfirs_supported(args.Cin, args.Cout, args.H, args.W) || args.segs < 1 || args.rows_per_seg * args.segs != args.H || args.rows_per_seg % kTH != 0 ||
-        args.total_blocks != args.B * args.m_tiles * args.strips * args.segs)
+    const int gi = args.W % kSW == 0 ? 0 : (args.W == 32 ? 1 : 2);
+    const bool narrow = gi != 0;
+    if (!(narrow ? upfirs_narrow_supported(args.Cin, args.Cout, args.H, args.W) : upfirs_supported(args.Cin, args.Cout, args.H, args.W)) || args.segs < 1 ||
+        args.rows_per_seg * args.segs != args.H || args.rows_per_seg % kTH != 0 || args.total_blocks != args.B * args.m_tiles * args.strips * args.segs ||
+        (narrow && (args.segs != 1 || args.strips != 1 || args.m_tiles * kBM * (kSW / args.W) != args.Cout)))
         return hipErrorInvalidValue;
     const int pre = args.input_prescaled ? 1 : 0, noise = args.noise != nullptr ? 1 : 0;
-    hipLaunchKernelGGL(kernels[2 * pre + noise], dim3(args.total_blocks), dim3(256), lds_bytes(pre ? 0 : args.Cin), stream, args);
+    hipLaunchKernelGGL(kernels[gi][2 * pre + noise], dim3(args.total_blocks), dim3(256), lds_of[gi](pre ? 0 : args.Cin), stream, args);
     return hipGetLastError();
 }
 
