@@ -24,6 +24,7 @@
 
 #include "../../include/gance_hip.h"
 #include "kernels.h"
+#include "engine_plan.h"
 
 namespace {
 
@@ -58,10 +59,6 @@ int nf(int stage) {
     return std::min(std::max(v, 1), 512);
 }
 
-struct ConvLayerHost {
-    int layer_idx, res_log2, cin, cout;
-    bool up;
-};
 struct RgbLayerHost {
     int res_log2, cin, row;
 };
@@ -95,90 +92,6 @@ int ilog2_exact(int v) {
     int l = 0;
     while ((1 << l) < v) ++l;
     return (1 << l) == v ? l : -1;
-}
-
-// One launch of the conv kernel: a stride-1 conv, or a transposed conv with its four parity classes
-// fused. Wide transposed convs (BM = 128) tile the H x W position grid exactly with 8x8 tiles and
-// cover the extra position row y' = H / column x' = W with 1x64 / 64x1 strip tiles in the SAME
-// launch (runtime tile geometry); the narrow ones tile the (H+1) x (W+1) grid directly.
-struct LayerPlan {
-    int tile_id;
-    int OH, OW;  // output bound for masking: H x W, or (H+1) x (W+1) positions when up
-    int tiles_x, tiles_y, tiles_b, row_tiles, col_tiles;
-    int m_tiles, nsplit, chunks_per_split, total_chunks, total_blocks;
-};
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-int layer_bm(int cout) { return cout == 32 ? 32 : (cout == 64 ? 64 : 128); }
-
-// K chunk (input channels per LDS stage) of the narrow layers. Tunable for experiments:
-// GANCE_TUNE_KC_CONV = 4 or 8 (read once). Transposed convs use 8.
-int tuned_kc(bool up) {
-    static const int conv_kc = [] { const char* v = std::getenv("GANCE_TUNE_KC_CONV"); return v && std::atoi(v) == 8 ? 8 : 4; }();
-    static const int up_kc = [] { const char* v = std::getenv("GANCE_TUNE_KC_UP"); return v && std::atoi(v) == 4 ? 4 : 8; }();
-    return up ? up_kc : conv_kc;
-}
-// GANCE_TUNE_KC_UP128 = 2: the wide transposed convs stage 2 input channels per chunk (tile 14)
-int tuned_kc_up128() {
-    static const int kc = [] { const char* v = std::getenv("GANCE_TUNE_KC_UP128"); return v && std::atoi(v) == 2 ? 2 : 4; }();
-    return kc;
-}
-int layer_kc(int cout, bool up) { return layer_bm(cout) == 128 ? (up ? tuned_kc_up128() : 4) : tuned_kc(up); }
-
-int choose_tile(int cout, bool up, int OH, int OW, int B) {
-    const bool kc4 = tuned_kc(up) == 4;
-    if (cout == 32) return up ? (kc4 ? 12 : 6) : (kc4 ? 10 : 0);
-    if (cout == 64) return up ? (kc4 ? 13 : 7) : (kc4 ? 11 : 1);
-    if (up) return tuned_kc_up128() == 2 ? 14 : 8;
-    const int first = 2, last = 5;
-    int best = first;
-    long best_tiles = -1;
-    for (int id = first; id <= last; ++id) {
-        const auto& t = gance::kConvTiles[id];
-        const long tiles = (long)ceil_div(B, t.TB) * ceil_div(OH, t.TH) * ceil_div(OW, t.TW);
-        if (best_tiles < 0 || tiles < best_tiles) {
-            best_tiles = tiles;
-            best = id;
-        }
-    }
-    return best;
-}
-
-int choose_nsplit(int base_blocks, int chunks) {
-    if (base_blocks >= 384) return 1;
-    const int want = ceil_div(768, base_blocks);
-    for (int d = 1; d <= chunks; ++d)
-        if (chunks % d == 0 && d >= want) return d;
-    return chunks;
-}
-
-LayerPlan plan_layer(const ConvLayerHost& c, int B) {
-    LayerPlan p{};
-    const int res = 1 << c.res_log2;
-    // strips pay once the position grid has several tiles per side; below that the launch is
-    // latency-bound and extra blocks only hurt
-    // (GANCE_TUNE_STRIPS_MIN, read once: smallest input side that takes the strips; default 16)
-    static const int strips_min = [] { const char* v = std::getenv("GANCE_TUNE_STRIPS_MIN"); return v ? std::atoi(v) : 16; }();
-    const bool strips = c.up && layer_bm(c.cout) == 128 && res / 2 >= strips_min;
-    const int grid = c.up ? (strips ? res / 2 : res / 2 + 1) : res;  // the tiled grid
-    p.OH = p.OW = c.up ? res / 2 + 1 : res;
-    p.tile_id = choose_tile(c.cout, c.up, grid, grid, B);
-    const auto& t = gance::kConvTiles[p.tile_id];
-    p.tiles_x = ceil_div(grid, t.TW);
-    p.tiles_y = ceil_div(grid, t.TH);
-    p.tiles_b = ceil_div(B, t.TB);
-    p.row_tiles = strips ? ceil_div(res / 2 + 1, 64) : 0;
-    p.col_tiles = strips ? ceil_div(res / 2, 64) : 0;
-    p.m_tiles = c.cout / t.BM;
-    p.total_chunks = c.cin / t.KC;
-    const int base = p.m_tiles * (p.tiles_x * p.tiles_y + p.row_tiles + p.col_tiles) * p.tiles_b;
-    p.nsplit = choose_nsplit(base, p.total_chunks);
-    if (c.up) p.nsplit = std::min(p.nsplit, 8);  // the FIR pass re-reads every slab
-    while (p.total_chunks % p.nsplit) --p.nsplit;
-    p.chunks_per_split = p.total_chunks / p.nsplit;
-    p.total_blocks = base * p.nsplit;
-    return p;
 }
 
 // zero-bordered geometry
@@ -248,8 +161,6 @@ struct gance_workspace {
     }
 };
 
-constexpr int kWino43DefaultMaxRes = 1024;  // every Conv1 from 32x32 up (measured faster than the F(2x2,3x3) kernels on all six: DESIGN.md §3)
-
 struct GraphEntry {
     hipGraphExec_t exec = nullptr;
     bool warmed = false;
@@ -269,9 +180,9 @@ struct gance_engine {
     // offsets into pool
     size_t map_w[kMappingLayers]{}, map_b[kMappingLayers]{};
     size_t avg_off = 0, const_off = 0, A_off = 0, bias1_off = 0, w2_off = 0;
-    std::vector<size_t> conv_w, conv_bias, conv_noise;
-    std::vector<size_t> wino_w;  // Winograd-domain weights of the stride-1 layers that support them (else SIZE_MAX)
-    std::vector<size_t> wino64_w;  // the same for the 64-channel Winograd kernel (layers with >= 64 output channels)
+    std::vector<size_t> conv_bias, conv_noise;
+    Tuning tune;                  // the process's tuning, with the per-engine knobs as they stood when this engine was created
+    std::vector<LayerCaps> caps;  // per conv layer: the forms this engine may run it in, and where their weight images sit in the pool
     // randomize_noise (the vector path): per-sample planes drawn by gance_engine_randomize_noise, layer li at
     // noise_rand + noise_rand_off[li] as [max_batch][res][res] (SIZE_MAX: the layer's strength is zero, it reads no noise);
     // while noise_randomized the conv launches read these (a plane per sample), else the stored buffers in the pool
@@ -279,18 +190,7 @@ struct gance_engine {
     std::vector<size_t> noise_rand_off;
     int noise_rand_count = 0;  // samples the last draw covered
     bool noise_randomized = false;
-    std::vector<size_t> wino43_w;  // F(4x4, 3x3) weights (winograd43_conv.hip), SIZE_MAX where the layer does not take that form
-    std::vector<size_t> upfir_w;  // fused transposed-conv + FIR kernel's weight image of the up layers that support it (else SIZE_MAX)
-    std::vector<size_t> upfir16_w;  // the same for its 16-channel, two-blocks-per-CU geometry (upfir16_fused.hip)
-    std::vector<size_t> winogemm_w;  // weight image of the Winograd F(4x4,3x3) GEMM form of the stride-1 layers at 8x8, 16x16 (gemm_forms.hip; else SIZE_MAX)
-    std::vector<size_t> upgemm_w;  // weight image of the scatter-form GEMM of the two smallest up layers (gemm_forms.hip; else SIZE_MAX)
     size_t up_packed_floats = 0, up_prod_floats = 0;
-    int gemm_bf16 = 0;  // experiment (GANCE_TUNE_GEMM_BF16X6 when the engine is created): 1 = the GEMM forms on the bf16 matrix cores from split operands, bf16 x 3 (six terms); any non-zero value selects it (a stale 2, the removed fp16 x 2 mode, too)
-    std::vector<size_t> upfir16x_w;  // ... and for that geometry's pair form (F(2,2) along x: 15 MFMAs per pair of columns instead of 18)
-    std::vector<size_t> upfirs_w;    // split-operand form of the fused up kernel (upfir_split.hip: three bf16 parts per value, six terms, fp32 accumulation)
-    int upfir_split = 1;  // GANCE_TUNE_UPFIR_SPLIT when the engine is created: 0 never, 1 (default) where a launch fills the chip without row segments, 2 wherever supported
-    int upfir_split_narrow = 1;  // GANCE_TUNE_UPFIR_SPLIT_NARROW: the split form's narrow geometries (inputs 32 and 16 wide) in mode 1 and 2 by the fill rule; 0 never
-    int upfir_split_max_res = 1024;  // GANCE_TUNE_UPFIR_SPLIT_MAXRES: the largest OUTPUT side that takes the split form in mode 1 (measured: DESIGN.md section 3; 512 until the staging went to 16-byte loads)
     int num_cus = 256;
     std::vector<float> conv_ns;
     std::vector<int> conv_s_off, conv_d_off;
@@ -370,74 +270,6 @@ struct FusedRgb {
     uint8_t* u8;
 };
 
-// Geometry of the fused up kernel: GANCE_TUNE_UPFIR16 (read once per process) = 0: always 32 channels per block, one block per
-// CU (upfir_fused.hip); 1: 16 channels per block, two blocks per CU (upfir16_fused.hip) wherever that kernel supports the layer.
-static int upfir16_mode() {
-    static const int mode = [] {
-        const char* v = std::getenv("GANCE_TUNE_UPFIR16");
-        return v ? std::atoi(v) : 1;
-    }();
-    return mode;
-}
-
-// GANCE_TUNE_UPFIR16X (read once per process) = 0: the fused up layers whose input the 64-column strips tile stay in direct form; 1
-// (default): they run in the pair form (F(2,2) along x) when their input arrives pre-scaled.
-static int upfir16x_mode() {
-    static const int mode = [] {
-        const char* v = std::getenv("GANCE_TUNE_UPFIR16X");
-        return v ? std::atoi(v) : 1;
-    }();
-    return mode;
-}
-
-// GANCE_TUNE_UPGEMM (read once per process): the two smallest up layers (4x4 -> 8x8, 8x8 -> 16x16) run in scatter form (gemm_forms.hip:
-// one dense GEMM, no position grid to tile) when a call has at least this many GEMM columns (samples x input positions); 0 = never.
-// Default 128 (one column tile): from 2 samples at 8x8, 8 at 4x4. Measured (tools/gpu_gemm_threshold_sweep.sh, frames/s at 4 ... 32 frames
-// per call): every threshold from 32 to 128 within 0.3 %, 256 / 512 -0.5 ... -1.5 %, 1 (always) -2 % at one frame per call.
-static int upgemm_min_columns() {
-    static const int columns = [] {
-        const char* v = std::getenv("GANCE_TUNE_UPGEMM");
-        return v ? std::atoi(v) : 128;
-    }();
-    return columns;
-}
-
-// GANCE_TUNE_UPGEMM_COLUMNS (read once per process): the scatter form's product buffer, in GEMM columns of a 512-channel layer (75 MB per 4096).
-// Default 16384 (302 MB): every up layer from 4 -> 8 to 128 -> 256 of a call of up to 4 ... 8 frames fits, i.e. up to where the fused up
-// kernel takes over (tools/gpu_upgemm_cap_sweep.sh: +2 ... 4 % frames/s at 2 ... 7 frames per call against 4096).
-static int upgemm_buffer_columns() {
-    static const int columns = [] {
-        const char* v = std::getenv("GANCE_TUNE_UPGEMM_COLUMNS");
-        return v ? std::max(4096, std::atoi(v)) : 16384;
-    }();
-    return columns;
-}
-
-// GANCE_TUNE_WINOGEMM (read once per process): the stride-1 layers at 8x8 and 16x16 run in Winograd F(4x4,3x3) GEMM form (gemm_forms.hip)
-// when a call has at least this many GEMM columns (samples x 4x4 output tiles); 0 = never. Default 64: from 4 samples at 16x16, 16 at
-// 8x8 (the same sweep). Like every Winograd form it is off in engines created with conv_form "direct" (or "winograd": F(2x2,3x3) only).
-static int winogemm_min_columns() {
-    static const int columns = [] {
-        const char* v = std::getenv("GANCE_TUNE_WINOGEMM");
-        return v ? std::atoi(v) : 64;
-    }();
-    return columns;
-}
-
-// Largest resolution whose Conv1 runs in Winograd F(4x4, 3x3) form (winograd43_conv.hip) in an engine with these
-// flags: GANCE_FLAG_WINOGRAD43 = every resolution the kernel supports; otherwise the default limit, which
-// GANCE_TUNE_WINO43 (read once per process: 0 = off, else a resolution) overrides.
-static int wino43_max_res(int flags) {
-    static const int env_value = [] {
-        const char* v = std::getenv("GANCE_TUNE_WINO43");
-        return v ? std::atoi(v) : -1;
-    }();
-    if (flags & GANCE_FLAG_DIRECT_CONV) return 0;
-    if (flags & GANCE_FLAG_WINOGRAD43) return 1 << 20;
-    if (flags & GANCE_FLAG_FORCE_WINOGRAD) return 0;  // FORCE_WINOGRAD alone = the F(2x2,3x3) kernels on every layer (parity tests of that form)
-    return env_value >= 0 ? env_value : kWino43DefaultMaxRes;
-}
-
 // The noise conv layer li adds, and the distance between the planes of two samples: the stored buffer [res][res] shared by
 // the batch (stride 0), or after gance_engine_randomize_noise the drawn planes [sample][res][res]; nullptr where the
 // layer's strength is zero.
@@ -451,15 +283,23 @@ const float* layer_noise(const gance_engine* e, int li, int* b_stride) {
     return e->pool + e->conv_noise[li];
 }
 
-int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p, const float* x,
-             long long x_b_stride, int H, int W, float* out, int epilogue, int out_row_stride,
-             int out_y_off, int out_x_off, long long out_b_stride, long long out_c_stride,
-             long long slab_stride, long long cls_stride, int B, hipStream_t stream,
-             const char* name, const FusedRgb* rgb = nullptr, bool winograd = false, bool wino64 = false,
-             const float* s_next = nullptr, bool wino43 = false) {
+// ---- one helper per argument struct: (engine, layer, its plan record, where the data is) -> what the launcher takes ----
+
+// where a conv launch writes: the layer's zero-bordered activation, dense split-K slabs, or an up layer's parity planes
+struct ConvOut {
+    float* out;
+    int epilogue, row_stride, y_off, x_off;
+    long long b_stride, c_stride, slab_stride, cls_stride;
+};
+
+gance::ConvArgs conv_args(const gance_engine* e, int li, const LayerStep& step, const float* x, long long x_b_stride, int H, int W,
+                          const ConvOut& o, int B, const FusedRgb* rgb, const float* s_next) {
+    const ConvLayerHost& c = e->convs[li];
+    const LayerCaps& caps = e->caps[li];
+    const LayerPlan& p = step.p;
     gance::ConvArgs a{};
-    a.s_next = (wino64 || wino43) ? s_next : nullptr;  // (only the 16x16x4 Winograd kernels scale their stores)
-    if (epilogue == gance::kEpilogueFullRgbPart) {  // (rgb->y: the partial image; the coefficient table is the workspace's)
+    a.s_next = s_next;
+    if (o.epilogue == gance::kEpilogueFullRgbPart) {  // (rgb->y: the partial image; the coefficient table is the workspace's)
         a.rgb_y = rgb->y;
         a.rgb_coef = e->ws->rgb_coef;
     } else if (rgb != nullptr) {
@@ -471,12 +311,16 @@ int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p
         a.rgb_u8 = rgb->u8;
     }
     a.x = x;
-    a.w = e->pool + e->conv_w[li];
+    // (F(4x4,3x3) and the 16x16x4 kernel's 32-channel geometry take the input multiplied by this layer's style: plan_call arranged
+    // that with the producing layer)
+    a.w = e->pool + (step.form == Form::Wino43 ? caps.w[kWino43]
+                                               : (step.form == Form::Wino64 ? caps.w[kWino64]
+                                                                            : ((step.form == Form::Wino || step.form == Form::WinoTorgb) ? caps.w[kWino] : caps.direct_w)));
     a.s = e->ws->styles + e->conv_s_off[li];
     a.d = e->ws->demod + e->conv_d_off[li];
     a.noise = layer_noise(e, li, &a.noise_b_stride);
     a.bias = e->pool + e->conv_bias[li];
-    a.out = out;
+    a.out = o.out;
     a.B = B;
     a.Cin = c.cin;
     a.Cout = c.cout;
@@ -495,28 +339,29 @@ int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p
     a.nsplit = p.nsplit;
     a.chunks_per_split = p.chunks_per_split;
     a.total_chunks = p.total_chunks;
-    a.epilogue = epilogue;
-    a.out_row_stride = out_row_stride;
-    a.out_y_off = out_y_off;
-    a.out_x_off = out_x_off;
-    a.out_b_stride = out_b_stride;
-    a.out_c_stride = out_c_stride;
-    a.slab_stride = slab_stride;
-    a.cls_stride = cls_stride;
+    a.epilogue = o.epilogue;
+    a.out_row_stride = o.row_stride;
+    a.out_y_off = o.y_off;
+    a.out_x_off = o.x_off;
+    a.out_b_stride = o.b_stride;
+    a.out_c_stride = o.c_stride;
+    a.slab_stride = o.slab_stride;
+    a.cls_stride = o.cls_stride;
     a.x_b_stride = x_b_stride;
-    static const int debug_flags = [] { const char* v = std::getenv("GANCE_DEBUG_CONV"); return v ? std::atoi(v) : 0; }();
-    a.debug_flags = debug_flags;
-    // Blocks per CU of the F(4x4,3x3) launches (ConvArgs::grid_rounds). Four: measured as fast as one persistent block per
-    // CU (1234 ... 1236 frames/s with 2 / 4 / 8 / 16 against 1228 with 1: the prologue of a block is a few k-steps of
-    // thousands), and a CU that something else holds for a while -- the RCCL copy kernels of the frame gather on a multi-GPU
-    // job -- then delays a quarter of its share instead of the tail of the launch. GANCE_TUNE_W43_ROUNDS=1: one block per CU.
-    static const int env_rounds = [] { const char* v = std::getenv("GANCE_TUNE_W43_ROUNDS"); return v ? std::atoi(v) : 0; }();
-    a.grid_rounds = env_rounds > 0 ? env_rounds : 4;
-    // GANCE_TUNE_W43_XCD=0: the channel tile fastest in the F(4x4,3x3) launches' tile order (round 3's); default: 4 x 8 blocking per XCD
-    // where the layer has 16 channel tiles
-    static const int env_xcd = [] { const char* v = std::getenv("GANCE_TUNE_W43_XCD"); return v ? std::atoi(v) : 1; }();
-    a.xcd_blocking = env_xcd != 0 ? 1 : 0;  // (the launcher drops it where the launch's pixel tiles are not a multiple of four)
+    a.debug_flags = e->tune.debug_conv;
+    a.grid_rounds = e->tune.w43_rounds;
+    a.xcd_blocking = e->tune.w43_xcd ? 1 : 0;  // (the launcher drops it where the launch's pixel tiles are not a multiple of four)
     a.fault_flag = e->ws->fault_flag;
+    return a;
+}
+
+int run_conv(gance_engine* e, int li, const LayerStep& step, const float* x, long long x_b_stride, int H, int W, const ConvOut& o, int B,
+             hipStream_t stream, const FusedRgb* rgb = nullptr, const float* s_next = nullptr) {
+    const ConvLayerHost& c = e->convs[li];
+    const LayerPlan& p = step.p;
+    const char* name = step.name;
+    gance::ConvArgs a = conv_args(e, li, step, x, x_b_stride, H, W, o, B, rgb, s_next);
+    const int debug_flags = e->tune.debug_conv;
     static unsigned long long* stamps = nullptr;
     if (debug_flags & 16) {
         if (stamps == nullptr) hipMalloc((void**)&stamps, (size_t)5 * 8 * 65536);
@@ -525,28 +370,23 @@ int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p
     double flops = 2.0 * 9 * (double)c.cin * c.cout * H * W * B;
     const double out_elems = (double)B * c.cout * (c.up ? 4.0 * H * W : (double)H * W) * p.nsplit;
     double bytes = 4.0 * ((double)B * c.cin * H * W + out_elems + 9.0 * c.cin * c.cout);
-    if (epilogue == gance::kEpilogueFullRgbPart) {  // + the ToRGB product and its fp32 partial image; no activation when out is null
+    if (o.epilogue == gance::kEpilogueFullRgbPart) {  // + the ToRGB product and its fp32 partial image; no activation when out is null
         flops += 2.0 * 3 * (double)c.cout * H * W * B;
-        bytes = 4.0 * ((double)B * c.cin * H * W + (out != nullptr ? out_elems : 0.0) + 9.0 * c.cin * c.cout + 3.0 * B * H * W);
+        bytes = 4.0 * ((double)B * c.cin * H * W + (o.out != nullptr ? out_elems : 0.0) + 9.0 * c.cin * c.cout + 3.0 * B * H * W);
     } else if (rgb != nullptr) {  // no activation leaves the chip: the uint8 image and the half-size skip image instead
         flops += 2.0 * 3 * (double)c.cout * H * W * B;
         bytes = 4.0 * ((double)B * c.cin * H * W + 9.0 * c.cin * c.cout + 0.75 * B * H * W) + 3.0 * B * H * W;
     }
     StepScope scope(e, stream, name, flops, bytes);
-    if (wino43) {  // F(4x4, 3x3); the input arrives multiplied by this layer's style (the caller arranged that)
-        a.w = e->pool + e->wino43_w[li];
+    if (step.form == Form::Wino43) {
         GANCE_HIP_CHECK(gance::launch_winograd43_conv(a, stream));
         return GANCE_OK;
     }
-    if (winograd) {
-        // the kernel on 16x16x4 MFMAs (in its 32-channel geometry the input arrives multiplied by this layer's style: the
-        // caller arranged that with the producing layer), else the round-1 32-channel kernel
-        if (wino64) {
-            a.w = e->pool + e->wino64_w[li];
-            GANCE_HIP_CHECK(gance::launch_winograd64_conv(a, stream));
-            return GANCE_OK;
-        }
-        a.w = e->pool + e->wino_w[li];
+    if (step.form == Form::Wino64) {
+        GANCE_HIP_CHECK(gance::launch_winograd64_conv(a, stream));
+        return GANCE_OK;
+    }
+    if (step.form == Form::Wino || step.form == Form::WinoTorgb) {  // the round-1 32-channel kernel
         GANCE_HIP_CHECK(gance::launch_winograd_conv(a, stream));
         return GANCE_OK;
     }
@@ -570,7 +410,7 @@ int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p
         const double life = (pro + main_ + epi) / 100.0;
         std::fprintf(stderr, "STAMPS %s blocks %d span %.1f us | per block: prologue %.2f us, main %.2f us, epilogue %.2f us | avg resident blocks/CU %.2f\n",
                      name, p.total_blocks, span, pro / n / 100.0, main_ / n / 100.0, epi / n / 100.0, life / span / 256.0);
-        if (std::getenv("GANCE_DEBUG_DUMP") && std::strstr(name, std::getenv("GANCE_DEBUG_DUMP"))) {
+        if (!e->tune.debug_dump.empty() && std::strstr(name, e->tune.debug_dump.c_str())) {
             for (int i = 0; i < p.total_blocks; ++i)
                 std::fprintf(stderr, "BLK %d %llu %llu %llu %llu %llx\n", i, h[5 * i] - t_min, h[5 * i + 1] - t_min, h[5 * i + 2] - t_min, h[5 * i + 3] - t_min, h[5 * i + 4]);
         }
@@ -578,9 +418,135 @@ int run_conv(gance_engine* e, const ConvLayerHost& c, int li, const LayerPlan& p
     return GANCE_OK;
 }
 
+gance::WinoGemmArgs winogemm_args(const gance_engine* e, int li, const float* x, long long x_b_stride, float* out, long long out_b_stride, int B) {
+    const ConvLayerHost& c = e->convs[li];
+    const int res = 1 << c.res_log2;
+    gance::WinoGemmArgs g{};
+    g.x = x;
+    g.w = e->pool + e->caps[li].w[kWinoGemm];
+    g.s = e->ws->styles + e->conv_s_off[li];
+    g.d = e->ws->demod + e->conv_d_off[li];
+    g.noise = layer_noise(e, li, &g.noise_b_stride);
+    g.bias = e->pool + e->conv_bias[li];
+    g.packed = e->ws->up_packed;
+    g.prod = e->ws->up_prod;
+    g.out = out;
+    g.x_b_stride = x_b_stride;
+    g.out_b_stride = out_b_stride;
+    g.noise_strength = e->conv_ns[li];
+    g.B = B;
+    g.Cin = c.cin;
+    g.Cout = c.cout;
+    g.H = res;
+    g.W = res;
+    g.s_stride = e->ctot;
+    g.d_stride = e->dtot;
+    g.n_tiles = gance::winogemm_n_tiles(B, res, res);
+    g.bf16_split = e->caps[li].gemm_split;  // (as the weights were arranged)
+    return g;
+}
+
+gance::UpGemmArgs upgemm_args(const gance_engine* e, int li, const float* x, long long x_b_stride, long long cls_stride, long long unit, int B) {
+    const ConvLayerHost& c = e->convs[li];
+    const int H = (1 << c.res_log2) / 2;
+    gance::UpGemmArgs g{};
+    g.x = x;
+    g.w = e->pool + e->caps[li].w[kUpGemm];
+    g.s = e->ws->styles + e->conv_s_off[li];
+    g.d = e->ws->demod + e->conv_d_off[li];
+    g.packed = e->ws->up_packed;
+    g.prod = e->ws->up_prod;
+    g.t = e->ws->tplanes[li];
+    g.x_b_stride = x_b_stride;
+    g.cls_stride = cls_stride;
+    g.unit_stride = unit;
+    g.B = B;
+    g.Cin = c.cin;
+    g.Cout = c.cout;
+    g.H = H;
+    g.W = H;
+    g.s_stride = e->ctot;
+    g.d_stride = e->dtot;
+    g.n_tiles = gance::upgemm_n_tiles(B, H, H);
+    g.bf16_split = e->caps[li].gemm_split;
+    return g;
+}
+
+// (the geometry comes planned in step.up)
+gance::UpFirArgs upfir_args(const gance_engine* e, int li, const LayerStep& step, const float* x, long long x_b_stride, float* out, int B,
+                            const float* s_next) {
+    const ConvLayerHost& c = e->convs[li];
+    const LayerCaps& caps = e->caps[li];
+    gance::UpFirArgs u = step.up;
+    u.pair_form = step.form == Form::UpFused16x ? 1 : 0;
+    u.x = x;
+    u.w = e->pool + (step.form == Form::UpSplit ? caps.w[kUpfirSplit]
+                                                : (step.form == Form::UpFused16x ? caps.w[kUpfir16x] : (step.form == Form::UpFused16 ? caps.w[kUpfir16] : caps.w[kUpfir])));
+    u.s = e->ws->styles + e->conv_s_off[li];
+    u.d = e->ws->demod + e->conv_d_off[li];
+    u.noise = layer_noise(e, li, &u.noise_b_stride);
+    u.bias = e->pool + e->conv_bias[li];
+    u.out = out;
+    u.B = B;
+    u.Cin = c.cin;
+    u.Cout = c.cout;
+    u.H = (1 << c.res_log2) / 2;
+    u.W = u.H;
+    u.s_stride = e->ctot;
+    u.d_stride = e->dtot;
+    u.noise_strength = e->conv_ns[li];
+    u.x_b_stride = x_b_stride;
+    u.s_next = s_next;
+    u.input_prescaled = step.input_prescaled ? 1 : 0;
+    return u;
+}
+
+gance::FirArgs fir_args(const gance_engine* e, int li, const LayerStep& step, long long cls_stride, long long unit, float* out, int B,
+                        const float* s_next) {
+    const ConvLayerHost& c = e->convs[li];
+    gance::FirArgs f{};
+    f.t = e->ws->tplanes[li];
+    f.cls_stride = cls_stride;
+    f.unit_stride = unit;
+    f.noise = layer_noise(e, li, &f.noise_b_stride);
+    f.bias = e->pool + e->conv_bias[li];
+    f.out = out;
+    f.noise_strength = e->conv_ns[li];
+    f.B = B;
+    f.C = c.cout;
+    f.H = (1 << c.res_log2) / 2;
+    f.W = f.H;
+    f.nsplit = step.form == Form::UpGemm ? 1 : step.p.nsplit;
+    f.s_next = s_next;
+    f.s_next_stride = e->ctot;
+    return f;
+}
+
+// (after a conv launch that did the channel sum: partial image in, bias and skip image added, image and/or bytes out)
+gance::ToRgbArgs torgb_args(const gance_engine* e, int ri, const LayerStep& step, const float* x, const float* y_prev, float* y, uint8_t* u8,
+                            bool skip_y_store, int B) {
+    gance::ToRgbArgs t{};
+    t.x = x;
+    t.w = e->pool + e->rgb_w[ri];
+    t.s = e->ws->styles + e->rgb_s_off[ri];
+    t.bias = e->pool + e->rgb_bias[ri];
+    t.y_prev = y_prev;
+    t.y = y;
+    t.u8 = u8;
+    t.partial = step.rgb_sum ? (step.rgb_partials == 1 ? t.y : e->ws->rgb_part) : nullptr;  // (one piece: in place)
+    t.partials = step.rgb_partials;
+    t.skip_y_store = skip_y_store;
+    t.B = B;
+    t.Cin = e->rgbs[ri].cin;
+    t.R = 1 << e->rgbs[ri].res_log2;
+    t.s_stride = e->ctot;
+    return t;
+}
+
+// Plans the call (plan_call: every form decision is made there), then walks the records: fill the argument struct, open the
+// profiling bracket under the record's name, launch.
 int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d_u8, float* d_f32,
                          hipStream_t stream) {
-    char name[64];
     {
         StepScope scope(e, stream, "styles", 2.0 * B * kDlatent * e->ctot,
                         4.0 * ((double)kDlatent * e->ctot + (double)B * e->ctot));
@@ -594,331 +560,97 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                                             (int)e->convs.size(), e->ws->demod, B, e->ctot, e->dtot,
                                             stream));
     }
+    const std::vector<LayerStep> plan = plan_call(e->convs, e->caps, e->tune, e->cfg.flags, e->num_cus, B, e->debug_stop_after);
 
     int ycur = 0;  // ybuf index holding the current skip image
     bool have_y = false;
-    const int num_convs = (int)e->convs.size();
-    const int limit = e->debug_stop_after > 0 ? std::min(e->debug_stop_after, num_convs) : num_convs;
     const float* x_in = e->pool + e->const_off;  // zero-bordered [512][6][12], shared by the batch
     long long x_b_stride = 0;
-
-    // Which form conv layer idx (a stride-1 conv) runs in for this batch. Decided in one place because the layer BEFORE
-    // a conv on the 16x16x4 Winograd kernel has to know: that kernel takes its input multiplied by its own style.
-    struct ConvForm {
-        bool fused_rgb, winograd, winograd_last, wino64, wino43;
-    };
-    auto conv_form_of = [&](int idx, bool have_y_then) -> ConvForm {
-        const ConvLayerHost& c = e->convs[idx];
-        const int res = 1 << c.res_log2;
-        const LayerPlan p = plan_layer(c, B);
-        ConvForm form{};
-        // the network's last conv absorbs its ToRGB when one block holds all channels of a pixel
-        // (BM = Cout = 32, i.e. the 1024^2 generator): neither its activation nor the fp32 image is
-        // written, only the uint8 frame (GANCE_TUNE_FUSE_RGB=0 turns this off) -- so not where a debug tap reads that activation:
-        // gance_engine_debug_read_activation would return whatever an earlier call left in the buffer
-        static const bool fuse_enabled = [] { const char* v = std::getenv("GANCE_TUNE_FUSE_RGB"); return !(v && std::atoi(v) == 0); }();
-        const auto& tile = gance::kConvTiles[p.tile_id];
-        form.fused_rgb = fuse_enabled && c.res_log2 == e->res_log2 && limit == num_convs && p.nsplit == 1 &&
-                         p.m_tiles == 1 && tile.TB == 1 && tile.BM == 32 && have_y_then && e->debug_stop_after <= 0;
-        // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry with the ToRGB product
-        // in its epilogue (GANCE_TUNE_LAST_WINO64 = 0 / 1; measured: see DESIGN.md §3)
-        static const int last_wino64 = [] { const char* v = std::getenv("GANCE_TUNE_LAST_WINO64"); return v ? std::atoi(v) : 1; }();
-        const long long last_tiles = (long long)(res / 16) * (res / 32) * B;
-        if (form.fused_rgb && last_wino64 != 0 && c.cout == 32 && e->wino64_w[idx] != SIZE_MAX && !(e->cfg.flags & GANCE_FLAG_DIRECT_CONV) &&
-            !(e->cfg.flags & GANCE_FLAG_FORCE_WINOGRAD) && last_tiles >= e->num_cus)
-            form.fused_rgb = false;
-        // Winograd F(2x2,3x3) form where the layer supports it and the launch fills the chip
-        // (one block per CU). Engine flags choose: DIRECT_CONV = never, FORCE_WINOGRAD = whatever
-        // the block count; GANCE_TUNE_WINOGRAD = 0 / 1 / 2 overrides them for tuning.
-        static const int env_mode = [] { const char* v = std::getenv("GANCE_TUNE_WINOGRAD"); return v ? std::atoi(v) : -1; }();
-        const int wino_mode = env_mode >= 0 ? env_mode
-                                            : ((e->cfg.flags & GANCE_FLAG_DIRECT_CONV) ? 0 : ((e->cfg.flags & GANCE_FLAG_FORCE_WINOGRAD) ? 2 : 1));
-        // (tiles of 8 x 64 pixels, or 16 x 32 on the 32-pixel-wide layer; the kernel has no split-K)
-        const long long wino_tiles = (long long)(c.cout / 32) * (res % 64 == 0 ? (res / 8) * (res / 64) : (res / 16) * (res / 32)) * B;
-        form.winograd = !c.up && wino_mode != 0 && e->wino_w[idx] != SIZE_MAX && (wino_mode == 2 || (p.nsplit == 1 && wino_tiles >= 256));
-        // the direct-form fused last layer stays unless Winograd is forced: the 32-channel Winograd kernel's own fused variant
-        // (built, parity-green) is register-starved in its epilogue and measured no faster; GANCE_TUNE_WINOGRAD_RGB=1 selects it
-        static const bool wino_rgb = [] { const char* v = std::getenv("GANCE_TUNE_WINOGRAD_RGB"); return v && std::atoi(v) != 0; }();
-        form.winograd_last = form.winograd && (wino_mode == 2 || wino_rgb);
-        // the kernel on 16x16x4 MFMAs (GANCE_TUNE_WINO64=0 keeps the round-1 32-channel kernel): every stride-1 conv it
-        // supports that follows an up layer (all of them do: Conv1 follows Conv0_up)
-        static const bool wino64_on = [] { const char* v = std::getenv("GANCE_TUNE_WINO64"); return !(v && std::atoi(v) == 0); }();
-        form.wino64 = !form.fused_rgb && form.winograd && wino64_on && e->wino64_w[idx] != SIZE_MAX && idx > 0 && e->convs[idx - 1].up;
-        // F(4x4, 3x3) where the layer has the weights for it (engine creation: resolution limit, geometry, an up layer in
-        // front) and the launch fills the chip; never the network's last layer while that one carries the fused ToRGB
-        const long long w43_tiles = (long long)(c.cout / 32) * (res >= 64 ? (res / 16) * (res / 64) : 1) * B;  // (32 x 32 pixels per tile on the 32-wide layer)
-        form.wino43 = !form.fused_rgb && form.winograd && e->wino43_w[idx] != SIZE_MAX && (w43_tiles >= e->num_cus || wino_mode == 2);
-        if (form.wino43) form.wino64 = false;
-        return form;
-    };
-    // Whether up layer idx runs as the fused kernel (transposed conv + FIR in one launch): where it is supported and fills
-    // the chip; GANCE_TUNE_UPFIR = 0 / 1 / 2 overrides the engine flags (never / auto / always). Decided here because the
-    // layer BEFORE it has to know: fed by a 16x16x4 Winograd launch the fused kernel takes its input pre-scaled by its style.
-    // split: the split-operand form (launch_upfir_split); fp32: the fp32-MFMA forms (launch_upfir16_fused / launch_upfir_fused)
-    enum class UpFused { no, fp32, split };
-    auto up_runs_fused = [&](int idx, gance::UpFirArgs* plan) -> UpFused {
-        const ConvLayerHost& c = e->convs[idx];
-        const int H = (1 << c.res_log2) / 2;
-        static const int upfir_env = [] { const char* v = std::getenv("GANCE_TUNE_UPFIR"); return v ? std::atoi(v) : -1; }();
-        const int upfir_mode = upfir_env >= 0 ? upfir_env
-                                              : ((e->cfg.flags & GANCE_FLAG_SPLIT_UPFIR) ? 0 : ((e->cfg.flags & GANCE_FLAG_FORCE_FUSED_UPFIR) ? 2 : 1));
-        if (!c.up || upfir_mode == 0 || (e->upfir_w[idx] == SIZE_MAX && e->upfir16_w[idx] == SIZE_MAX)) return UpFused::no;
-        gance::UpFirArgs u{};
-        u.Cin = c.cin;
-        // the split-operand form (upfir_split.hip; a block sweeps the image's height, or a row segment of it where whole images would leave
-        // CUs idle: upfirs_plan): where its launch has blocks for 9/16 of the CUs
-        if (e->upfirs_w[idx] != SIZE_MAX && upfir_mode != 0) {
-            gance::upfirs_plan(B, c.cout, H, H, e->num_cus, &u);
-            // (9/16: measured without row segments, 16 blocks per frame at every layer -- whole calls of 8 / 9 / 10 / 11 frames ran at 1053 / 842 / 909 / 940
-            // frames/s in the fp32 forms, at 953 / ~1000 / 1045 / 1106 in this one; with row segments 1 ... 8 frames per call take it too wherever 16-row
-            // segments reach that many blocks: 645 / 895 / 899 / 1080 / 934 / 1055 / 1136 / 1202 frames/s against 614 / 817 / 861 / 960 / - / 980 / - / 1047)
-            // (mode 2 forces the wide geometry only; the narrow ones -- 64 / W channel tiles per block -- take the fill rule in both modes)
-            const bool narrow = !gance::upfirs_supported(c.cin, c.cout, H, H);
-            if ((e->upfir_split == 2 && !narrow) || (u.total_blocks >= e->num_cus * 9 / 16 && 2 * H <= e->upfir_split_max_res)) {
-                if (plan != nullptr) *plan = u;
-                return UpFused::split;
-            }
-            u = gance::UpFirArgs{};
-            u.Cin = c.cin;
-        }
-        if (e->upfir16_w[idx] != SIZE_MAX)
-            gance::upfir16_plan(B, c.cout, H, H, e->num_cus, &u);
-        else
-            gance::upfir_plan(B, c.cout, H, H, e->num_cus, &u);
-        const int steps_per_seg = u.rows_per_seg / u.step_rows;
-        if (plan != nullptr) *plan = u;
-        // (the narrow strip geometries -- inputs 32 and 16 wide -- have one or two steps per image: never cut into segments)
-        return (upfir_mode == 2 || (u.total_blocks >= e->num_cus * 3 / 4 && (u.segs == 1 || steps_per_seg >= 4))) ? UpFused::fp32 : UpFused::no;
-    };
-    static const bool prescale_up = [] { const char* v = std::getenv("GANCE_TUNE_PRESCALE_UP"); return !(v && std::atoi(v) == 0); }();
-    bool x_prescaled = false;  // x_in carries the style of the layer about to read it
-    bool fused_rgb = false;
-    for (int li = 0; li < limit; ++li) {
+    for (int li = 0; li < (int)plan.size(); ++li) {
+        const LayerStep& step = plan[li];
         const ConvLayerHost& c = e->convs[li];
-        const int res = 1 << c.res_log2;
-        const LayerPlan p = plan_layer(c, B);
+        const int res = 1 << c.res_log2, H = res / 2, ri = c.res_log2 - 2;
         float* x_out = e->ws->act[li];
-        const long long out_c = (long long)act_plane(res);
-        const long long out_b = out_c * c.cout;
-        int noise_b_stride = 0;
-        const float* noise = layer_noise(e, li, &noise_b_stride);
-        const float* bias = e->pool + e->conv_bias[li];
-        bool rgb_part = false;  // this layer's conv launch also did the channel sum of its ToRGB
-        int rgb_partials = 1;   // ... in this many partial images (one per channel tile of a pixel)
-        if (!c.up) {
-            std::snprintf(name, sizeof(name), "conv%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin,
-                          c.cout);
-            const ConvForm form = conv_form_of(li, have_y);
-            x_prescaled = false;  // (set below where this launch scales its stores for the next layer)
-            // Winograd F(4x4,3x3) as 36 dense GEMMs: at 8x8 / 16x16 always (from winogemm_min_columns() columns up), at 32x32 ... 128x128 for the
-            // calls too small for the fused F(4x4,3x3) kernel (one tile per CU): one frame per call at 128x128, up to 4 at 64x64, 16 at 32x32
-            const int gemm_columns = B * (res / 4) * (res / 4);
-            const bool gemm_form = e->winogemm_w[li] != SIZE_MAX && gemm_columns >= winogemm_min_columns() && gemm_columns <= gance::kWinoGemmMaxColumns &&
-                                   !form.wino43;
-            fused_rgb = form.fused_rgb && !gemm_form;
-            const bool winograd = form.winograd, winograd_last = form.winograd_last;
-            if (gemm_form) {
-                // ("convVG": input transform + 36 GEMMs + output transform, gemm_forms.hip)
-                std::snprintf(name, sizeof(name), "convVG%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin, c.cout);
-                gance::WinoGemmArgs g{};
-                g.x = x_in;
-                g.w = e->pool + e->winogemm_w[li];
-                g.s = e->ws->styles + e->conv_s_off[li];
-                g.d = e->ws->demod + e->conv_d_off[li];
-                g.noise = noise;
-                g.bias = bias;
-                g.packed = e->ws->up_packed;
-                g.prod = e->ws->up_prod;
-                g.out = x_out;
-                g.x_b_stride = x_b_stride;
-                g.out_b_stride = out_b;
-                g.noise_strength = e->conv_ns[li];
-                g.noise_b_stride = noise_b_stride;
-                g.B = B;
-                g.Cin = c.cin;
-                g.Cout = c.cout;
-                g.H = res;
-                g.W = res;
-                g.s_stride = e->ctot;
-                g.d_stride = e->dtot;
-                g.n_tiles = gance::winogemm_n_tiles(B, res, res);
-                g.bf16_split = c.cout % 256 == 0 ? e->gemm_bf16 : 0;  // (the split GEMM's block tiles are 256 rows: as the weights were arranged)
+        const long long out_c = (long long)act_plane(res), out_b = out_c * c.cout;
+        const ConvOut activation{x_out, gance::kEpilogueFull, res + 8, 1, 4, out_b, out_c, 0, 0};
+        const float* const s_next = step.scales_stores ? e->ws->styles + e->conv_s_off[li + 1] : nullptr;
+        const long long tc = (long long)t_plane(H), unit = tc * c.cout, cls_stride = unit * e->t_units[li];  // (up layers: the parity planes)
+        switch (step.form) {
+            case Form::WinoGemm: {
+                const gance::WinoGemmArgs g = winogemm_args(e, li, x_in, x_b_stride, x_out, out_b, B);
                 const double n = (double)g.n_tiles * 128;
-                StepScope scope(e, stream, name, 2.0 * 9 * c.cin * c.cout * (double)B * res * res,
+                StepScope scope(e, stream, step.name, 2.0 * 9 * c.cin * c.cout * (double)B * res * res,
                                 4.0 * (36.0 * c.cin * c.cout + 2.0 * 36 * (c.cin + c.cout) * n + (double)B * (c.cin + c.cout) * res * res));
                 GANCE_HIP_CHECK(gance::launch_winogemm(g, stream));
-            } else if (fused_rgb) {
-                const int ri = c.res_log2 - 2;
+                break;
+            }
+            case Form::DirectTorgb:
+            case Form::WinoTorgb: {
                 FusedRgb rgb{e->pool + e->rgb_w[ri], e->ws->styles + e->rgb_s_off[ri], e->pool + e->rgb_bias[ri],
                              e->ws->ybuf[ycur], (d_f32 != nullptr || e->keep_skip_image) ? e->ws->ybuf[1 - ycur] : nullptr, d_u8};
-                std::snprintf(name, sizeof(name), "conv%s%d+torgb_%dx%d_%d->%d", winograd_last ? "W" : "", c.layer_idx, res, res, c.cin, c.cout);
-                int rc = run_conv(e, c, li, p, x_in, x_b_stride, res, res, x_out, gance::kEpilogueRgb, res + 8, 1, 4,
-                                  out_b, out_c, 0, 0, B, stream, name, &rgb, winograd_last);
-                if (rc) return rc;
+                ConvOut o = activation;
+                o.epilogue = gance::kEpilogueRgb;
+                if (int rc = run_conv(e, li, step, x_in, x_b_stride, res, res, o, B, stream, &rgb)) return rc;
                 ycur = 1 - ycur;
-            } else if (p.nsplit == 1 || winograd) {
-                // Where the 64-channel Winograd kernel holds every channel of a pixel in one block (Cout = 64 at 512^2,
-                // Cout = 32 at 1024^2) its epilogue also does the channel sum of the layer's ToRGB on the matrix pipe; the
-                // ToRGB pass below then only adds bias and skip image (and converts). The LAST layer's activation has no
-                // other reader and is not stored (unless a debug tap wants it). GANCE_TUNE_W64_RGB=0 turns this off.
-                static const bool w64_rgb_enabled = [] { const char* v = std::getenv("GANCE_TUNE_W64_RGB"); return !(v && std::atoi(v) == 0); }();
-                rgb_part = w64_rgb_enabled && ((form.wino64 && gance::winograd64_rgb_supported(c.cout)) || (form.wino43 && gance::winograd43_rgb_supported(c.cout)));
-                if (winograd) std::snprintf(name, sizeof(name), rgb_part ? "convW%d+rgb_%dx%d_%d->%d" : "convW%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin, c.cout);
-                if (form.wino43) std::snprintf(name, sizeof(name), rgb_part ? "convV%d+rgb_%dx%d_%d->%d" : "convV%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin, c.cout);
-                // the next layer's style rides on this launch's stores when that layer is a fused up kernel — and only when this
-                // launch also does the ToRGB channel sum (from the plain values): torgb_kernel would otherwise read the scaled ones
-                const float* const s_next_up =
-                    (rgb_part && (form.wino64 || form.wino43) && c.cout % 64 == 0 && prescale_up && li + 1 < limit && up_runs_fused(li + 1, nullptr) != UpFused::no)
-                        ? e->ws->styles + e->conv_s_off[li + 1]
-                        : nullptr;
-                x_prescaled = s_next_up != nullptr;
-                int rc;
-                if (rgb_part) {
-                    const int ri = c.res_log2 - 2;
-                    GANCE_HIP_CHECK(gance::launch_winograd64_rgb_coef(e->pool + e->rgb_w[ri], e->ws->styles + e->rgb_s_off[ri], e->ctot, B, c.cout,
-                                                                      e->ws->rgb_coef, stream));
-                    // (one partial image: straight into the skip buffer ToRGB finishes in place; several: the workspace's)
-                    rgb_partials = form.wino43 ? gance::winograd43_rgb_partials(c.cout) : gance::winograd64_rgb_partials(c.cout);
-                    FusedRgb part{nullptr, nullptr, nullptr, nullptr, rgb_partials == 1 ? e->ws->ybuf[have_y ? 1 - ycur : ycur] : e->ws->rgb_part, nullptr};
-                    const bool last_unread = c.res_log2 == e->res_log2 && limit == num_convs && e->debug_stop_after <= 0;
-                    rc = run_conv(e, c, li, p, x_in, x_b_stride, res, res, last_unread ? nullptr : x_out, gance::kEpilogueFullRgbPart,
-                                  res + 8, 1, 4, out_b, out_c, 0, 0, B, stream, name, &part, true, !form.wino43, s_next_up, form.wino43);
+                break;
+            }
+            case Form::Direct:
+            case Form::Wino:
+            case Form::Wino64:
+            case Form::Wino43: {
+                if (!step.rgb_sum) {
+                    if (int rc = run_conv(e, li, step, x_in, x_b_stride, res, res, activation, B, stream, nullptr, s_next)) return rc;
+                    break;
+                }
+                GANCE_HIP_CHECK(gance::launch_winograd64_rgb_coef(e->pool + e->rgb_w[ri], e->ws->styles + e->rgb_s_off[ri], e->ctot, B, c.cout,
+                                                                  e->ws->rgb_coef, stream));
+                // (one partial image: straight into the skip buffer ToRGB finishes in place; several: the workspace's)
+                FusedRgb part{nullptr, nullptr, nullptr, nullptr, step.rgb_partials == 1 ? e->ws->ybuf[have_y ? 1 - ycur : ycur] : e->ws->rgb_part, nullptr};
+                ConvOut o = activation;
+                o.epilogue = gance::kEpilogueFullRgbPart;
+                if (!step.stores_activation) o.out = nullptr;
+                if (int rc = run_conv(e, li, step, x_in, x_b_stride, res, res, o, B, stream, &part, s_next)) return rc;
+                break;
+            }
+            case Form::DirectSplitK: {
+                const long long dense_c = (long long)res * res, slab = dense_c * c.cout * B;
+                const ConvOut slabs{e->ws->slabs, gance::kEpilogueRaw, res, 0, 0, dense_c * c.cout, dense_c, slab, 0};
+                if (int rc = run_conv(e, li, step, x_in, x_b_stride, res, res, slabs, B, stream)) return rc;
+                int noise_b_stride = 0;
+                const float* noise = layer_noise(e, li, &noise_b_stride);
+                StepScope scope(e, stream, step.second, 0.0, 4.0 * (double)slab * (step.p.nsplit + 1));
+                GANCE_HIP_CHECK(gance::launch_splitk_finish(e->ws->slabs, slab, step.p.nsplit, noise, e->conv_ns[li], noise_b_stride,
+                                                            e->pool + e->conv_bias[li], x_out, B, c.cout, res, res, stream));
+                break;
+            }
+            case Form::UpFused:
+            case Form::UpFused16:
+            case Form::UpFused16x:
+            case Form::UpSplit: {
+                const gance::UpFirArgs u = upfir_args(e, li, step, x_in, x_b_stride, x_out, B, s_next);
+                StepScope scope(e, stream, step.name, 2.0 * 9 * (double)c.cin * c.cout * H * H * B,
+                                4.0 * ((double)B * c.cin * H * H + (double)B * c.cout * res * res + 9.0 * c.cin * c.cout));
+                GANCE_HIP_CHECK(step.form == Form::UpSplit ? gance::launch_upfir_split(u, stream)
+                                                           : (step.form == Form::UpFused ? gance::launch_upfir_fused(u, stream) : gance::launch_upfir16_fused(u, stream)));
+                break;
+            }
+            case Form::UpGemm:
+            case Form::UpTwoPass: {
+                if (step.form == Form::UpGemm) {
+                    const gance::UpGemmArgs g = upgemm_args(e, li, x_in, x_b_stride, cls_stride, unit, B);
+                    const double n = (double)g.n_tiles * 128;
+                    StepScope scope(e, stream, step.name, 2.0 * 9 * c.cin * c.cout * (double)B * H * H,
+                                    4.0 * (9.0 * c.cin * c.cout + 2.0 * c.cin * n + 2.0 * 9 * c.cout * n + 4.0 * unit * B));
+                    GANCE_HIP_CHECK(gance::launch_upgemm(g, stream));
                 } else {
-                    rc = run_conv(e, c, li, p, x_in, x_b_stride, res, res, x_out,
-                                  gance::kEpilogueFull, res + 8, 1, 4, out_b, out_c, 0, 0, B, stream,
-                                  name, nullptr, winograd, form.wino64, s_next_up, form.wino43);
+                    const ConvOut planes{e->ws->tplanes[li], gance::kEpilogueRaw, H + 8, 1, 4, unit, tc, unit * B, cls_stride};
+                    if (int rc = run_conv(e, li, step, x_in, x_b_stride, H, H, planes, B, stream)) return rc;
                 }
-                if (rc) return rc;
-            } else {
-                const long long dense_c = (long long)res * res;
-                const long long slab = dense_c * c.cout * B;
-                int rc = run_conv(e, c, li, p, x_in, x_b_stride, res, res, e->ws->slabs,
-                                  gance::kEpilogueRaw, res, 0, 0, dense_c * c.cout, dense_c, slab, 0,
-                                  B, stream, name);
-                if (rc) return rc;
-                std::snprintf(name, sizeof(name), "finish%d_%dx%d", c.layer_idx, res, res);
-                StepScope scope(e, stream, name, 0.0, 4.0 * (double)slab * (p.nsplit + 1));
-                GANCE_HIP_CHECK(gance::launch_splitk_finish(e->ws->slabs, slab, p.nsplit, noise,
-                                                            e->conv_ns[li], noise_b_stride, bias, x_out, B, c.cout,
-                                                            res, res, stream));
+                const gance::FirArgs f = fir_args(e, li, step, cls_stride, unit, x_out, B, s_next);
+                StepScope scope(e, stream, step.second, 0.0, 4.0 * (double)B * c.cout * res * res * (step.p.nsplit + 1));
+                GANCE_HIP_CHECK(gance::launch_fir_epilogue(f, stream));
+                break;
             }
-        } else {
-            const int H = res / 2, W = res / 2;
-            // the next layer's style rides on this layer's activation when that layer takes its input pre-scaled
-            const float* const s_next =
-                (li + 1 < limit && !e->convs[li + 1].up &&
-                 ((conv_form_of(li + 1, true).wino64 && gance::winograd64_input_prescaled(e->convs[li + 1].cout)) || conv_form_of(li + 1, true).wino43))
-                    ? e->ws->styles + e->conv_s_off[li + 1]
-                    : nullptr;
-            const bool input_prescaled = x_prescaled;
-            x_prescaled = false;
-            {
-                gance::UpFirArgs u{};
-                const UpFused fused = up_runs_fused(li, &u);
-                if (fused != UpFused::no) {
-                    const bool split_form = fused == UpFused::split;
-                    const bool geometry16 = !split_form && e->upfir16_w[li] != SIZE_MAX;
-                    const bool pair_form = geometry16 && e->upfir16x_w[li] != SIZE_MAX && input_prescaled;
-                    u.pair_form = pair_form ? 1 : 0;
-                    u.x = x_in;
-                    u.w = e->pool + (split_form ? e->upfirs_w[li] : (pair_form ? e->upfir16x_w[li] : (geometry16 ? e->upfir16_w[li] : e->upfir_w[li])));
-                    u.s = e->ws->styles + e->conv_s_off[li];
-                    u.d = e->ws->demod + e->conv_d_off[li];
-                    u.noise = noise;
-                    u.bias = bias;
-                    u.out = x_out;
-                    u.B = B;
-                    u.Cin = c.cin;
-                    u.Cout = c.cout;
-                    u.H = H;
-                    u.W = W;
-                    u.s_stride = e->ctot;
-                    u.d_stride = e->dtot;
-                    u.noise_strength = e->conv_ns[li];
-                    u.noise_b_stride = noise_b_stride;
-                    u.x_b_stride = x_b_stride;
-                    u.s_next = s_next;
-                    u.input_prescaled = input_prescaled ? 1 : 0;
-                    // ("convTFp": upfir_fused_pre_kernel, the input arrives multiplied by this layer's style)
-                    // (a trailing "/16": the 16-channel, two-blocks-per-CU geometry, upfir16_fused*_kernel; "/16x": its pair form)
-                    // ("/s3": the split-operand form, upfirs_fused*_kernel: bf16 x 3 parts, six product terms, fp32 accumulation)
-                    std::snprintf(name, sizeof(name), input_prescaled ? "convTFp%d_%dx%d_%d->%d%s" : "convTF%d_%dx%d_%d->%d%s", c.layer_idx, res, res, c.cin,
-                                  c.cout, split_form ? "/s3" : (pair_form ? "/16x" : (geometry16 ? "/16" : "")));
-                    {
-                        const double flops = 2.0 * 9 * (double)c.cin * c.cout * H * W * B;
-                        const double bytes = 4.0 * ((double)B * c.cin * H * W + (double)B * c.cout * res * res + 9.0 * c.cin * c.cout);
-                        StepScope scope(e, stream, name, flops, bytes);
-                        GANCE_HIP_CHECK(split_form ? gance::launch_upfir_split(u, stream)
-                                                   : (geometry16 ? gance::launch_upfir16_fused(u, stream) : gance::launch_upfir_fused(u, stream)));
-                    }
-                    x_in = x_out;
-                    x_b_stride = out_b;
-                    e->last_act_layer = li;
-                    e->last_act_c = c.cout;
-                    e->last_act_side = res;
-                    continue;
-                }
-            }
-            const long long tc = (long long)t_plane(H);
-            const long long unit = tc * c.cout;
-            const long long cls_stride = unit * e->t_units[li];
-            // (the scatter form: at 4x4 / 8x8 inputs from upgemm_min_columns() columns up, at 32x32 / 64x64 inputs for calls this small)
-            const bool scatter = e->upgemm_w[li] != SIZE_MAX && B * H * W >= upgemm_min_columns() && B * H * W <= gance::upgemm_max_columns(c.cout, upgemm_buffer_columns());
-            if (scatter) {
-                // ("convTG": pack + GEMM + gather, gemm_forms.hip)
-                std::snprintf(name, sizeof(name), "convTG%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin, c.cout);
-                gance::UpGemmArgs g{};
-                g.x = x_in;
-                g.w = e->pool + e->upgemm_w[li];
-                g.s = e->ws->styles + e->conv_s_off[li];
-                g.d = e->ws->demod + e->conv_d_off[li];
-                g.packed = e->ws->up_packed;
-                g.prod = e->ws->up_prod;
-                g.t = e->ws->tplanes[li];
-                g.x_b_stride = x_b_stride;
-                g.cls_stride = cls_stride;
-                g.unit_stride = unit;
-                g.B = B;
-                g.Cin = c.cin;
-                g.Cout = c.cout;
-                g.H = H;
-                g.W = W;
-                g.s_stride = e->ctot;
-                g.d_stride = e->dtot;
-                g.n_tiles = gance::upgemm_n_tiles(B, H, W);
-                g.bf16_split = (9 * c.cout) % 256 == 0 ? e->gemm_bf16 : 0;
-                const double n = (double)g.n_tiles * 128;
-                StepScope scope(e, stream, name, 2.0 * 9 * c.cin * c.cout * (double)B * H * W,
-                                4.0 * (9.0 * c.cin * c.cout + 2.0 * c.cin * n + 2.0 * 9 * c.cout * n + 4.0 * unit * B));
-                GANCE_HIP_CHECK(gance::launch_upgemm(g, stream));
-            } else {
-                std::snprintf(name, sizeof(name), "convT%d_%dx%d_%d->%d", c.layer_idx, res, res, c.cin,
-                              c.cout);
-                int rc = run_conv(e, c, li, p, x_in, x_b_stride, H, W, e->ws->tplanes[li],
-                                  gance::kEpilogueRaw, W + 8, 1, 4, unit, tc, unit * B, cls_stride, B,
-                                  stream, name);
-                if (rc) return rc;
-            }
-            gance::FirArgs f{};
-            f.t = e->ws->tplanes[li];
-            f.cls_stride = cls_stride;
-            f.unit_stride = unit;
-            f.noise = noise;
-            f.bias = bias;
-            f.out = x_out;
-            f.noise_strength = e->conv_ns[li];
-            f.noise_b_stride = noise_b_stride;
-            f.B = B;
-            f.C = c.cout;
-            f.H = H;
-            f.W = W;
-            f.nsplit = scatter ? 1 : p.nsplit;
-            f.s_next = s_next;
-            f.s_next_stride = e->ctot;
-            std::snprintf(name, sizeof(name), "fir%d_%dx%d", c.layer_idx, res, res);
-            StepScope scope(e, stream, name, 0.0,
-                            4.0 * (double)B * c.cout * res * res * (p.nsplit + 1));
-            GANCE_HIP_CHECK(gance::launch_fir_epilogue(f, stream));
         }
         x_in = x_out;
         x_b_stride = out_b;
@@ -926,38 +658,21 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
         e->last_act_c = c.cout;
         e->last_act_side = res;
 
-        // ToRGB after the 4x4 conv and after every Conv1
-        if (!c.up && !fused_rgb) {
-            int ri = c.res_log2 - 2;
-            const RgbLayerHost& r = e->rgbs[ri];
-            gance::ToRgbArgs t{};
-            t.x = x_in;
-            t.w = e->pool + e->rgb_w[ri];
-            t.s = e->ws->styles + e->rgb_s_off[ri];
-            t.bias = e->pool + e->rgb_bias[ri];
-            t.y_prev = have_y ? e->ws->ybuf[ycur] : nullptr;
-            t.y = e->ws->ybuf[have_y ? 1 - ycur : ycur];
+        if (step.torgb[0] != '\0') {
             const bool last = (c.res_log2 == e->res_log2);
-            t.u8 = last ? d_u8 : nullptr;
-            t.partial = rgb_part ? (rgb_partials == 1 ? t.y : e->ws->rgb_part) : nullptr;  // (one piece: in place)
-            t.partials = rgb_partials;
-            t.skip_y_store = last && res > 128 && d_u8 != nullptr && d_f32 == nullptr && !e->keep_skip_image && limit == num_convs;
-            t.B = B;
-            t.Cin = r.cin;
-            t.R = res;
-            t.s_stride = e->ctot;
-            std::snprintf(name, sizeof(name), "torgb_%dx%d", res, res);
-            // (after a conv launch that did the channel sum: partial image in, bias and skip image added, image and/or bytes out)
+            const bool skip_y_store = step.may_skip_y_store && d_u8 != nullptr && d_f32 == nullptr && !e->keep_skip_image;
+            const gance::ToRgbArgs t = torgb_args(e, ri, step, x_in, have_y ? e->ws->ybuf[ycur] : nullptr, e->ws->ybuf[have_y ? 1 - ycur : ycur],
+                                                  last ? d_u8 : nullptr, skip_y_store, B);
             const double px = (double)B * res * res;
-            StepScope scope(e, stream, name, rgb_part ? 0.0 : 2.0 * 3 * (double)r.cin * px,
-                            rgb_part ? px * (12.0 * rgb_partials + 3.0 + (t.skip_y_store ? 0.0 : 12.0) + (t.u8 != nullptr ? 3.0 : 0.0))
-                                     : 4.0 * px * (r.cin + 3 + 0.75) + 3.0 * px);
+            StepScope scope(e, stream, step.torgb, step.rgb_sum ? 0.0 : 2.0 * 3 * (double)t.Cin * px,
+                            step.rgb_sum ? px * (12.0 * step.rgb_partials + 3.0 + (t.skip_y_store ? 0.0 : 12.0) + (t.u8 != nullptr ? 3.0 : 0.0))
+                                         : 4.0 * px * (t.Cin + 3 + 0.75) + 3.0 * px);
             GANCE_HIP_CHECK(gance::launch_torgb(t, stream));
             if (have_y) ycur = 1 - ycur;
             have_y = true;
         }
     }
-    if (d_f32 != nullptr && limit == num_convs) {
+    if (d_f32 != nullptr && (int)plan.size() == (int)e->convs.size()) {
         const size_t bytes = (size_t)B * 3 * e->cfg.resolution * e->cfg.resolution * sizeof(float);
         GANCE_HIP_CHECK(hipMemcpyAsync(d_f32, e->ws->ybuf[ycur], bytes, hipMemcpyDeviceToDevice, stream));
     }
@@ -1108,16 +823,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     GANCE_HIP_CHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, config->device));
 
     gance_engine* e = new gance_engine();
-    {  // (read per engine, not once per process: a test creates engines with and without it)
-        const char* v = std::getenv("GANCE_TUNE_GEMM_BF16X6");
-        e->gemm_bf16 = v != nullptr && std::atoi(v) != 0 ? 1 : 0;
-        const char* const split = std::getenv("GANCE_TUNE_UPFIR_SPLIT");
-        e->upfir_split = split != nullptr ? std::max(0, std::min(2, std::atoi(split))) : 1;
-        const char* const split_res = std::getenv("GANCE_TUNE_UPFIR_SPLIT_MAXRES");
-        if (split_res != nullptr) e->upfir_split_max_res = std::atoi(split_res);
-        const char* const split_narrow = std::getenv("GANCE_TUNE_UPFIR_SPLIT_NARROW");
-        e->upfir_split_narrow = split_narrow != nullptr && std::atoi(split_narrow) == 0 ? 0 : 1;
-    }
+    e->tune = engine_tuning();  // (the per-engine knobs as they stand now: a test creates engines with and without them)
     e->cfg = *config;
     e->num_cus = num_cus > 0 ? num_cus : 256;
     e->res_log2 = res_log2;
@@ -1180,22 +886,59 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     e->w2_off = reserve(w2_total);
     const float mod_coef = (float)(1.0 / std::sqrt((double)kDlatent));
     std::vector<gance::DemodLayer> demod_layers(nconv);
-    e->conv_w.resize(nconv);
+    // every form's weight image beyond the direct one, in the pool's order (enum WeightImage): its size and how it is arranged
+    // from the scaled HWIO weights (split: LayerCaps::gemm_split, three bf16 parts per value = 1.5 x the floats)
+    struct WeightImageKind {
+        size_t (*floats)(int cin, int cout, int split);
+        void (*arrange)(const float* scaled, int cin, int cout, int split, float* out);
+    };
+    static const WeightImageKind kinds[kNumWeightImages] = {
+        // U = G w G^T of the scaled weights, in the Winograd kernel's LDS image [m tile][chunk][16][4][32]
+        {[](int ci, int co, int) { return gance::winograd_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::winograd_transform_weights(w, ci, co, out); }},
+        {[](int ci, int co, int) { return gance::winograd64_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::winograd64_transform_weights(w, ci, co, out); }},
+        {[](int ci, int co, int) { return gance::winograd43_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::winograd43_transform_weights(w, ci, co, out); }},
+        {[](int ci, int co, int) { return gance::upfir_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::upfir_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {[](int ci, int co, int) { return gance::upfir16_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::upfir16_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {[](int ci, int co, int split) { return gance::winogemm_weight_floats(ci, co) * (split ? 3 : 2) / 2; },
+         [](const float* w, int ci, int co, int split, float* out) {
+             if (split) gance::winogemm_arrange_weights_split(w, ci, co, out);
+             else gance::winogemm_arrange_weights(w, ci, co, out);
+         }},
+        {[](int ci, int co, int split) { return gance::upgemm_weight_floats(ci, co) * (split ? 3 : 2) / 2; },
+         [](const float* w, int ci, int co, int split, float* out) {
+             if (split) gance::upgemm_arrange_weights_split(w, ci, co, kUpTapWeight, out);
+             else gance::upgemm_arrange_weights(w, ci, co, kUpTapWeight, out);
+         }},
+        {[](int ci, int co, int) { return gance::upfirs_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::upfirs_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {[](int ci, int co, int) { return gance::upfir16x_weight_floats(ci, co); },
+         [](const float* w, int ci, int co, int, float* out) { gance::upfir16x_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+    };
+    e->caps.resize(nconv);
     e->conv_bias.resize(nconv);
     e->conv_noise.resize(nconv);
     e->conv_ns.resize(nconv);
     size_t w2_cursor = 0;
+    std::vector<float> scaled;
     for (int i = 0; i < nconv; ++i) {
         const ConvLayerHost& c = e->convs[i];
         const size_t wn = (size_t)9 * c.cin * c.cout;
         const float coef = (float)(1.0 / std::sqrt(9.0 * c.cin));
-        e->conv_w[i] = reserve(wn);
+        scaled.resize(wn);  // the layer's scaled HWIO weights: what every form's image is arranged from
+        for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
+        LayerCaps& caps = e->caps[i] = layer_caps(e->convs, i, e->cfg.flags, e->tune);
+        caps.direct_w = reserve(wn);
         {
-            // scaled HWIO weights, re-laid-out as the kernel's LDS image:
+            // the direct form's LDS image:
             // [m tile][K chunk][tap slot][KC][BM], slot t of an up layer = filter tap kUpTapWeight[t]
-            const int BM = layer_bm(c.cout), KC = layer_kc(c.cout, c.up);
+            const int BM = layer_bm(c.cout), KC = layer_kc(c.cout, c.up, e->tune);
             const int m_tiles = c.cout / BM, chunks = c.cin / KC;
-            float* w = &pool[e->conv_w[i]];
+            float* w = &pool[caps.direct_w];
             float* w2 = &pool[e->w2_off + w2_cursor];
             for (int mt = 0; mt < m_tiles; ++mt)
                 for (int ch = 0; ch < chunks; ++ch)
@@ -1204,87 +947,16 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
                         for (int kc = 0; kc < KC; ++kc)
                             for (int m = 0; m < BM; ++m) {
                                 const int ci = ch * KC + kc, co = mt * BM + m;
-                                const float v = src[((size_t)tap * c.cin + ci) * c.cout + co] * coef;
+                                const float v = scaled[((size_t)tap * c.cin + ci) * c.cout + co];
                                 w[((((size_t)mt * chunks + ch) * 9 + t) * KC + kc) * BM + m] = v;
                                 w2[(size_t)ci * c.cout + co] += v * v;
                             }
                     }
         }
-        e->wino_w.push_back(SIZE_MAX);
-        if (!c.up && gance::winograd_supported(c.cin, c.cout, 1 << c.res_log2, 1 << c.res_log2)) {
-            // U = G w G^T of the scaled weights, in the Winograd kernel's LDS image [m tile][chunk][16][4][32]
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->wino_w[i] = reserve(gance::winograd_weight_floats(c.cin, c.cout));
-            gance::winograd_transform_weights(scaled.data(), c.cin, c.cout, &pool[e->wino_w[i]]);
-        }
-        e->wino64_w.push_back(SIZE_MAX);
-        if (!c.up && gance::winograd64_supported(c.cin, c.cout, 1 << c.res_log2, 1 << c.res_log2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->wino64_w[i] = reserve(gance::winograd64_weight_floats(c.cin, c.cout));
-            gance::winograd64_transform_weights(scaled.data(), c.cin, c.cout, &pool[e->wino64_w[i]]);
-        }
-        e->wino43_w.push_back(SIZE_MAX);
-        if (!c.up && i > 0 && e->convs[i - 1].up && (1 << c.res_log2) >= 32 && (1 << c.res_log2) <= wino43_max_res(e->cfg.flags) &&
-            gance::winograd43_supported(c.cin, c.cout, 1 << c.res_log2, 1 << c.res_log2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->wino43_w[i] = reserve(gance::winograd43_weight_floats(c.cin, c.cout));
-            gance::winograd43_transform_weights(scaled.data(), c.cin, c.cout, &pool[e->wino43_w[i]]);
-        }
-        e->upfir_w.push_back(SIZE_MAX);
-        // (the 32-channel kernel's image only where the 16-channel kernel will not take the layer: GANCE_TUNE_UPFIR16=0)
-        if (c.up && gance::upfir_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2) &&
-            !(upfir16_mode() != 0 && gance::upfir16_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2))) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->upfir_w[i] = reserve(gance::upfir_weight_floats(c.cin, c.cout));
-            gance::upfir_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upfir_w[i]]);
-        }
-        e->upfir16_w.push_back(SIZE_MAX);
-        if (c.up && upfir16_mode() != 0 && gance::upfir16_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->upfir16_w[i] = reserve(gance::upfir16_weight_floats(c.cin, c.cout));
-            gance::upfir16_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upfir16_w[i]]);
-        }
-        e->winogemm_w.push_back(SIZE_MAX);
-        if (!c.up && i > 0 && winogemm_min_columns() > 0 && wino43_max_res(e->cfg.flags) >= 16 &&
-            gance::winogemm_supported(c.cin, c.cout, 1 << c.res_log2, 1 << c.res_log2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            // (the experiment's 256-row block tiles need Cout to be a multiple of 256: a 128-channel layer of a reduced network keeps the fp32 GEMM)
-            const int split_mode = c.cout % 256 == 0 ? e->gemm_bf16 : 0;
-            e->winogemm_w[i] = reserve(gance::winogemm_weight_floats(c.cin, c.cout) * (split_mode ? 3 : 2) / 2);
-            if (split_mode) gance::winogemm_arrange_weights_split(scaled.data(), c.cin, c.cout, &pool[e->winogemm_w[i]]);
-            else gance::winogemm_arrange_weights(scaled.data(), c.cin, c.cout, &pool[e->winogemm_w[i]]);
-        }
-        e->upgemm_w.push_back(SIZE_MAX);
-        if (c.up && upgemm_min_columns() > 0 && gance::upgemm_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            // (the experiment's 256-row block tiles need 9 Cout to be a multiple of 256: the 128-channel layer keeps the fp32 GEMM)
-            const int split_mode = (9 * c.cout) % 256 == 0 ? e->gemm_bf16 : 0;
-            e->upgemm_w[i] = reserve(gance::upgemm_weight_floats(c.cin, c.cout) * (split_mode ? 3 : 2) / 2);
-            if (split_mode) gance::upgemm_arrange_weights_split(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upgemm_w[i]]);
-            else gance::upgemm_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upgemm_w[i]]);
-        }
-        e->upfirs_w.push_back(SIZE_MAX);
-        if (c.up && e->upfir_split != 0 && upfir16_mode() != 0 &&
-            (gance::upfirs_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2) ||
-             (e->upfir_split_narrow != 0 && gance::upfirs_narrow_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)))) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->upfirs_w[i] = reserve(gance::upfirs_weight_floats(c.cin, c.cout));
-            gance::upfirs_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upfirs_w[i]]);
-        }
-        e->upfir16x_w.push_back(SIZE_MAX);
-        if (c.up && upfir16_mode() != 0 && upfir16x_mode() != 0 && gance::upfir16x_supported(c.cin, c.cout, (1 << c.res_log2) / 2, (1 << c.res_log2) / 2)) {
-            std::vector<float> scaled(wn);
-            for (size_t j = 0; j < wn; ++j) scaled[j] = src[j] * coef;
-            e->upfir16x_w[i] = reserve(gance::upfir16x_weight_floats(c.cin, c.cout));
-            gance::upfir16x_arrange_weights(scaled.data(), c.cin, c.cout, kUpTapWeight, &pool[e->upfir16x_w[i]]);
+        for (int f = 0; f < kNumWeightImages; ++f) {
+            if (!caps.has[f]) continue;
+            caps.w[f] = reserve(kinds[f].floats(c.cin, c.cout, caps.gemm_split));
+            kinds[f].arrange(scaled.data(), c.cin, c.cout, caps.gemm_split, &pool[caps.w[f]]);
         }
         src += wn;
         demod_layers[i] = {(long long)w2_cursor, e->conv_s_off[i], e->conv_d_off[i], c.cin, c.cout};
@@ -1351,7 +1023,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     for (int i = 0; i < nconv; ++i) {
         const ConvLayerHost& c = e->convs[i];
         for (int B = 1; B <= Bmax; ++B) {
-            const LayerPlan p = plan_layer(c, B);
+            const LayerPlan p = plan_layer(c, B, e->tune);
             if (c.up) e->t_units[i] = std::max(e->t_units[i], p.nsplit * B);
             else if (p.nsplit > 1)
                 slab_max = std::max(slab_max, (size_t)p.nsplit * B * c.cout << (2 * c.res_log2));
@@ -1364,7 +1036,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         const int H = (1 << c.res_log2) / 2;
         if (c.up && gance::upgemm_supported(c.cin, c.cout, H, H)) {
             // (x 3/2: room for the three bf16 parts of the experiment's operand images, whatever this engine's knobs say)
-            const int samples = std::max(1, std::min(Bmax, gance::upgemm_max_columns(c.cout, upgemm_buffer_columns()) / (H * H)));
+            const int samples = std::max(1, std::min(Bmax, gance::upgemm_max_columns(c.cout, e->tune.upgemm_buffer_columns) / (H * H)));
             e->up_packed_floats = std::max(e->up_packed_floats, gance::upgemm_packed_floats(samples, c.cin, H, H) * 3 / 2);
             e->up_prod_floats = std::max(e->up_prod_floats, gance::upgemm_prod_floats(samples, c.cout, H, H));
         }
@@ -1496,8 +1168,7 @@ static int host_call(gance_engine* e, const float* h_in, size_t in_floats, int b
         return is_z ? synthesize_from_z(e, d_in, batch, psi, ws->u8buf, nullptr, hs)
                     : synthesize_from_dlat(e, d_in, batch, ws->u8buf, nullptr, hs);
     };
-    static const bool graphs_enabled = [] { const char* v = std::getenv("GANCE_TUNE_GRAPH"); return !(v && std::atoi(v) == 0); }();
-    const bool plain = !graphs_enabled || (e->cfg.flags & GANCE_FLAG_PROFILE_STEPS) || e->debug_stop_after > 0;
+    const bool plain = !e->tune.graph || (e->cfg.flags & GANCE_FLAG_PROFILE_STEPS) || e->debug_stop_after > 0;
     int rc = GANCE_OK;
     if (plain) {
         if (e->profile_only.empty() || e->steps_used >= 4096) e->steps_used = 0;
@@ -1650,6 +1321,28 @@ int gance_engine_debug_read_noise(gance_engine* e, int32_t conv_layer, int32_t s
     const float* src = layer_noise(e, conv_layer, &b_stride);
     if (src == nullptr) src = e->pool + e->conv_noise[conv_layer];  // (strength zero: the stored buffer, which no launch reads)
     GANCE_HIP_CHECK(hipMemcpy(h_out, src + (size_t)sample * b_stride, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GANCE_OK;
+}
+
+// The plan of a full call without a device: capabilities from the config alone (layer_caps needs no weights), the same
+// plan_call and the same names (name_step) as synthesize_from_dlat.
+int gance_engine_describe_plan(const gance_engine_config* config, int32_t num_cus, int32_t batch, char* out, uint64_t capacity) {
+    if (config == nullptr || out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_engine_describe_plan");
+    const int res_log2 = ilog2_exact(config->resolution);
+    if (res_log2 < 3 || res_log2 > 10 || config->max_batch < 1 || config->max_batch > 64 || batch < 1 || batch > config->max_batch || num_cus < 1)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_describe_plan: resolution, max_batch, batch or num_cus out of range");
+    std::vector<ConvLayerHost> convs;
+    std::vector<RgbLayerHost> rgbs;
+    build_spec(res_log2, &convs, &rgbs);
+    const Tuning tune = engine_tuning();
+    std::vector<LayerCaps> caps;
+    for (int i = 0; i < (int)convs.size(); ++i) caps.push_back(layer_caps(convs, i, config->flags, tune));
+    std::string text = "styles\ndemod\n";
+    for (const LayerStep& step : plan_call(convs, caps, tune, config->flags, num_cus, batch, 0))
+        for (const char* name : {step.name, step.second, step.torgb})
+            if (name[0] != '\0') text += std::string(name) + "\n";
+    if (text.size() + 1 > capacity) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_describe_plan: capacity too small");
+    std::memcpy(out, text.c_str(), text.size() + 1);
     return GANCE_OK;
 }
 

@@ -129,6 +129,9 @@ SIGNATURES = {
             ctypes.POINTER(ctypes.c_double),
         ],
     ),
+    "gance_engine_describe_plan": (
+        ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_uint64]
+    ),
     "gance_engine_debug_stop_after": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "gance_engine_debug_read_activation": (
         ctypes.c_int,
@@ -232,6 +235,10 @@ SIGNATURES = {
     ),
 }
 
+# entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
+# libgance_hip_prev.so) may lack them, and only a call of the missing entry fails there
+ADDED_WITHIN_ABI = {"gance_engine_describe_plan"}
+
 _LIB: Optional[ctypes.CDLL] = None
 
 
@@ -251,6 +258,8 @@ def load_library() -> ctypes.CDLL:
         )
     lib = ctypes.CDLL(str(LIBRARY_PATH))
     for name, (restype, argtypes) in SIGNATURES.items():
+        if name in ADDED_WITHIN_ABI and not hasattr(lib, name):
+            continue
         function = getattr(lib, name)  # AttributeError if the .so does not export it
         function.restype = restype
         function.argtypes = argtypes

@@ -138,6 +138,11 @@ int gance_engine_set_profiling(gance_engine* engine, int32_t flags, const char* 
 int32_t gance_engine_step_count(const gance_engine* engine);
 int gance_engine_step_info(gance_engine* engine, int32_t index, char* name64, float* ms,
                            double* flops, double* bytes);
+/* Host only, no device and no weights: the launch names, one per line and in launch order, of a gance_synthesize_w call of
+ * `batch` frames on an engine created from `config` (and the GANCE_TUNE_* environment of this process) on a device of `num_cus`
+ * compute units -- the very strings gance_engine_step_info reports for such a call. `out` receives them NUL-terminated;
+ * GANCE_ERR_INVALID_ARGUMENT for a bad configuration or batch, or a `capacity` that is too small. */
+int gance_engine_describe_plan(const gance_engine_config* config, int32_t num_cus, int32_t batch, char* out, uint64_t capacity);
 /*
  * randomize_noise of the generator. The reference's vector path (create_image_vector, network_functions.py:152-157)
  * leaves `randomize_noise` at the upstream default True: every call draws fresh N(0, 1) noise, one plane per layer AND

@@ -442,8 +442,8 @@ def test_config_f_1024_at_the_batch_sizes_the_product_stream_issues(library) -> 
     """
     The form a layer runs in is a function of (resolution, batch): Winograd F(4x4,3x3) / F(2x2,3x3) / direct by the tile
     count of the launch, fused or two-pass up layers by `upfir_plan`, split-K factors, the last layer fused with its ToRGB or
-    not (engine.hip: conv_form_of, up_runs_fused, plan_layer). The product stream issues every batch size in [1, 64] at
-    1024^2 (three networks: calls of ~21 frames; ragged window ends; a tail chunk of 8), so the frames are checked at
+    not (engine_plan.h: plan_call, which asks conv_form_of, up_runs_fused and plan_layer once per layer). The product stream
+    issues every batch size in [1, 64] at 1024^2 (three networks: calls of ~21 frames; ragged window ends; a tail chunk of 8), so the frames are checked at
     such sizes, every term on: first and last frame of each batch against the same z alone (the one-frame call is
     oracle-checked above), and for one of the sizes the last frame against the fp64 oracle as well (the 64-frame batch
     is oracle-checked by test_bench_configuration_batch_64...). The launch names of
