@@ -18,7 +18,7 @@
 // Geometry. Block = 8 waves = 2 channel tiles of 16 x 4 tile rows; a wave owns 16 channels x one row of sixteen 4x4 output
 // tiles (4 x 64 pixels): the block 32 channels x 16 x 64 pixels. The two waves of a SIMD take the two channel tiles of the
 // SAME tile row (tile row = SIMD id, channel tile = the wave's ticket on that SIMD): they run the two halves of the pipeline,
-// and the ToRGB sums of the first reach the second through LDS, so a block writes ONE partial ToRGB image. Lane (n = lane % 16, g = lane / 16) transforms the 6x6
+// and their ToRGB sums meet in LDS, so a block writes ONE partial ToRGB image. Lane (n = lane % 16, g = lane / 16) transforms the 6x6
 // window of tile n for input channel 4 ks + g; as A operand it holds output channel n of its channel tile for the same
 // input channel. The input arrives ALREADY multiplied by this layer's style (ConvArgs::x contract, as for the
 // 32-channel geometry of winograd64_conv.hip: the producing up layer folds s[b][ci] into its leaky ReLU; V is linear in d).
@@ -31,7 +31,10 @@
 //
 // Epilogue: output transform A^T M A in registers (the 36 positions of a (channel, tile) pair live in ONE lane),
 // demodulation, noise, bias, leaky ReLU, optional scale by the next layer's style, 16-byte stores (256 contiguous
-// bytes per 16 lanes).
+// bytes per 16 lanes). The two epilogues of a tile (one per channel tile = per wave of a SIMD) run in the SAME interval between two
+// barriers, the first interval of the block's next tile, beside that interval's multiplies: the wave that finishes a tile's K loop
+// first defers its epilogue by one interval (see the stream loop). One after the other, each with its SIMD partner parked at
+// the barrier, they cost 7.5 us per tile, which is 1.9 ms of the 1024^2 layer's 5.4.
 
 #include <hip/hip_runtime.h>
 
@@ -101,8 +104,8 @@ constexpr int kNBUF = GANCE_W43_NBUF;          // ring slots: chunk G + 2 is iss
 // noise [16][64] | (RGB) A operands of the ToRGB product [2 channel tiles][4 steps][64 lanes]
 constexpr int kConstD = 0, kConstB = 64, kConstS = 128, kConstNoise = 192, kConstRgb = kConstNoise + 1024, kConstFloats = kConstRgb + 512;
 constexpr int kStoresPerEpilogue = 16, kRgbStores = 12;
-// (RGB) hand-over of a wave's ToRGB sums to the wave that holds the OTHER sixteen channels of the same pixels:
-// [tile row][output row x colour = 12][16 lanes] float4
+// (RGB) the ToRGB sums of a wave's sixteen channels, left in LDS for the add with the sums of the wave that holds the OTHER sixteen
+// channels of the same pixels: [tile row][output row x colour = 12][16 lanes] float4, one such buffer per role
 constexpr int kRgbXchgFloats = 4 * 12 * 16 * 4;
 
 // B^T of F(4,3), points 0, +-1, +-2 (Lavin & Gray): 12 vector instructions, on one window line or on two at once
@@ -174,7 +177,7 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
     // Work of this wave: tile row = the SIMD it runs on, channel tile = its ticket there (two waves of 256 registers fill a
     // SIMD, so each SIMD holds exactly two of the block's eight). The two waves of a SIMD then hold the two channel tiles of
     // the SAME pixels and run the two halves of the pipeline (see the stream loop): the ticket is the wave's role as well, and
-    // the hand-over of the ToRGB sums between them (epilogue) needs no atomic: role 0 is always a barrier ahead of role 1.
+    // their ToRGB sums are added without an atomic: each role leaves its own in LDS, role 0 adds them a barrier later (finish_rgb).
     // Which waves share a SIMD is the dispatcher's choice, so the wave asks the hardware (HW_ID.simd_id).
     __shared__ int simd_tickets[4];
     if (tid < 4) simd_tickets[tid] = 0;
@@ -320,7 +323,8 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(st_x_rsrc, (lds_ptr_t)(base + kWFloats + (piece - kWPieces) * 256), 16, piece_voff[r], cur_x, 0, 0);
     };
 
-    float* const rgb_xchg = const0 + 2 * kConstFloats;
+    float* const rgb_xchg = const0 + 2 * kConstFloats;  // [role][kRgbXchgFloats]
+    size_t rgb_off = 0;  // (RGB) where the partial image of the tile whose sums lie in rgb_xchg begins (scalar; set by the epilogue)
 
     f32x4 acc[36];  // (every tile's first k-step overwrites them: multiply(first))
 
@@ -493,28 +497,40 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
         if constexpr (RGB) {
             // Partial image of the block's 32 channels: [Cout / 32][B][3][OH][OW]. Lanes 0 .. 15 of a wave hold (R, G, B, 0)
             // of their tile's pixels for the wave's 16 channels; the other wave of the SIMD holds the other 16 channels of the
-            // same pixels. The role-0 wave (channel tile 0) leaves its sums in LDS: its epilogue ends an interval; the role-1
-            // wave (channel tile 1) runs its epilogue of the same tile behind the next barrier, adds them to its own and stores.
-            f32x4* const xchg = reinterpret_cast<f32x4*>(rgb_xchg) + (pg * 12) * 16 + n16;
-            if (cot == 0) {
-                if (g == 0) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-#pragma unroll
-                        for (int oy = 0; oy < 4; ++oy) xchg[(c * 4 + oy) * 16] = f32x4{rgbacc[oy][0][c], rgbacc[oy][1][c], rgbacc[oy][2][c], rgbacc[oy][3][c]};
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (in LDS before this wave's next barrier)
-            } else if (g == 0) {
-                float* const y_base = p.rgb_y + (((size_t)t.m_tile * p.B + t.b0) * 3) * p.OH * p.OW + (size_t)oy0 * p.OW + ox0;
+            // same pixels. Both epilogues of a tile run between the same two barriers, so neither wave can read the other's sums
+            // here: each leaves its own in its role's buffer, and the role-0 wave adds and stores them behind the next barrier
+            // (finish_rgb). The buffers are written again at the next tile boundary, n >= 4 barriers later (winograd43_supported):
+            // one buffer per role is enough, no second set by tile parity.
+            f32x4* const xchg = reinterpret_cast<f32x4*>(rgb_xchg + cot * kRgbXchgFloats) + (pg * 12) * 16 + n16;
+            if (g == 0) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
 #pragma unroll
-                    for (int oy = 0; oy < 4; ++oy)
-                        *reinterpret_cast<f32x4*>(y_base + ((size_t)c * p.OH + oy) * p.OW) =
-                            f32x4{rgbacc[oy][0][c], rgbacc[oy][1][c], rgbacc[oy][2][c], rgbacc[oy][3][c]} + xchg[(c * 4 + oy) * 16];
+                    for (int oy = 0; oy < 4; ++oy) xchg[(c * 4 + oy) * 16] = f32x4{rgbacc[oy][0][c], rgbacc[oy][1][c], rgbacc[oy][2][c], rgbacc[oy][3][c]};
             }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (in LDS before this wave's next barrier)
+            rgb_off = (((size_t)t.m_tile * p.B + t.b0) * 3) * p.OH * p.OW + (size_t)t.y0 * p.OW + t.x0;
         }
         lane_setup();
+    };
+    // (RGB, role 0, behind the barrier that follows a tile's two epilogues) the partial image of that tile: the sums of channel
+    // tile 1 + those of channel tile 0, in this order (what the role-1 wave added in its registers before the epilogues shared an
+    // interval: the images stay bit for bit). Twelve 16-byte stores from the lanes g == 0; one colour at a time (24 live registers).
+    auto finish_rgb = [&]() {
+        const int lane = fresh_lane();
+        const int n16 = lane & 15;
+        if (lane < 16) {
+            const f32x4* const x0 = reinterpret_cast<const f32x4*>(rgb_xchg) + (pg * 12) * 16 + n16;
+            const f32x4* const x1 = x0 + kRgbXchgFloats / 4;
+            float* const y_base = p.rgb_y + rgb_off + (size_t)(4 * (pg * kTR + n16 / kTC)) * p.OW + 4 * (n16 % kTC);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int oy = 0; oy < 4; ++oy)
+                    *reinterpret_cast<f32x4*>(y_base + ((size_t)c * p.OH + oy) * p.OW) = x1[(c * 4 + oy) * 16] + x0[(c * 4 + oy) * 16];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
     };
 
     // ---- ring prologue: the first two chunks of the stream, all pieces at once ----
@@ -530,22 +546,46 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
     // The two waves of a SIMD run half a k-step apart: in the interval between two barriers the role-0 wave loads and
     // transforms chunk G and then multiplies it, the role-1 wave first multiplies chunk G - 1 out of its registers and then
     // loads and transforms chunk G. While one of them waits for LDS or issues vector instructions the other keeps the
-    // matrix pipe busy. A tile's epilogue runs right behind its last multiply -- for a role-1 wave that is in the first
-    // interval of the NEXT tile -- while the ring keeps fetching: the stream never drains between tiles.
+    // matrix pipe busy.
+    // Tile boundaries. BOTH epilogues of a tile run in the first interval of the NEXT tile (interval B), while the ring keeps
+    // fetching: the role-1 wave multiplies the tile's last chunk there, which it has in registers, and runs its epilogue behind
+    // it; the role-0 wave, whose last multiply ended the interval before, has DEFERRED its epilogue to the top of interval B, in
+    // front of the next tile's first load + transform + multiply (its accumulators are dead until that multiply's C = 0, V / A
+    // until the load). So the two epilogues run beside each other and beside a multiply, not one after the other with the partner
+    // parked at the barrier. The block's last tile has no interval B: both waves run its epilogue behind the stream's last
+    // barrier, again side by side. What this order relies on:
+    //  * the constants of tile t (set t & 1) are overwritten by those of tile t + 2, which are issued with that tile's first
+    //    chunk in interval n - 2 of tile t + 1; both epilogues of tile t end in interval 0 of tile t + 1: n - 2 >= 2 > 0
+    //    (winograd43_supported demands n >= 4);
+    //  * (RGB) the sums both waves leave in rgb_xchg in interval B are added and stored by the role-0 wave at the top of
+    //    interval B + 1 (finish_rgb), or behind one trailing barrier that both roles execute for the block's last tile.
     // Shape of the loops: tiles outside, their chunks inside, the epilogue UNCONDITIONALLY behind the inner loop, one nest per
     // role: accumulators that flow through a conditional (an epilogue under `if` inside one loop) cost 244 spilled
     // registers here; do-while because the guard path of a `for` (all accumulators zero) meets the real path in front of the
-    // epilogue and costs accumulator copies.
+    // epilogue and costs accumulator copies. For the same reason the role-0 nest is rotated by one k-step (the first tile's first
+    // k-step is peeled): the next tile's first multiply follows the epilogue unconditionally -- behind the block's last tile it
+    // multiplies stale operands into dead accumulators, 36 MFMAs per block -- and only the barrier and the load around it are
+    // conditional, as in the role-1 nest.
     int slot = 0, G = 0;
-    // opens interval G: chunk G must have landed; chunk G + 1 (five pieces) may stay in flight, and so may the stores of an
-    // epilogue this wave ran in the previous interval (vmcnt counts in issue order: they are younger than chunk G's pieces)
-    auto open_interval = [&](bool stores_behind, bool rgb_stores = false) {
+    // Opens interval G: chunk G must have landed. vmcnt counts in issue order, so the wait may leave in flight whatever this
+    // wave issued BEHIND chunk G's pieces: always the five pieces of chunk G + 1, and `stores` stores of an epilogue:
+    //  * kStoresPerEpilogue at the open of interval B + 1, both roles, in the launches that store activations (p.out: every
+    //    layer but the 1024^2 one, which only feeds ToRGB and issues none -- there the count is the plain five). The epilogue's
+    //    stores go out in interval B; role 0: [chunk B + 1: interval B - 1] < stores < [chunk B + 2: this multiply];
+    //    role 1: [chunk B + 1] < [chunk B + 2: the multiply in front of the epilogue] < stores. Either way 16 + 5 are younger
+    //    than chunk B + 1;
+    //  * kRgbStores at the open of interval B + 2, role 0, RGB: finish_rgb stores at the top of interval B + 1,
+    //    [chunk B + 2: interval B] < 12 stores < [chunk B + 3: interval B + 1's multiply]; the activation stores of interval B
+    //    are older than chunk B + 2 there and are waited for (issued more than an interval earlier);
+    //  * 0 everywhere else (role 1 at B + 2 waits for its activation stores of interval B, which are younger than chunk B + 2:
+    //    stricter than needed, as it has always been, and more than an interval old).
+    auto open_interval = [&](int stores) {
         if (G + 1 >= total)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (stores_behind && rgb_stores)  // (only the role-1 wave stores the partial ToRGB image)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPiecesPerWave + kStoresPerEpilogue + kRgbStores) : "memory");
-        else if (stores_behind)
+        else if (stores == kStoresPerEpilogue)
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPiecesPerWave + kStoresPerEpilogue) : "memory");
+        else if (stores == kRgbStores)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPiecesPerWave + kRgbStores) : "memory");
         else
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPiecesPerWave) : "memory");
         if (!(GANCE_W43_ABLATE & 16)) __builtin_amdgcn_s_barrier();
@@ -558,27 +598,55 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
         slot = slot == kNBUF - 1 ? 0 : slot + 1;
         ++G;
     };
+    const int act_stores = p.out != nullptr ? kStoresPerEpilogue : 0;  // (wave-uniform)
     if (role == 0) {
+        lane_setup();  // (again, per nest: per-lane values shared by the two nests are live to the common tail and cost a spilled register)
+        open_interval(0);  // interval 0 of the block's first tile
+        load_transform(slot);
+        __builtin_amdgcn_sched_barrier(0);
+        multiply(std::true_type{});
+        close_interval();
         int tile = 0;
+        // what a tile boundary leaves to the two intervals behind it: the stores their opens may leave in flight (carried as state,
+        // not derived from q: hipcc then peels those two trips of the inner loop, and the peeled copies spill accumulators)
+        int stores = 0, stores_next = 0;
         do {
-            open_interval(tile > 0);
-            load_transform(slot);
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(std::true_type{});
-            close_interval();
             int q = 1;
-            do {
-                open_interval(false);
+            do {  // intervals 1 .. n - 1 of the tile
+                open_interval(stores);
+                if constexpr (RGB) {
+                    if (stores_next != 0) finish_rgb();  // (interval B + 1, in front of this interval's five pieces)
+                }
+                stores = stores_next;
+                stores_next = 0;
+                asm volatile("" : "+s"(stores), "+s"(stores_next));  // (opaque: values that settle after two trips make hipcc peel two trips)
                 load_transform(slot);
                 __builtin_amdgcn_sched_barrier(0);
                 multiply(std::false_type{});
                 close_interval();
             } while (++q < n);
+            // interval 0 of the next tile, if there is one: this tile's epilogue first
+            const bool more = tile + 1 < my_tiles;
+            if (more)
+                open_interval(0);
+            else
+                cur_valid = false;
             epilogue(tile);
+            stores = act_stores;
+            stores_next = RGB ? kRgbStores : 0;
+            if (more) {
+                load_transform(slot);
+            } else {  // (operands of a multiply nobody reads: left undefined, so that the old ones are not kept across the epilogue)
+#pragma unroll
+                for (int k = 0; k < 36; ++k) asm volatile("" : "=v"(V[k]), "=v"(A[k]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            multiply(std::true_type{});
+            if (more) close_interval();
         } while (++tile < my_tiles);
-        if constexpr (RGB) __builtin_amdgcn_s_barrier();  // the block's last ToRGB sums are in LDS (the role-1 waves wait for this in front of their last epilogue)
     } else {
-        open_interval(false);  // interval 0: nothing to multiply yet; this interval's DMA pieces go out in one burst
+        lane_setup();
+        open_interval(0);  // interval 0: nothing to multiply yet; this interval's DMA pieces go out in one burst
         if (cur_valid) {
 #pragma unroll
             for (int r = 0; r < kPiecesPerWave; ++r) stage_piece(r);
@@ -587,14 +655,14 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
         close_interval();
         int tile = 0;
         do {
-            open_interval(tile > 0, RGB);
+            open_interval(tile > 0 ? act_stores : 0);
             multiply(std::true_type{});  // chunk 0 of the tile
             __builtin_amdgcn_sched_barrier(0);
             load_transform(slot);
             close_interval();
             int q = 2;
             do {
-                open_interval(false);
+                open_interval(0);
                 multiply(std::false_type{});
                 __builtin_amdgcn_sched_barrier(0);
                 load_transform(slot);
@@ -603,12 +671,10 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
             // the tile's last chunk: multiplied in the first interval of the next tile (if there is one), then the epilogue,
             // then that interval's own load + transform
             const bool more = tile + 1 < my_tiles;
-            if (more) {
-                open_interval(false);
-            } else {
+            if (more)
+                open_interval(0);
+            else
                 cur_valid = false;
-                if constexpr (RGB) __builtin_amdgcn_s_barrier();
-            }
             multiply(std::false_type{});
             __builtin_amdgcn_sched_barrier(0);
             epilogue(tile);
@@ -617,6 +683,11 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
                 close_interval();
             }
         } while (++tile < my_tiles);
+    }
+    if constexpr (RGB) {  // the sums of the block's last tile: in LDS, from both roles, behind one more barrier
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (role == 0) finish_rgb();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing of the ring may still be landing when the block's LDS is given back
 }
@@ -628,7 +699,8 @@ __global__ __launch_bounds__(512, 1) void winograd43_w32_kernel(const ConvArgs p
 __global__ __launch_bounds__(512, 1) void winograd43_w32_rgb_kernel(const ConvArgs p) { winograd43_body<true, 32>(p); }
 
 bool winograd43_supported(int cin, int cout, int H, int W) {
-    // (>= 4 chunks per tile: two constant sets). Pixel tiles of 16 x 64, or 32 x 32 on the 32-pixel-wide layer.
+    // (>= 4 chunks per tile: a tile's constant set and the ToRGB buffers are written again n - 2 / n intervals behind the interval
+    // that holds the previous tile's two epilogues -- see the stream loop). Pixel tiles of 16 x 64, or 32 x 32 on the 32-pixel-wide layer.
     return cin % kKC == 0 && cin / kKC >= 4 && cout % kBM == 0 && ((W % 64 == 0 && H % 16 == 0) || (W == 32 && H % 32 == 0));
 }
 
@@ -668,7 +740,10 @@ hipError_t launch_winograd43_conv(const ConvArgs& args, hipStream_t stream) {
     const bool narrow = args.W % 64 != 0;  // the 32 x 32 pixel geometry
     void (*const kernel)(const ConvArgs) = narrow ? (rgb ? winograd43_w32_rgb_kernel : winograd43_w32_kernel) : (rgb ? winograd43_rgb_kernel : winograd43_kernel);
     const int tw = narrow ? 32 : 64, th = 1024 / tw;
-    const size_t lds_bytes = sizeof(float) * ((size_t)kNBUF * (narrow ? Geo43<32>::kSlot : Geo43<64>::kSlot) + 2 * kConstFloats + (rgb ? kRgbXchgFloats : 0));
+    const size_t lds_bytes = sizeof(float) * ((size_t)kNBUF * (narrow ? Geo43<32>::kSlot : Geo43<64>::kSlot) + 2 * kConstFloats + (rgb ? 2 * kRgbXchgFloats : 0));
+    // (154.5 KB / 157.5 KB with both ToRGB buffers, + 16 bytes of tickets, of the CU's 160 KB)
+    static_assert(sizeof(float) * (kNBUF * std::max(Geo43<32>::kSlot, Geo43<64>::kSlot) + 2 * kConstFloats + 2 * kRgbXchgFloats) + 64 <= 160 * 1024 || kNBUF != 3,
+                  "ring + tile constants + ToRGB buffers must fit the LDS of a CU");
     static PerDeviceInt resident[4];  // per device: the dynamic-LDS opt-in and the launch size = one block per CU, a multiple of 8 (XCDs)
     int resident_blocks = 0;
     hipError_t e = resident[(narrow ? 2 : 0) + (rgb ? 1 : 0)].get(
