@@ -1,5 +1,6 @@
 // Baseline JPEG (JFIF, 4:2:2, standard Huffman tables, one restart interval per MCU row) of uint8 frames in HBM:
-// gance_jpeg_encode_bounds and gance_jpeg_encode_u8 of include/gance_hip.h. The arithmetic is libjpeg's "islow" path, so
+// gance_jpeg_encode_bounds / gance_jpeg_encode_u8 (square frames) and gance_jpeg_encode_rect_bounds /
+// gance_jpeg_encode_rect_u8 (width x height, the square entries call them) of include/gance_hip.h. The arithmetic is libjpeg's "islow" path, so
 // libjpeg decodes our files to exactly the pixels it decodes from its own encode at the same quality:
 //
 //   RGB -> YCbCr        jccolor.c rgb_ycc_convert: 16-bit fixed point, Y rounded half up, Cb/Cr with ONE_HALF - 1
@@ -146,7 +147,7 @@ struct Header {
 };
 
 // SOI, APP0 (JFIF 1.01, aspect 1:1), DQT x2 (zigzag), SOF0 (Y 2x1, Cb 1x1, Cr 1x1), DHT x4, DRI, SOS
-static Header make_header(int side, int quality) {
+static Header make_header(int width, int height, int quality) {
     Header h{};
     int n = 0;
     auto put = [&](int v) { h.bytes[n++] = (uint8_t)v; };
@@ -161,7 +162,7 @@ static Header make_header(int side, int quality) {
         put16(0xFFDB); put16(67); put(c);
         for (int i = 0; i < 64; ++i) put(table[natural_of_zigzag(i)]);
     }
-    put16(0xFFC0); put16(17); put(8); put16(side); put16(side); put(3);
+    put16(0xFFC0); put16(17); put(8); put16(height); put16(width); put(3);
     put(1); put(0x21); put(0);
     put(2); put(0x11); put(1);
     put(3); put(0x11); put(1);
@@ -175,7 +176,7 @@ static Header make_header(int side, int quality) {
         for (int i = 0; i < 16; ++i) put(bits[t][i]);
         for (int i = 0; i < count; ++i) put(values[t][i]);
     }
-    put16(0xFFDD); put16(4); put16(side / 16);
+    put16(0xFFDD); put16(4); put16(width / 16);
     put16(0xFFDA); put16(12); put(3);
     put(1); put(0x00);
     put(2); put(0x11);
@@ -195,10 +196,10 @@ struct Layout {
 
 static int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
 
-static Layout layout_of(int64_t batch, int64_t side) {
+static Layout layout_of(int64_t batch, int64_t width, int64_t height) {
     Layout l{};
-    l.mcu_cols = side / 16;
-    l.mcu_rows = side / 8;
+    l.mcu_cols = width / 16;
+    l.mcu_rows = height / 8;
     l.segment_blocks = 4 * l.mcu_cols;  // Y0 Y1 Cb Cr per MCU
     l.segments = batch * l.mcu_rows;
     l.blocks = l.segments * l.segment_blocks;
@@ -265,7 +266,7 @@ __host__ __device__ __forceinline__ int chroma(int r, int g, int b, bool cr) {
     return (v + (128 << 16) + 32767) >> 16;
 }
 
-// Block `kind` (0 / 1 = left / right Y, 2 = Cb, 3 = Cr) of the MCU at (mcu_row, mcu_col) of `frame` [side][side][3]:
+// Block `kind` (0 / 1 = left / right Y, 2 = Cb, 3 = Cr) of the MCU at (mcu_row, mcu_col) of `frame` [rows][side][3]:
 // level-shifted samples, DCT, quantisation; out[64] in zigzag order. `frame` rows are 16-byte aligned (side % 16 == 0).
 __host__ __device__ inline void transform_block(const uint8_t* __restrict__ frame, int side, int mcu_row, int mcu_col, int kind,
                                                 const QuantArgs& quant, int16_t* __restrict__ out) {
@@ -325,7 +326,7 @@ __host__ __device__ inline void transform_block(const uint8_t* __restrict__ fram
 // Block index g (within the whole call) <-> (segment, position in the segment). Blocks of a segment are in MCU order:
 // MCU m holds positions 4m (Y left), 4m + 1 (Y right), 4m + 2 (Cb), 4m + 3 (Cr). Threads are numbered kind-major
 // inside a segment so that a wave works on one kind of block (one code path, adjacent pixels).
-__global__ void __launch_bounds__(256) mjpeg_transform_kernel(const uint8_t* __restrict__ frames, int side, int64_t mcu_rows,
+__global__ void __launch_bounds__(256) mjpeg_transform_kernel(const uint8_t* __restrict__ frames, int width, int height, int64_t mcu_rows,
                                                               int64_t mcu_cols, int64_t blocks, QuantArgs quant,
                                                               int16_t* __restrict__ coef) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -337,7 +338,7 @@ __global__ void __launch_bounds__(256) mjpeg_transform_kernel(const uint8_t* __r
     const int64_t frame = segment / mcu_rows;
     const int row = (int)(segment - frame * mcu_rows);
     int16_t out[64];
-    transform_block(frames + frame * side * side * 3, side, row, mcu, kind, quant, out);
+    transform_block(frames + frame * width * height * 3, width, row, mcu, kind, quant, out);
     uint4* dst = (uint4*)(coef + (segment * segment_blocks + 4 * mcu + kind) * 64);
     const uint4* src = (const uint4*)out;
 #pragma unroll
@@ -601,36 +602,30 @@ static int check_sizes(int32_t batch, int32_t side) {
     return GANCE_OK;
 }
 
-}  // namespace gance_mjpeg
-
-extern "C" {
-
-int gance_jpeg_encode_bounds(int32_t batch, int32_t side, uint64_t* workspace_bytes, uint64_t* out_capacity) {
-    using namespace gance_mjpeg;
-    if (workspace_bytes == nullptr || out_capacity == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_bounds");
-    if (const int status = check_sizes(batch, side)) return status;
-    const Layout l = layout_of(batch, side);
-    *workspace_bytes = (uint64_t)l.workspace_bytes;
-    *out_capacity = (uint64_t)l.out_capacity;
+static int check_rect_sizes(int32_t batch, int32_t width, int32_t height) {
+    if (batch < 1) return fail(GANCE_ERR_INVALID_ARGUMENT, "batch must be >= 1");
+    for (const int32_t extent : {width, height})
+        if (extent < 16 || extent > kMaxSide || extent % 16 != 0)
+            return fail(GANCE_ERR_INVALID_ARGUMENT, "width and height must be multiples of 16 in [16, " + std::to_string(kMaxSide) +
+                                                        "], got " + std::to_string(width) + " x " + std::to_string(height));
     return GANCE_OK;
 }
 
-int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, int32_t quality, void* d_workspace,
-                         uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream_ptr) {
-    using namespace gance_mjpeg;
-    if (d_frames == nullptr || d_workspace == nullptr || d_out == nullptr || d_offsets == nullptr)
-        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_u8");
-    if (const int status = check_sizes(batch, side)) return status;
+// The encode of `batch` frames [height][width][3]; sizes, quality and pointers (NULL) are checked by the callers.
+static int encode(const char* entry, const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality,
+                  void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets,
+                  void* stream_ptr) {
     if (quality < 1 || quality > 100) return fail(GANCE_ERR_INVALID_ARGUMENT, "quality must be in [1, 100], got " + std::to_string(quality));
     if ((uintptr_t)d_frames % 16 != 0 || (uintptr_t)d_workspace % 16 != 0)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "frames and workspace must be 16-byte aligned");
-    const Layout l = layout_of(batch, side);
+    const Layout l = layout_of(batch, width, height);
+    const std::string bounds = std::string(" needed (") + entry + ")";
     if (workspace_bytes < (uint64_t)l.workspace_bytes)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                                    std::to_string(l.workspace_bytes) + " needed (gance_jpeg_encode_bounds)");
+                                                    std::to_string(l.workspace_bytes) + bounds);
     if (out_capacity < (uint64_t)l.out_capacity)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "output capacity of " + std::to_string(out_capacity) + " bytes, " +
-                                                    std::to_string(l.out_capacity) + " needed (gance_jpeg_encode_bounds)");
+                                                    std::to_string(l.out_capacity) + bounds);
     int device_count = 0;
     if (hipGetDeviceCount(&device_count) != hipSuccess || device_count == 0)
         return fail(GANCE_ERR_NO_DEVICE, "no HIP device visible; libgance_hip has no CPU path");
@@ -644,10 +639,10 @@ int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, i
     uint8_t* slots = (uint8_t*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes);
     int* segment_sizes = (int*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes);
     int* segment_dst = (int*)(ws + l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes + l.size_bytes);
-    const Header header = make_header(side, quality);
+    const Header header = make_header(width, height, quality);
     hipStream_t stream = (hipStream_t)stream_ptr;
     const unsigned grid = (unsigned)((l.blocks + 255) / 256);
-    mjpeg_transform_kernel<<<grid, 256, 0, stream>>>(d_frames, side, l.mcu_rows, l.mcu_cols, l.blocks, make_quant(quality), coef);
+    mjpeg_transform_kernel<<<grid, 256, 0, stream>>>(d_frames, width, height, l.mcu_rows, l.mcu_cols, l.blocks, make_quant(quality), coef);
     mjpeg_huffman_kernel<<<grid, 256, 0, stream>>>(coef, l.mcu_cols, l.blocks, bits, bit_counts);
     mjpeg_segment_kernel<<<(unsigned)l.segments, kSegmentThreads, 0, stream>>>(bits, bit_counts, (int)l.segment_blocks, l.segment_capacity,
                                                                                slots, segment_sizes);
@@ -659,6 +654,51 @@ int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, i
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(GANCE_ERR_HIP, std::string("mjpeg launch: ") + hipGetErrorString(err));
     return GANCE_OK;
+}
+
+}  // namespace gance_mjpeg
+
+extern "C" {
+
+int gance_jpeg_encode_rect_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes, uint64_t* out_capacity) {
+    using namespace gance_mjpeg;
+    if (workspace_bytes == nullptr || out_capacity == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_rect_bounds");
+    if (const int status = check_rect_sizes(batch, width, height)) return status;
+    const Layout l = layout_of(batch, width, height);
+    *workspace_bytes = (uint64_t)l.workspace_bytes;
+    *out_capacity = (uint64_t)l.out_capacity;
+    return GANCE_OK;
+}
+
+int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality, void* d_workspace,
+                              uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream_ptr) {
+    using namespace gance_mjpeg;
+    if (d_frames == nullptr || d_workspace == nullptr || d_out == nullptr || d_offsets == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_rect_u8");
+    if (const int status = check_rect_sizes(batch, width, height)) return status;
+    return encode("gance_jpeg_encode_rect_bounds", d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out,
+                  out_capacity, d_offsets, stream_ptr);
+}
+
+int gance_jpeg_encode_bounds(int32_t batch, int32_t side, uint64_t* workspace_bytes, uint64_t* out_capacity) {
+    using namespace gance_mjpeg;
+    if (workspace_bytes == nullptr || out_capacity == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_bounds");
+    if (const int status = check_sizes(batch, side)) return status;
+    const Layout l = layout_of(batch, side, side);
+    *workspace_bytes = (uint64_t)l.workspace_bytes;
+    *out_capacity = (uint64_t)l.out_capacity;
+    return GANCE_OK;
+}
+
+int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, int32_t quality, void* d_workspace,
+                         uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream_ptr) {
+    using namespace gance_mjpeg;
+    if (d_frames == nullptr || d_workspace == nullptr || d_out == nullptr || d_offsets == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_u8");
+    if (const int status = check_sizes(batch, side)) return status;
+    return encode("gance_jpeg_encode_bounds", d_frames, batch, side, side, quality, d_workspace, workspace_bytes, d_out, out_capacity,
+                  d_offsets, stream_ptr);
 }
 
 }  // extern "C"

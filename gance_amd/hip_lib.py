@@ -216,6 +216,25 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_jpeg_encode_rect_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_jpeg_encode_rect_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_debug_place_panels_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
+    ),
+    "gance_debug_draw_panels_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
+    ),
     "gance_vec_rms_rolling_max": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p],
@@ -237,7 +256,10 @@ SIGNATURES = {
 
 # entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
 # libgance_hip_prev.so) may lack them, and only a call of the missing entry fails there
-ADDED_WITHIN_ABI = {"gance_engine_describe_plan"}
+ADDED_WITHIN_ABI = {
+    "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
+    "gance_debug_draw_panels_u8",
+}
 
 _LIB: Optional[ctypes.CDLL] = None
 
@@ -755,6 +777,106 @@ def jpeg_encode_device(  # pylint: disable=too-many-arguments
         lib,
         lib.gance_jpeg_encode_u8(
             d_frames, batch, side, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
+        ),
+    )
+
+
+def jpeg_encode_rect_bounds(batch: int, width: int, height: int) -> Tuple[int, int]:
+    """(workspace bytes, output capacity) of one `jpeg_encode_rect_device` call of `batch` frames [height][width][3].
+    :raises ValueError: width or height not a multiple of 16 in [16, 8192], or batch < 1."""
+    lib = load_library()
+    workspace, capacity = ctypes.c_uint64(), ctypes.c_uint64()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_jpeg_encode_rect_bounds(batch, width, height, ctypes.byref(workspace), ctypes.byref(capacity))
+    )
+    return int(workspace.value), int(capacity.value)
+
+
+def jpeg_encode_rect_device(  # pylint: disable=too-many-arguments
+    d_frames: int, batch: int, width: int, height: int, quality: int, d_workspace: int, workspace_bytes: int, d_out: int,
+    out_capacity: int, d_offsets: int, stream: int = 0,
+) -> None:
+    """
+    `jpeg_encode_device` for frames [batch][height][width][3] (DRI = width / 16): the debug video's row of panels.
+    :raises ValueError: bad width or height, quality outside 1..100, workspace or capacity below `jpeg_encode_rect_bounds`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_jpeg_encode_rect_u8(
+            d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
+        ),
+    )
+
+
+class DebugAxis(ctypes.Structure):
+    """`gance_debug_axis` of include/gance_hip.h: a pixel rectangle of a panel and the data limits mapped onto it."""
+
+    _fields_ = [
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("x_min", ctypes.c_double), ("x_max", ctypes.c_double), ("y_min", ctypes.c_double), ("y_max", ctypes.c_double),
+    ]
+
+
+class DebugMark(ctypes.Structure):
+    """`gance_debug_mark` of include/gance_hip.h."""
+
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("axis", ctypes.c_int32), ("dtype", ctypes.c_int32), ("count", ctypes.c_int32),
+        ("data", ctypes.c_void_p), ("limit", ctypes.c_int64), ("frame_stride", ctypes.c_int64),
+        ("frame_divisor", ctypes.c_int32), ("size", ctypes.c_int32), ("dash_on", ctypes.c_int32), ("dash_off", ctypes.c_int32),
+        ("flag_mask", ctypes.c_int32), ("flag_value", ctypes.c_int32), ("rgba", ctypes.c_uint8 * 4), ("reserved", ctypes.c_int32),
+        ("x_start", ctypes.c_double),
+    ]
+
+
+DEBUG_MARK_POINTS, DEBUG_MARK_POLYLINE, DEBUG_MARK_CURSOR, DEBUG_MARK_BAR = range(4)
+DEBUG_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int32): 2}
+DEBUG_MAX_AXES, DEBUG_MAX_MARKS = 8, 24
+# `gance_debug_frame`: what changes from frame to frame
+DEBUG_FRAME_DTYPE = np.dtype([("number", np.int64), ("cursor", np.float64), ("flags", np.int32), ("reserved", np.int32)])
+
+
+def debug_place_panels_device(  # pylint: disable=too-many-arguments
+    d_src: int, src_count: int, side: int, first_number: int, divisor: int, src_base: int, batch: int, d_out: int,
+    out_frame_stride: int, out_row_stride: int, stream: int = 0,
+) -> None:
+    """
+    One image panel of `batch` consecutive debug frames: frame b shows src[(first_number + b) // divisor - src_base]
+    ([src_count][side][side][3] uint8 in HBM); the panel's row r of frame b starts at d_out + b * out_frame_stride +
+    r * out_row_stride. Asynchronous on `stream`.
+    :raises ValueError: bad side, strides or alignment, or frames that would read outside `src_count`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_debug_place_panels_u8(
+            d_src or None, src_count, side, first_number, divisor, src_base, batch, d_out or None, out_frame_stride, out_row_stride,
+            stream or None,
+        ),
+    )
+
+
+def debug_draw_panels_device(  # pylint: disable=too-many-arguments
+    d_chrome: int, side: int, axes, marks, d_frames: int, batch: int, d_out: int, out_frame_stride: int, out_row_stride: int,
+    stream: int = 0,
+) -> None:
+    """
+    One plot panel of `batch` debug frames: the chrome template [side][side][3] (HBM) copied to every frame, then `marks`
+    (a sequence of DebugMark, or None) composited in order on `axes` (a sequence of DebugAxis, or None) with the per-frame
+    records at d_frames (DEBUG_FRAME_DTYPE [batch] in HBM). Asynchronous on `stream`; see include/gance_hip.h.
+    :raises ValueError: a missing table, bad sizes or strides, axes that overlap or leave the panel, a bad mark.
+    """
+    lib = load_library()
+    # (None stands for a NULL table with a count of one: the library refuses it, like every other bad argument)
+    axes_array = (DebugAxis * len(axes))(*axes) if axes is not None else None
+    marks_array = (DebugMark * max(1, len(marks)))(*marks) if marks is not None else None
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_debug_draw_panels_u8(
+            d_chrome or None, side, axes_array, len(axes) if axes is not None else 1, marks_array,
+            len(marks) if marks is not None else 1, d_frames or None, batch, d_out or None, out_frame_stride, out_row_stride,
+            stream or None,
         ),
     )
 

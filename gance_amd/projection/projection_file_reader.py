@@ -196,6 +196,7 @@ def write_projection_npz(  # pylint: disable=too-many-arguments
     target_images: Optional[np.ndarray] = None,
     original_target_path: str = "synthetic.mp4",
     original_network_path: str = "synthetic.pkl",
+    final_images: Optional[np.ndarray] = None,
 ) -> None:
     """Write the `.npz` container (synthetic projections for tests and benchmarks)."""
     latents = np.asarray(final_latents, dtype=np.float32)
@@ -212,4 +213,6 @@ def write_projection_npz(  # pylint: disable=too-many-arguments
     arrays = {"attributes": np.array(json.dumps(attributes)), FINAL_LATENTS_GROUP_NAME: latents}
     if target_images is not None:
         arrays[TARGET_IMAGES_GROUP_NAME] = np.asarray(target_images, dtype=np.uint8)
+    if final_images is not None:
+        arrays[FINAL_IMAGE_GROUP_NAME] = np.asarray(final_images, dtype=np.uint8)
     np.savez(str(path), **arrays)

@@ -13,8 +13,10 @@ projection-file-blend end to end: WAV(s) + projection file + network(s) -> frame
   run-length filter only ever holds back the frames of a run that is still shorter than `track_length`;
 * the video is Motion-JPEG in an OpenDML AVI with the WAVs muxed in (`output_format="avi"`), encoded in HBM by the HIP
   JPEG encoder and written by gance_amd/video/mjpeg_avi.py, instead of x264 through ffmpeg; `output_format="npy"` (the
-  default) writes the raw frames as a `.npy` uint8 array [N][S][S][3]. Asking for the debug video raises
-  NotImplementedError.
+  default) writes the raw frames as a `.npy` uint8 array [N][S][S][3];
+* the debug video (`debug_path`) is composed in HBM as well (gance_amd/debug_video: image panels resized and placed, plot
+  panels rasterised by HIP kernels from per-window templates instead of one matplotlib draw per frame) and written as a
+  second Motion-JPEG AVI.
 """
 
 import os
@@ -30,6 +32,7 @@ import torch.distributed as dist
 from gance_amd import divisor, frame_sharding, hip_lib, torch_ops  # noqa: F401  (torch_ops registers torch.ops.gance.*)
 from gance_amd.data_into_network_visualization import visualization_inputs
 from gance_amd.data_into_network_visualization.visualization_common import DataLabel, ResultLayers
+from gance_amd.debug_video.compose import DebugSources, DebugVideo, DebugVideoComposer, validate_side_length
 from gance_amd.logger_common import LOGGER
 from gance_amd.network_interface.network_functions import TRUNCATION_PSI, MultiNetwork
 
@@ -203,21 +206,32 @@ class OverlayParameters(NamedTuple):
     face_finder: Optional[overlay_eye_tracking.FaceFinder] = None  # default: overlay_eye_tracking.FACE_FINDER_FACTORY()
 
 
-def music_complexity_skip_mask(audio: np.ndarray, vector_length: int, window: int, threshold: float) -> List[bool]:
+def music_complexity_result_layers(audio: np.ndarray, vector_length: int, window: int) -> ResultLayers:
     """
-    Frames where the music's complexity is changing too fast for an overlay
-    (gance/projection_file_blend.py:192-226): zlib size per vector, rolling average + savgol,
-    first derivative, absolute value, rolling sum; NaN (window not yet full) counts as infinity.
+    How fast the music's complexity changes (gance/projection_file_blend.py:201-221): zlib size per vector, rolling
+    average + savgol, first derivative, absolute value, rolling sum; NaN while the window is not yet full.
     """
     smoothed_sizes = vector_reduction.reduce_vector_gzip_compression_rolling_average(audio, vector_length)
     derived = vector_reduction.derive_results_layers(smoothed_sizes, order=1).result.data
-    mask = vector_reduction.rolling_sum_results_layers(
+    return vector_reduction.rolling_sum_results_layers(
         vector_reduction.absolute_value_results_layers(
             ResultLayers(result=DataLabel(derived, "Gzipped audio, smoothed, averaged, 1st order derivation."))
         ),
         window_length=window,
     )
+
+
+def skip_mask_of(mask: ResultLayers, threshold: float) -> List[bool]:
+    """Frames to skip (gance/projection_file_blend.py:226-233): NaN counts as infinity."""
     return list(pd.Series(mask.result.data).fillna(np.inf) > threshold)
+
+
+def music_complexity_skip_mask(audio: np.ndarray, vector_length: int, window: int, threshold: float) -> List[bool]:
+    """
+    Frames where the music's complexity is changing too fast for an overlay
+    (gance/projection_file_blend.py:192-226): `music_complexity_result_layers` above the threshold.
+    """
+    return skip_mask_of(music_complexity_result_layers(audio, vector_length, window), threshold)
 
 
 def apply_eye_tracking_overlay(  # pylint: disable=too-many-arguments,too-many-locals
@@ -282,6 +296,7 @@ class _BlendInputs(NamedTuple):
     target_images: Optional[np.ndarray]
     audio: Optional[np.ndarray]
     frame_multiplier: int
+    debug: Optional[DebugSources] = None  # only when the debug video is asked for
 
 
 def _prepare_blend_inputs(  # pylint: disable=too-many-arguments,too-many-locals
@@ -297,10 +312,16 @@ def _prepare_blend_inputs(  # pylint: disable=too-many-arguments,too-many-locals
     want_target_images: bool,
     device: torch.device,
     timings: Optional[Dict[str, float]] = None,
+    want_debug: bool = False,
 ) -> _BlendInputs:
-    """Rank 0: projection file + WAV -> per-frame latent matrices and network indices in HBM (the reference's checks included)."""
+    """
+    Rank 0: projection file + WAV -> per-frame latent matrices and network indices in HBM (the reference's checks included).
+    :param want_debug: also keep what the debug video shows: `reader.final_images`, the blend stages `final` (input A) and
+    `index_smoothed`, and row 0 of the projected latents (input B), as DebugSources.
+    """
     vector_length = networks.expected_vector_length
     target_images = None
+    final_images = None
     clock = time.perf_counter()
     # the audio -> latent stage has global dependencies over a few MB: once, on rank 0
     with projection_file_reader.load_projection_file(Path(projection_file_path)) as reader:
@@ -308,6 +329,10 @@ def _prepare_blend_inputs(  # pylint: disable=too-many-arguments,too-many-locals
         attributes = reader.projection_attributes
         if want_target_images:
             target_images = np.stack(list(reader.target_images))
+        if want_debug:
+            final_images = list(reader.final_images)
+            # (a projection file written without final images: the panel stays black rather than the video empty)
+            final_images = np.stack(final_images) if final_images else np.zeros((attributes.projection_frame_count, 16, 16, 3), dtype=np.uint8)
     final_latents_in_file = underlying_length(final_latents.data) / vector_length
     LOGGER.info(
         f"Reading projection file. Complete: {attributes.complete}, "
@@ -329,16 +354,41 @@ def _prepare_blend_inputs(  # pylint: disable=too-many-arguments,too-many-locals
     blend_timings: Optional[Dict[str, float]] = {} if timings is not None else None
     blend = visualization_inputs.alpha_blend_projection_file_device(
         final_latents.data, alpha, fft_roll_enabled, fft_amplitude_range, blend_depth, audio, vector_length,
-        len(networks.network_indices), device=device.index, timings=blend_timings,
+        len(networks.network_indices), device=device.index, timings=blend_timings, keep_stages=want_debug,
     )
     dlatents, indices = blend.dlatents, blend.network_indices
+    debug = None
+    if want_debug:
+        try:  # (one read-back before the stream starts: the stages live in the blend's workspace, which is freed below)
+            spectrogram = blend.blend.read_stage("final")
+            index_smoothed = blend.blend.read_stage("index_smoothed")
+        except Exception:
+            blend.blend.close()
+            raise
+        count = int(dlatents.shape[0]) if frames_to_visualize is None else min(int(dlatents.shape[0]), frames_to_visualize)
+        row0 = np.ascontiguousarray(np.asarray(final_latents.data)[0], dtype=np.float32).reshape(-1, vector_length)
+        debug = DebugSources(
+            a_vectors=torch.from_numpy(spectrogram[:count]).to(device),
+            b_vectors=torch.from_numpy(row0).to(device),
+            limits={
+                "a": (float(spectrogram.min()), float(spectrogram.max())),
+                "b": (float(row0.min()), float(row0.max())),
+                "combined": (float(dlatents.min()), float(dlatents.max())),
+            },
+            labels={"a": "Rolled Audio Spectrogram", "b": final_latents.label, "combined": f"Combined w/ Alpha Blending, a={alpha}"},
+            network_indices=ResultLayers(
+                result=DataLabel(indices[:count].cpu().numpy().astype(int), "Savgol Smoothing Filter (window=3, polyorder=2) Scaled, Quantized"),
+                layers=[DataLabel(index_smoothed[:count], "Savgol Smoothing Filter (window=3, polyorder=2)")],
+            ),
+            final_images=final_images,
+        )
     blend.blend.close()
     if timings is not None:
         timings["audio_to_latents_ms"] = (time.perf_counter() - clock) * 1e3
         timings["audio_to_latents_split_ms"] = blend_timings
     if frames_to_visualize is not None:
         dlatents, indices = dlatents[:frames_to_visualize], indices[:frames_to_visualize]
-    return _BlendInputs(dlatents, indices, int(dlatents.shape[0]), target_images, audio, int(frame_multiplier))
+    return _BlendInputs(dlatents, indices, int(dlatents.shape[0]), target_images, audio, int(frame_multiplier), debug)
 
 
 # Pieces per network in a window of the multi-network stream: a window of w * networks pieces ends in up to `networks` short
@@ -415,6 +465,10 @@ class _StreamingOverlay:
         self._pending: List[Tuple[int, torch.Tensor, torch.Tensor, list]] = []  # (first, background, foreground, boxes per frame)
         self.chunks_held_max = 0
         self.overlays_written = 0
+        # the debug video's taps: called with the contexts of every chunk as it is evaluated; foreground of a released chunk
+        self.on_contexts: Optional[Callable[[list], None]] = None
+        self.keep_foregrounds = False
+        self.foregrounds: Dict[int, torch.Tensor] = {}
         if -(-num_frames // frame_multiplier) > len(target_images):
             raise ValueError("the projection file holds too few target images for the frames being written")
 
@@ -441,6 +495,8 @@ class _StreamingOverlay:
             written = [boxes if keep[first + i] else None for i, boxes in enumerate(boxes_list)]
             self.overlays_written += sum(boxes is not None for boxes in written)
             out.append((first, overlay_common.write_boxes_onto_frames_device(foreground, background, written)))
+            if self.keep_foregrounds:
+                self.foregrounds[first] = foreground
         return out
 
     def push(self, first: int, frames: torch.Tensor) -> List[Tuple[int, torch.Tensor]]:
@@ -454,6 +510,8 @@ class _StreamingOverlay:
             min_bbox_distance=self._parameters.bbox_distance, skip_mask=skips, face_finder=self._parameters.face_finder,
         )
         boxes_list = list(result.bbox_lists)
+        if self.on_contexts is not None:
+            self.on_contexts(list(result.contexts))
         self._gated.extend(not skip and boxes is not None for skip, boxes in zip(skips, boxes_list))
         self._pending.append((first, background, foreground, boxes_list))
         self.chunks_held_max = max(self.chunks_held_max, len(self._pending))
@@ -465,10 +523,13 @@ class _StreamingOverlay:
 
 
 class EncodedFrames:
-    """A chunk of JPEG-encoded frames of side `side` on the host: frame i is the JFIF file data[offsets[i]:offsets[i + 1]]."""
+    """
+    A chunk of JPEG-encoded frames of side `side` on the host: frame i is the JFIF file data[offsets[i]:offsets[i + 1]].
+    Debug frames are `side` high and `width` wide.
+    """
 
-    def __init__(self, data: np.ndarray, offsets: np.ndarray, side: int) -> None:
-        self.data, self.offsets, self.side = data, offsets, side
+    def __init__(self, data: np.ndarray, offsets: np.ndarray, side: int, width: Optional[int] = None) -> None:
+        self.data, self.offsets, self.side, self.width = data, offsets, side, side if width is None else width
 
     def __len__(self) -> int:
         return len(self.offsets) - 1
@@ -490,18 +551,18 @@ class _EncodedHostRing:
         self._data: List[Optional[torch.Tensor]] = [None] * slots
         self._offsets: List[Optional[torch.Tensor]] = [None] * slots
         self._next = 0
-        self._pending = None  # (first, count, bytes, slot, event, side)
+        self._pending = None  # (first, count, bytes, slot, event, side, width)
 
     def _finish(self):
         if self._pending is None:
             return None
-        first, count, size, slot, event, side = self._pending
+        first, count, size, slot, event, side, width = self._pending
         self._pending = None
         event.synchronize()
-        return first, EncodedFrames(self._data[slot][:size].numpy(), self._offsets[slot][: count + 1].numpy(), side)
+        return first, EncodedFrames(self._data[slot][:size].numpy(), self._offsets[slot][: count + 1].numpy(), side, width)
 
     def push(  # pylint: disable=too-many-arguments
-        self, first: int, data: torch.Tensor, offsets: torch.Tensor, side: int, reader_stream
+        self, first: int, data: torch.Tensor, offsets: torch.Tensor, side: int, reader_stream, width: Optional[int] = None
     ) -> Tuple[int, Optional[tuple]]:
         """Start draining one encoded chunk; returns (bytes it moves to the host, previous chunk or None)."""
         done = self._finish()
@@ -521,7 +582,7 @@ class _EncodedHostRing:
             self._data[slot][:size].copy_(data[:size], non_blocking=True)
             event = torch.cuda.Event()
             event.record(reader_stream)
-        self._pending = (first, count, size, slot, event, side)
+        self._pending = (first, count, size, slot, event, side, width)
         return size + 8 * (count + 1), done
 
     def flush(self):
@@ -544,6 +605,17 @@ def encode_into_ring(  # pylint: disable=too-many-arguments
         yield ring.push(first + start, data, offsets, side, reader_stream)
 
 
+def encode_debug_into_ring(  # pylint: disable=too-many-arguments
+    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream
+) -> Iterator[Tuple[int, Optional[tuple]]]:
+    """`encode_into_ring` for composed debug frames [n, side, P * side, 3]: torch.ops.gance.jpeg_encode_rect."""
+    side, width = int(frames.shape[1]), int(frames.shape[2])
+    for start in range(0, int(frames.shape[0]), piece_frames):
+        with torch.cuda.stream(reader_stream):
+            data, offsets = torch.ops.gance.jpeg_encode_rect(frames[start : start + piece_frames], quality)
+        yield ring.push(first + start, data, offsets, side, reader_stream, width=width)
+
+
 def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements,too-many-branches
     wav: List[str],
     network_paths: List[Path],
@@ -562,6 +634,8 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     drain: str = "rank0",
     on_total: Optional[Callable[[int], None]] = None,
     jpeg_quality: Optional[int] = None,
+    *,
+    debug: Optional[DebugVideo] = None,
 ) -> Iterator[Tuple[int, int, np.ndarray]]:
     """
     The frame stream of the reference's pipeline (gance/projection_file_blend.py:343 hands an iterator of frames to
@@ -588,6 +662,13 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     call, and drains only the offsets and the compressed bytes to a pinned host ring: the generator yields
     (first_frame_index, total_frames, EncodedFrames) and raw frames never reach the host; timings["bytes_to_host"] counts
     the compressed bytes. Needs drain="rank0" and an output side that is a multiple of 16.
+    :param debug: None (default): nothing changes. A DebugVideo: rank 0 also composes the debug frames of every released
+    chunk in HBM on the reader stream (gance_amd/debug_video/compose.py: output, foreground, final images, synthesis
+    inputs, overlay computation, overlay binary mask, side by side), encodes them with torch.ops.gance.jpeg_encode_rect at
+    `debug.jpeg_quality`, drains them through a second encoded ring and hands them to `debug.on_encoded` in frame order.
+    What the generator yields is unchanged. With the overlay on, composed debug frames wait in HBM until the contexts of
+    their window are complete: at most one debug window plus one chunk (timings["debug_frames_held_max"]). Needs
+    drain="rank0"; with `overlay`, `debug.window` must be given.
     """
     if drain not in frame_sharding.DRAIN_MODES:
         raise ValueError(f"drain must be one of {frame_sharding.DRAIN_MODES}, got {drain!r}")
@@ -600,6 +681,14 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
             raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
         if output_side_length is not None and int(output_side_length) % 16 != 0:
             raise ValueError(f"the JPEG encoder needs an output side that is a multiple of 16, got {output_side_length}")
+    if debug is not None:
+        if drain != "rank0":
+            raise ValueError("the debug video is composed on rank 0 after the gather: drain=\"rank0\"")
+        validate_side_length(debug.side_length)
+        if overlay is not None and debug.window is None:
+            raise ValueError("the debug video of an overlay run needs debug_window (frames per overlay context)")
+        if not 1 <= int(debug.jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in [1, 100], got {debug.jpeg_quality}")
     rank = dist.get_rank() if dist.is_initialized() else 0
     world_size = dist.get_world_size() if dist.is_initialized() else 1
     device = torch.device("cuda", torch.cuda.current_device())
@@ -613,7 +702,7 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
             try:
                 inputs = _prepare_blend_inputs(
                     wav, networks, frames_to_visualize, output_fps, alpha, fft_roll_enabled, fft_amplitude_range,
-                    projection_file_path, blend_depth, overlay is not None, device, timings,
+                    projection_file_path, blend_depth, overlay is not None, device, timings, want_debug=debug is not None,
                 )
             except Exception as error:  # pylint: disable=broad-except
                 failure = error
@@ -655,16 +744,25 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
         num_networks = len(set(networks.network_paths))
         synthesize_piece = _WindowSynthesizer(dlatents, indices, networks, side, frames_per_call, 1 if num_networks == 1 else STREAM_WINDOW_PIECES_PER_NETWORK * num_networks)
         stage = None
+        mask_layers = None
         if overlay is not None and rank == 0:
             music_mask = overlay.complexity_change_rolling_sum_window is not None and overlay.complexity_change_threshold is not None
-            skip_mask = (
-                music_complexity_skip_mask(
-                    inputs.audio, networks.expected_vector_length, overlay.complexity_change_rolling_sum_window, overlay.complexity_change_threshold
-                )[:num_frames]
-                if music_mask
-                else [False] * num_frames
-            )
+            if music_mask:
+                mask_layers = music_complexity_result_layers(
+                    inputs.audio, networks.expected_vector_length, overlay.complexity_change_rolling_sum_window
+                )
+            skip_mask = skip_mask_of(mask_layers, overlay.complexity_change_threshold)[:num_frames] if music_mask else [False] * num_frames
             stage = _StreamingOverlay(inputs.target_images, inputs.frame_multiplier, overlay, skip_mask, num_frames, side, device)
+        composer, debug_ring = None, None
+        if debug is not None and rank == 0:
+            composer = DebugVideoComposer(
+                debug.side_length, debug.window, num_frames, inputs.frame_multiplier, inputs.debug, inputs.dlatents, device,
+                overlay_thresholds=(overlay.phash_distance, overlay.bbox_distance) if overlay is not None else None,
+                mask=mask_layers, mask_threshold=overlay.complexity_change_threshold if mask_layers is not None else None,
+            )
+            debug_ring = _EncodedHostRing(slots=3)
+            if stage is not None:
+                stage.on_contexts, stage.keep_foregrounds = composer.add_contexts, True
         if jpeg_quality is not None and side % 16 != 0:
             raise ValueError(f"the JPEG encoder needs an output side that is a multiple of 16, got {side}")
         ring = None
@@ -688,6 +786,23 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
                 if done is not None:
                     yield done
 
+        def debug_chunks(composed, reader_stream) -> None:
+            """Encodes composed debug chunks on the reader stream and hands every chunk that has landed to the callback."""
+            for composed_first, composed_frames in composed:
+                if debug.on_composed is not None:
+                    with torch.cuda.stream(reader_stream):
+                        debug.on_composed(composed_first, composed_frames)
+                for _moved, done in encode_debug_into_ring(
+                    debug_ring, composed_first, composed_frames, int(debug.jpeg_quality), frames_per_call, reader_stream
+                ):
+                    if done is not None:
+                        debug.on_encoded(done[0], done[1])
+
+        def debug_chunk(ready_first: int, ready_frames: torch.Tensor, reader_stream) -> None:
+            with torch.cuda.stream(reader_stream):
+                composed = composer.push(ready_first, ready_frames, stage.foregrounds.pop(ready_first) if stage is not None else None)
+            debug_chunks(composed, reader_stream)
+
         for first, frames, reader_stream in frame_sharding.ordered_device_chunks(
             synthesize_piece, num_frames, frames_per_call, (side, side, 3), device, drain=drain
         ):
@@ -703,15 +818,26 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
                 with torch.cuda.stream(reader_stream):  # (the chunk view may only be read on the reader stream)
                     ready = stage.push(first, frames)
             for ready_first, ready_frames in ready:
+                if composer is not None:  # (before the yield: a chunk view is only valid until the generator is advanced)
+                    debug_chunk(ready_first, ready_frames, reader_stream)
                 for done in drain_chunk(ready_first, ready_frames, reader_stream):
                     yield done[0], num_frames, done[1]
         if stage is not None:
             with torch.cuda.stream(reader_stream):
                 ready = stage.flush()
             for ready_first, ready_frames in ready:
+                if composer is not None:
+                    debug_chunk(ready_first, ready_frames, reader_stream)
                 for done in drain_chunk(ready_first, ready_frames, reader_stream):
                     yield done[0], num_frames, done[1]
             LOGGER.info(f"Eye tracking overlay written on {stage.overlays_written} of {num_frames} frames")
+        if composer is not None and num_frames > 0:
+            with torch.cuda.stream(reader_stream):
+                composed = composer.flush()
+            debug_chunks(composed, reader_stream)
+            last_debug = debug_ring.flush()
+            if last_debug is not None:
+                debug.on_encoded(last_debug[0], last_debug[1])
         if ring is not None:
             last = ring.flush()
             if last is not None:
@@ -726,6 +852,8 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
             if stage is not None:
                 timings["overlay_chunks_held_max"] = stage.chunks_held_max
                 timings["overlays_written"] = stage.overlays_written
+            if composer is not None:
+                timings["debug_frames_held_max"] = composer.frames_held_max
     finally:
         if own_networks:
             networks.unload()
@@ -777,8 +905,8 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     output_fps: float,
     output_side_length: int,
     debug_path: Optional[str],
-    debug_window: Optional[int],  # pylint: disable=unused-argument
-    debug_side_length: Optional[int],  # pylint: disable=unused-argument
+    debug_window: Optional[int],
+    debug_side_length: Optional[int],
     alpha: float,
     fft_roll_enabled: bool,
     fft_amplitude_range: Tuple[int, int],
@@ -799,7 +927,12 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     written to `output_path` as a `.npy` uint8 array (`output_format="npy"`, the default), or as a video.
     :raises ValueError: the reference's own checks (music mask without overlay, invalid projection file,
     non-integer fps ratio).
-    :raises NotImplementedError: debug video requested (out of scope), or the overlay requested
+    With `debug_path` the debug video (gance/projection_file_blend.py:288-341) is written there as a Motion-JPEG AVI with
+    the WAVs muxed in, whatever `output_format` says about the main output: per frame a row of square panels of
+    `debug_side_length` (blended output, foreground, final images, synthesis inputs, overlay computation, overlay binary
+    mask; the overlay's three only with the overlay / music mask on), plot windows of `debug_window` frames (synthesis
+    inputs: a fifth of the run if None), encoded at `jpeg_quality`; forces drain="rank0".
+    :raises NotImplementedError: the overlay requested
     without a landmark detector (face_recognition / dlib is not installed; see overlay_eye_tracking).
     :param drain: (not a parameter of the reference) how frames reach the output file under `torch.distributed`:
     "rank0" = gathered over RCCL and written by rank 0; "per-rank" = every rank writes the pieces it synthesised into
@@ -809,7 +942,8 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     Motion-JPEG: frames encoded in HBM on rank 0 (torch.ops.gance.jpeg_encode at `jpeg_quality`), an OpenDML AVI at
     `output_path` exactly, the WAVs concatenated as its audio stream (gance_amd/video/mjpeg_avi.py); forces drain="rank0".
     :raises ValueError: (also) an unknown output_format, or "avi" with an output side that is not a multiple of 16 (checked
-    before any synthesis; with output_side_length None the networks' own side, checked once they are loaded).
+    before any synthesis; with output_side_length None the networks' own side, checked once they are loaded); `debug_path`
+    without a `debug_side_length` that is a multiple of 16, or with the overlay on and no `debug_window` (before any synthesis).
     """
     if output_format not in ("npy", "avi"):
         raise ValueError(f"output_format must be \"npy\" or \"avi\", got {output_format!r}")
@@ -828,8 +962,14 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     )
     if overlay_music_mask_enabled and not overlay_enabled:
         raise ValueError("Overlay music mask without overlay being enabled is not supported!")
+    debug_side = None
     if debug_path is not None:
-        raise NotImplementedError("the matplotlib debug video is out of scope")
+        debug_side = validate_side_length(debug_side_length)
+        if overlay_enabled and debug_window is None:
+            raise ValueError("the debug video of an overlay run needs debug_window (frames per overlay context)")
+        if not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
+        mjpeg_avi.frame_rate_fraction(output_fps)
     overlay = (
         OverlayParameters(
             phash_distance, bbox_distance, track_length, complexity_change_rolling_sum_window, complexity_change_threshold
@@ -837,7 +977,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         if overlay_enabled
         else None
     )
-    if overlay is not None or encode:
+    if overlay is not None or encode or debug_path is not None:
         drain = "rank0"
     # frame chunks go straight from the pinned ring into the (memory-mapped) output file: nothing holds the video
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -847,6 +987,11 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         # rank 0 creates the file (the frame side is known up front: every frame is resized to output_side_length); with
         # drain="per-rank" the other ranks then map the same file and write their own pieces into it
         state["total"] = total
+        if debug_path is not None and rank == 0:
+            debug_panels = 3 + (2 if overlay_enabled else 0) + (1 if overlay_music_mask_enabled else 0)
+            state["debug_writer"] = mjpeg_avi.MjpegAviWriter(
+                debug_path, debug_side, output_fps, wavs=wav, width=debug_panels * debug_side, height=debug_side
+            )
         if output_path is None or (rank != 0 and drain != "per-rank"):
             return
         if encode:
@@ -862,11 +1007,16 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         elif total > 0:
             state["writer"] = np.load(_npy_path(output_path), mmap_mode="r+")
 
+    def write_debug_frames(_first: int, encoded: EncodedFrames) -> None:  # (chunks arrive in frame order on rank 0)
+        for index in range(len(encoded)):
+            state["debug_writer"].add_frame(encoded.frame(index))
+
+    debug = DebugVideo(debug_side, debug_window, write_debug_frames, jpeg_quality=int(jpeg_quality)) if debug_path is not None else None
     try:
         for first, _total, frames in projection_file_blend_frame_chunks(
             wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled,
             fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=open_output,
-            jpeg_quality=int(jpeg_quality) if encode else None,
+            jpeg_quality=int(jpeg_quality) if encode else None, debug=debug,
         ):
             if encode and state.get("avi_side_pending") and state["writer"] is None:
                 state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, frames.side, output_fps, wavs=wav)
@@ -882,5 +1032,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     finally:
         if encode and state["writer"] is not None:
             state["writer"].close()
+        if state.get("debug_writer") is not None:
+            state["debug_writer"].close()
     if state["writer"] is not None and not encode:
         state["writer"].flush()

@@ -7,6 +7,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.resize_bicubic(frames, side)           [B, S, S, 3] u8  -> [B, side, side, 3] u8
     torch.ops.gance.synthesize_w_out / synthesize_z_out / resize_bicubic_out   the same, into a caller-owned `out`
     torch.ops.gance.blend(audio, latent_row0, blend)       [samples] f32, [F, L] f32 -> ([N, depth, L] f32, [N] i32)
+    torch.ops.gance.jpeg_encode_rect(frames, quality)      [B, H, W, 3] u8  -> the same for frames that are not square
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
@@ -249,4 +250,34 @@ def jpeg_encode(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch
 def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
     batch, side = int(frames.shape[0]), int(frames.shape[1])
     _, capacity = hip_lib.jpeg_encode_bounds(batch, side)
+    return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+@torch.library.custom_op("gance::jpeg_encode_rect", mutates_args=(), device_types="cuda")
+def jpeg_encode_rect(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    `jpeg_encode` for frames [B, H, W, 3] with H and W multiples of 16 (the debug video's row of panels, written by the
+    reference through write_source_to_disk_consume, gance/projection_file_blend.py:302-341): the same (data, offsets);
+    square frames give the bytes `jpeg_encode` gives.
+    """
+    _require_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [B, H, W, 3], got {tuple(frames.shape)}")
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    workspace_bytes, capacity = hip_lib.jpeg_encode_rect_bounds(batch, width, height)
+    frames = frames.contiguous()
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
+    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
+    hip_lib.jpeg_encode_rect_device(
+        frames.data_ptr(), batch, width, height, int(quality), workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity,
+        offsets.data_ptr(), _stream(frames),
+    )
+    return data, offsets
+
+
+@jpeg_encode_rect.register_fake
+def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    _, capacity = hip_lib.jpeg_encode_rect_bounds(batch, width, height)
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)

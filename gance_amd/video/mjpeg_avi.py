@@ -73,6 +73,8 @@ class MjpegAviWriter:  # pylint: disable=too-many-instance-attributes
     `add_frame(jpeg_bytes)` in frame order, then `close()` (or use as a context manager). The file is complete only
     after `close()`.
     :param segment_limit: bytes per RIFF segment (default 1 GiB); a test can force many segments with a small one.
+    :param width: :param height: (keyword only) frames that are not square, e.g. the debug video's row of panels; each
+    defaults to `side`.
     """
 
     def __init__(  # pylint: disable=too-many-arguments
@@ -82,9 +84,13 @@ class MjpegAviWriter:  # pylint: disable=too-many-instance-attributes
         output_fps: float,
         wavs: Optional[Sequence[Union[str, Path]]] = None,
         segment_limit: int = DEFAULT_SEGMENT_LIMIT,
+        *,
+        width: Optional[int] = None,
+        height: Optional[int] = None,
     ) -> None:
         self._rate, self._scale = frame_rate_fraction(output_fps)
-        self._width = self._height = int(side)
+        self._width = int(side if width is None else width)
+        self._height = int(side if height is None else height)
         self._segment_limit = int(segment_limit)
         self._audio: Optional[np.ndarray] = None
         self._audio_rate = 0

@@ -370,6 +370,70 @@ int gance_jpeg_encode_bounds(int32_t batch, int32_t side, uint64_t* workspace_by
 int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, int32_t quality, void* d_workspace,
                          uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream);
 
+/* Frames [batch][height][width][3] of any 4:2:2-compatible size (the debug video is a row of square panels:
+ * horizontal_concat_images at gance/projection_file_blend.py:302-334, written with high_quality=False at :335-341
+ * "because this video can be shaped very weird"). width and height are multiples of 16 in [16, 8192], DRI = width / 16;
+ * everything else as gance_jpeg_encode_bounds / gance_jpeg_encode_u8, which are these with width = height = side and
+ * produce the same bytes as before. */
+int gance_jpeg_encode_rect_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes, uint64_t* out_capacity);
+int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality,
+                              void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                              int64_t* d_offsets, void* stream);
+
+/* ---- debug-video panels ------------------------------------------------------------------------
+ * Replaces the per-frame matplotlib drawing of the debug video: fig.canvas.draw() per frame in
+ * render_current_matplotlib_frame (gance/data_into_network_visualization/visualization_common.py) under
+ * _write_data_to_axes (network_visualization.py:254-400), visualize_overlay_computation
+ * (gance/overlay/overlay_visualization.py:128-234) and visualize_result_layers (visualize_vector_reduction.py:85-179),
+ * and the horizontal_concat_images of gance/projection_file_blend.py:302-334.
+ * A debug frame is a row of square panels; both entries write ONE panel [side][side][3] of `batch` consecutive
+ * frames: panel row r of frame b starts at d_out + b * out_frame_stride + r * out_row_stride (bytes; d_out and both
+ * strides 16-byte aligned; side a multiple of 16 in [16, 4096]). Asynchronous on `stream`, no host synchronisation;
+ * the bytes written are a pure function of the arguments (the same however the frames are split into calls).
+ * Both return GANCE_ERR_INVALID_ARGUMENT before touching a device for a NULL pointer, a bad side or stride, a source
+ * index outside `src_count`, or a table that fails the rules below. */
+#define GANCE_DEBUG_MAX_AXES 8
+#define GANCE_DEBUG_MAX_MARKS 24
+enum { GANCE_DEBUG_MARK_POINTS = 0, GANCE_DEBUG_MARK_POLYLINE = 1, GANCE_DEBUG_MARK_CURSOR = 2, GANCE_DEBUG_MARK_BAR = 3 };
+enum { GANCE_DEBUG_F32 = 0, GANCE_DEBUG_F64 = 1, GANCE_DEBUG_I32 = 2 };
+/* pixel rectangle inside the panel and the data limits mapped onto it; rectangles of one call must not overlap */
+typedef struct gance_debug_axis {
+    int32_t x, y, width, height;
+    double x_min, x_max, y_min, y_max; /* finite, min != max */
+} gance_debug_axis;
+/* One mark. Sample i of a series is at x = x_start + i and reads data[(frame.number / frame_divisor) * frame_stride + i]
+ * (skipped when that index is outside [0, limit) or the value is not finite). POINTS: a filled square per sample
+ * (ax.scatter). POLYLINE: the samples joined (ax.plot; dash_on / dash_off in pixel columns, 0 = solid). CURSOR: a
+ * vertical line over the axis height at x = frame.cursor (axvline / vlines; no series). BAR: a horizontal bar from
+ * x = 0 to x = sample 0 over the middle half of the axis (barh). Drawn iff (frame.flags & flag_mask) == flag_value. */
+typedef struct gance_debug_mark {
+    int32_t kind, axis, dtype, count;
+    const void* data; /* device, aligned to its element */
+    int64_t limit, frame_stride;
+    int32_t frame_divisor, size; /* size: side of the square stamped per sample / line step, 1 .. 64 pixels */
+    int32_t dash_on, dash_off;
+    int32_t flag_mask, flag_value;
+    uint8_t rgba[4]; /* alpha 0 .. 255 */
+    int32_t reserved;
+    double x_start;
+} gance_debug_mark;
+typedef struct gance_debug_frame {
+    int64_t number; /* frame number (>= 0) the series rows are derived from */
+    double cursor;  /* x of CURSOR marks */
+    int32_t flags, reserved;
+} gance_debug_frame;
+/* image panels: frame b shows d_src[(first_number + b) / divisor - src_base] of [src_count][side][side][3] (device,
+ * 16-byte aligned): divisor 1 for the stream's own frames, frame_multiplier for reader.final_images / target_images */
+int gance_debug_place_panels_u8(const uint8_t* d_src, int32_t src_count, int32_t side, int64_t first_number, int32_t divisor,
+                                int64_t src_base, int32_t batch, uint8_t* d_out, int64_t out_frame_stride, int64_t out_row_stride,
+                                void* stream);
+/* plot panels: d_chrome [side][side][3] (device: the window's static template) copied to every frame, then `marks`
+ * (host, <= GANCE_DEBUG_MAX_MARKS) composited in table order on `axes` (host, <= GANCE_DEBUG_MAX_AXES) with the per-frame
+ * values of d_frames [batch] (device). The rasterisation rule is in DESIGN.md section 9 and gance_amd/csrc/debug_panels.hip. */
+int gance_debug_draw_panels_u8(const uint8_t* d_chrome, int32_t side, const gance_debug_axis* axes, int32_t num_axes,
+                               const gance_debug_mark* marks, int32_t num_marks, const gance_debug_frame* d_frames, int32_t batch,
+                               uint8_t* d_out, int64_t out_frame_stride, int64_t out_row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
