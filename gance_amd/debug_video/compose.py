@@ -18,7 +18,7 @@ from gance_amd.overlay.overlay_common import OverlayContext
 
 class DebugVideo(NamedTuple):
     """
-    The keyword-only `debug` argument of projection_file_blend_frame_chunks: what the debug stream looks like and who
+    The keyword-only `debug` argument of projection_file_blend_frame_chunks and noise_blend_frame_chunks: what the debug stream looks like and who
     receives it. `on_encoded(first_frame, EncodedFrames)` gets every chunk of JPEG-encoded debug frames in frame
     order; `on_composed(first_frame, frames [n, side, P * side, 3] uint8 in HBM)`, if given, sees the raw frames
     first (on the reader stream: copy what is to be kept).
@@ -39,7 +39,41 @@ class DebugSources(NamedTuple):
     limits: Dict[str, Tuple[float, float]]  # global min / max of "a", "b", "combined"
     labels: Dict[str, str]
     network_indices: ResultLayers  # host: the indices and the layer(s) they were quantised from
-    final_images: np.ndarray  # [F, s, s, 3] uint8: reader.final_images
+    final_images: Optional[np.ndarray] = None  # [F, s, s, 3] uint8: reader.final_images; None (noise-blend): no such panel
+
+
+class PanelLayout(NamedTuple):
+    """Where the panels of a debug frame sit, counted in panels from the left; None: the panel is not there."""
+
+    panel_count: int
+    foreground: Optional[int]
+    final_images: Optional[int]
+    synthesis: int
+    overlay: Optional[int]
+    mask: Optional[int]
+
+
+def panel_layout(final_images: bool, overlay: bool, mask: bool) -> PanelLayout:
+    """
+    The row of panels a debug frame is (pure host arithmetic): blended output, foreground (overlay on), final images (a
+    projection file's), synthesis inputs, overlay computation (overlay on), overlay binary mask (music mask on).
+    projection-file-blend has 3 / 5 / 6 of them, noise-blend (no final images, no overlay) 2.
+    """
+    order = ["output"] + ["foreground"] * overlay + ["final_images"] * final_images + ["synthesis"] + ["overlay"] * overlay + ["mask"] * mask
+    at = {name: order.index(name) if name in order else None for name in ("foreground", "final_images", "synthesis", "overlay", "mask")}
+    return PanelLayout(len(order), at["foreground"], at["final_images"], at["synthesis"], at["overlay"], at["mask"])
+
+
+def synthesis_panel_of(side: int, window: Optional[int], frame_multiplier: int, sources: DebugSources, combined: torch.Tensor) -> panels.SynthesisPanel:
+    """
+    The synthesis-inputs panel of a run (host tables only): input B advances once per `frame_multiplier` frames, and the
+    combined series is read `combined.stride(0)` elements apart: 18 L for latent matrices [N, 18, L] (their row 0), L for
+    z vectors [N, L].
+    """
+    return panels.SynthesisPanel(
+        side, int(sources.a_vectors.shape[1]), sources.limits, sources.labels, sources.network_indices, window, int(frame_multiplier),
+        combined_stride=int(combined.stride(0)),
+    )
 
 
 def validate_side_length(debug_side_length: Optional[int]) -> int:
@@ -94,8 +128,10 @@ class DebugVideoComposer:  # pylint: disable=too-many-instance-attributes
     """
     `push(first, frames, foreground)` takes each released chunk of the stream in frame order (tensors in HBM, on the
     current stream) and returns the composed debug chunks that are complete: [(first, [n, side, P * side, 3] uint8)].
-    Panels, each a square of `side`: blended output, foreground (overlay on), final images (each shown
-    `frame_multiplier` times), synthesis inputs, overlay computation (overlay on), overlay binary mask (music mask on).
+    Panels, each a square of `side` (panel_layout): blended output, foreground (overlay on), final images (each shown
+    `frame_multiplier` times; only where the sources have them), synthesis inputs, overlay computation (overlay on),
+    overlay binary mask (music mask on). `combined` is what the frames were synthesised from, [N, 18, L] latent matrices
+    or [N, L] z vectors: the synthesis panel reads row 0 / the vector of each frame, `combined.stride(0)` elements apart.
 
     Only the overlay panel can make a chunk wait: its y limits need every context of the frame's window
     (overlay_visualization.py:155-206), and the overlay stage evaluates contexts chunk by chunk (`add_contexts`). A
@@ -110,14 +146,11 @@ class DebugVideoComposer:  # pylint: disable=too-many-instance-attributes
     ) -> None:
         self.side, self.num_frames, self.multiplier, self.device = validate_side_length(side), num_frames, int(frame_multiplier), device
         self._sources = sources
-        vector_length = int(sources.a_vectors.shape[1])
-        self._synthesis = panels.SynthesisPanel(
-            self.side, vector_length, sources.limits, sources.labels, sources.network_indices, window, self.multiplier,
-            combined_stride=int(combined.stride(0)),
-        )
+        self._synthesis = synthesis_panel_of(self.side, window, self.multiplier, sources, combined)
         self._overlay = panels.OverlayPanel(self.side, window, *overlay_thresholds) if overlay_thresholds is not None else None
         self._mask = panels.MaskPanel(self.side, mask, window, mask_threshold) if mask is not None else None
-        self.panel_count = 3 + (2 if self._overlay is not None else 0) + (1 if self._mask is not None else 0)
+        self.layout = panel_layout(sources.final_images is not None, self._overlay is not None, self._mask is not None)
+        self.panel_count = self.layout.panel_count
         self.width = self.panel_count * self.side
         self._series = {"a": sources.a_vectors, "b": sources.b_vectors, "combined": combined}
         self._series.update({f"synthesis.{name}": _upload(values, device) for name, values in self._synthesis.host_series().items()})
@@ -189,19 +222,17 @@ class DebugVideoComposer:  # pylint: disable=too-many-instance-attributes
         """One released chunk in; every debug chunk that is complete out."""
         count = int(frames.shape[0])
         out = torch.empty((count, self.side, self.width, 3), dtype=torch.uint8, device=self.device)
-        panel = 0
-        self._place(out, panel, frames, first, 1, first)
+        self._place(out, 0, frames, first, 1, first)
         if self._overlay is not None:
             if foreground is None:
                 raise ValueError("the debug video of an overlay run needs the foreground frames")
-            panel += 1
-            self._place(out, panel, foreground, first, 1, first)
-        panel += 1
-        low, high = first // self.multiplier, (first + count - 1) // self.multiplier + 1
-        if high > len(self._sources.final_images):
-            raise ValueError("the projection file holds too few final images for the frames being written")
-        self._place(out, panel, _upload(self._sources.final_images[low:high], self.device), first, self.multiplier, low)
-        panel += 1
+            self._place(out, self.layout.foreground, foreground, first, 1, first)
+        if self.layout.final_images is not None:
+            low, high = first // self.multiplier, (first + count - 1) // self.multiplier + 1
+            if high > len(self._sources.final_images):
+                raise ValueError("the projection file holds too few final images for the frames being written")
+            self._place(out, self.layout.final_images, _upload(self._sources.final_images[low:high], self.device), first, self.multiplier, low)
+        panel = self.layout.synthesis
         series = {"a": self._series["a"], "b": self._series["b"], "combined": self._series["combined"], **self._prefixed("synthesis.")}
         for window_index, start, frames_in_run in self._runs(first, count, self._synthesis.width):
             self._draw(
@@ -209,7 +240,7 @@ class DebugVideoComposer:  # pylint: disable=too-many-instance-attributes
                 frames_in_run, self._synthesis.cursor, [0] * frames_in_run,
             )
         if self._mask is not None:
-            mask_panel = self.panel_count - 1
+            mask_panel = self.layout.mask
             for window_index, start, frames_in_run in self._runs(first, count, self._mask.width):
                 self._draw(
                     out[start - first :], mask_panel, "mask", window_index, self._mask.window(window_index), self._prefixed("mask."),
@@ -229,7 +260,7 @@ class DebugVideoComposer:  # pylint: disable=too-many-instance-attributes
                 needed = min(self.num_frames, ((first + count - 1) // width + 1) * width)
                 if len(self._contexts) < needed and not final:
                     break
-                panel = 3 + 1  # output, foreground, final images, synthesis inputs come first
+                panel = self.layout.overlay  # (output, foreground, final images if any, synthesis inputs come first)
                 for window_index, start, frames_in_run in self._runs(first, count, width):
                     contexts = self._contexts[window_index * width : (window_index + 1) * width]
                     window, host_series = self._overlay.window(window_index, contexts)

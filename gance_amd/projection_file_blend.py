@@ -32,7 +32,7 @@ import torch.distributed as dist
 from gance_amd import divisor, frame_sharding, hip_lib, torch_ops  # noqa: F401  (torch_ops registers torch.ops.gance.*)
 from gance_amd.data_into_network_visualization import visualization_inputs
 from gance_amd.data_into_network_visualization.visualization_common import DataLabel, ResultLayers
-from gance_amd.debug_video.compose import DebugSources, DebugVideo, DebugVideoComposer, validate_side_length
+from gance_amd.debug_video.compose import DebugSources, DebugVideo, DebugVideoComposer, panel_layout, validate_side_length
 from gance_amd.logger_common import LOGGER
 from gance_amd.network_interface.network_functions import TRUNCATION_PSI, MultiNetwork
 
@@ -100,6 +100,21 @@ def synthesize_device_frames(  # pylint: disable=too-many-locals
         yield frames
 
 
+def _seeded_noise(engine, seed: int, ids: np.ndarray, device: torch.device, stream: int) -> None:
+    """
+    The planes of (seed, layer, ids[b]) for sample b of the next engine call: a run of consecutive numbers by its first
+    one, anything else through an int64 id tensor in HBM (uploaded from pinned memory without blocking, like `members` below).
+    """
+    count = len(ids)
+    if count == 1 or bool(np.all(np.diff(ids) == 1)):
+        engine.randomize_noise(seed, count=count, first_sample=int(ids[0]), stream=stream)
+        return
+    d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64))
+    d_ids = (d_ids.pin_memory() if device.type == "cuda" else d_ids).to(device, non_blocking=True)
+    # (enqueued on the current stream, as the upload is: the caching allocator hands the block out again in that order only)
+    engine.randomize_noise(seed, count=count, d_sample_ids=d_ids.data_ptr(), stream=stream)
+
+
 def synthesize_device_frames_network_major(  # pylint: disable=too-many-locals
     dlatents: torch.Tensor,
     network_indices: torch.Tensor,
@@ -107,6 +122,8 @@ def synthesize_device_frames_network_major(  # pylint: disable=too-many-locals
     output_side_length: Optional[int] = None,
     batch: Optional[int] = None,
     out: Optional[torch.Tensor] = None,
+    noise_seed: Optional[int] = None,
+    sample_ids: Optional[np.ndarray] = None,
 ) -> torch.Tensor:
     """
     The same frames as `synthesize_device_frames`, as one tensor [n, S, S, 3] (`out`, if given), computed network by
@@ -114,6 +131,9 @@ def synthesize_device_frames_network_major(  # pylint: disable=too-many-locals
     sorts by network for the same reason, network_visualization.py:653-674: there a switch costs a
     process restart, here only a short batch). Frames land at their own positions, so the order of
     the result is the frame order.
+    :param noise_seed: (z vectors only) None (default): fresh noise planes per engine call, from an OS seed. An int: frame
+    i reads the planes of (noise_seed, layer, sample_ids[i]), whichever engine call it lands in.
+    :param sample_ids: the GLOBAL numbers of the frames, a host array [n] of integers; default: their positions 0 .. n - 1.
     """
     device = dlatents.device
     # (a host array is taken as it is: the stream hands slices of one host copy, not a device-to-host sync per window)
@@ -148,7 +168,10 @@ def synthesize_device_frames_network_major(  # pylint: disable=too-many-locals
             stream = torch.cuda.current_stream(device).cuda_stream
             if dlatents.dim() == 2:
                 # the reference's vector path draws fresh noise per call, a plane per layer and sample (upstream default)
-                engine.randomize_noise(count=count, stream=stream)
+                if noise_seed is None:
+                    engine.randomize_noise(count=count, stream=stream)
+                else:
+                    _seeded_noise(engine, int(noise_seed), host_members if sample_ids is None else sample_ids[host_members], device, stream)
                 selected = dlatents[first : first + count] if in_place else dlatents.index_select(0, members)
                 torch.ops.gance.synthesize_z_out(selected, engine.op_handle, TRUNCATION_PSI, native)
             else:
@@ -407,24 +430,37 @@ class _WindowSynthesizer:  # pylint: disable=too-few-public-methods
     the whole video (network_visualization.py:653-674), bounded to `window` pieces of HBM.
     """
 
-    def __init__(self, dlatents: torch.Tensor, indices: torch.Tensor, networks: MultiNetwork, side: int, frames_per_call: int, window: int) -> None:
+    def __init__(  # pylint: disable=too-many-arguments
+        self, dlatents: torch.Tensor, indices: torch.Tensor, networks: MultiNetwork, side: int, frames_per_call: int, window: int,
+        noise_seed: Optional[int] = None, sample_ids: Optional[np.ndarray] = None,
+    ) -> None:
+        """`noise_seed`, `sample_ids`: see synthesize_device_frames_network_major; the ids are the global numbers of ALL the rank's frames."""
         self._dlatents, self._indices, self._networks, self._side = dlatents, indices.cpu().numpy(), networks, side
         self._frames_per_call, self._window = frames_per_call, max(1, window)
         self._start, self._frames = 0, None
+        self._noise_seed = noise_seed
+        self._sample_ids = np.arange(int(dlatents.shape[0]), dtype=np.int64) if noise_seed is not None and sample_ids is None else sample_ids
+
+    def _noise(self, start: int, stop: int) -> dict:
+        if self._noise_seed is None:
+            return {}
+        return {"noise_seed": self._noise_seed, "sample_ids": self._sample_ids[start:stop]}
 
     writes_into = True  # (frame_sharding.ordered_device_chunks: the frames go straight into the stream's buffer)
 
     def __call__(self, offset: int, count: int, out: torch.Tensor) -> None:
         if self._window == 1:  # one network: every engine call writes its frames in place
             synthesize_device_frames_network_major(
-                self._dlatents[offset : offset + count], self._indices[offset : offset + count], self._networks, self._side, self._frames_per_call, out=out
+                self._dlatents[offset : offset + count], self._indices[offset : offset + count], self._networks, self._side, self._frames_per_call, out=out,
+                **self._noise(offset, offset + count),
             )
             return
         if self._frames is None or not self._start <= offset < self._start + int(self._frames.shape[0]):
             stop = min(int(self._dlatents.shape[0]), offset + self._window * self._frames_per_call)
             self._start = offset
             self._frames = synthesize_device_frames_network_major(
-                self._dlatents[offset:stop], self._indices[offset:stop], self._networks, self._side, self._frames_per_call
+                self._dlatents[offset:stop], self._indices[offset:stop], self._networks, self._side, self._frames_per_call,
+                **self._noise(offset, stop),
             )
         out.copy_(self._frames[offset - self._start : offset - self._start + count])
 
@@ -616,60 +652,10 @@ def encode_debug_into_ring(  # pylint: disable=too-many-arguments
         yield ring.push(first + start, data, offsets, side, reader_stream, width=width)
 
 
-def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements,too-many-branches
-    wav: List[str],
-    network_paths: List[Path],
-    frames_to_visualize: Optional[int],
-    output_fps: float,
-    output_side_length: int,
-    alpha: float,
-    fft_roll_enabled: bool,
-    fft_amplitude_range: Tuple[int, int],
-    projection_file_path: str,
-    blend_depth: int,
-    frames_per_call: int = DEFAULT_STREAM_BATCH,
-    overlay: Optional[OverlayParameters] = None,
-    networks: Optional[MultiNetwork] = None,
-    timings: Optional[Dict[str, object]] = None,
-    drain: str = "rank0",
-    on_total: Optional[Callable[[int], None]] = None,
-    jpeg_quality: Optional[int] = None,
-    *,
-    debug: Optional[DebugVideo] = None,
-) -> Iterator[Tuple[int, int, np.ndarray]]:
-    """
-    The frame stream of the reference's pipeline (gance/projection_file_blend.py:343 hands an iterator of frames to
-    the video writer): a generator of (first_frame_index, total_frames, frames [n, S, S, 3] uint8) in frame order.
-    Nothing holds all frames: per chunk, every rank synthesises `frames_per_call` frames, one gather lands the chunk
-    in order on rank 0 while the next chunk is already being synthesised, rank 0 runs the eye-tracking overlay on it
-    if `overlay` is given (in HBM; see _StreamingOverlay) and drains it to a pinned host ring (`frames` is a view of
-    a ring slot: consume or copy it before advancing the generator twice more). With several networks the engine
-    calls are batched by network across a window of pieces (_WindowSynthesizer).
-    Collective under `torch.distributed`: every rank must exhaust the generator; only rank 0 receives chunks. If a rank
-    fails, every rank leaves the generator with an exception (frame_sharding.exchange_status).
-    :param networks: networks already resident (not unloaded at the end); default: load `network_paths`, unload after.
-    :param timings: if given, rank 0 records the wall-clock split of the call there (milliseconds).
-    :param drain: "rank0" (default): the RCCL gather lands every chunk on rank 0, which alone receives chunks -- for
-    consumers of the ordered stream in one place (the overlay stage; an encoder fed by rank 0). "per-rank": no gather; EVERY
-    rank receives its own pieces (first_frame_index of the piece, total, frames) and drains them over its own PCIe link
-    into its own pinned ring -- for host-bound legs: at 2160^2 a frame is 14 MB, one link sustains ~57 GB/s pinned,
-    i.e. ~4 000 frames/s through rank 0 alone, less than four GPUs synthesise (DESIGN.md section 7). Not with `overlay`
-    (its run-length filter needs the ordered stream in one place).
-    :param on_total: called once on every rank with the total frame count as soon as it is known, rank 0 first and the
-    other ranks after rank 0's call has returned (so rank 0 can create an output file the others then open).
-    :param jpeg_quality: None (default): chunks of raw frames as above. 1..100: rank 0 encodes every released chunk (after
-    the overlay stage, if any) on the reader stream with torch.ops.gance.jpeg_encode, at most `frames_per_call` frames per
-    call, and drains only the offsets and the compressed bytes to a pinned host ring: the generator yields
-    (first_frame_index, total_frames, EncodedFrames) and raw frames never reach the host; timings["bytes_to_host"] counts
-    the compressed bytes. Needs drain="rank0" and an output side that is a multiple of 16.
-    :param debug: None (default): nothing changes. A DebugVideo: rank 0 also composes the debug frames of every released
-    chunk in HBM on the reader stream (gance_amd/debug_video/compose.py: output, foreground, final images, synthesis
-    inputs, overlay computation, overlay binary mask, side by side), encodes them with torch.ops.gance.jpeg_encode_rect at
-    `debug.jpeg_quality`, drains them through a second encoded ring and hands them to `debug.on_encoded` in frame order.
-    What the generator yields is unchanged. With the overlay on, composed debug frames wait in HBM until the contexts of
-    their window are complete: at most one debug window plus one chunk (timings["debug_frames_held_max"]). Needs
-    drain="rank0"; with `overlay`, `debug.window` must be given.
-    """
+def _check_stream_arguments(  # pylint: disable=too-many-arguments
+    drain: str, overlay: Optional[OverlayParameters], jpeg_quality: Optional[int], output_side_length: Optional[int], debug: Optional[DebugVideo]
+) -> None:
+    """The argument checks of a frame stream, before anything is loaded. :raises ValueError: see the generators' docstrings."""
     if drain not in frame_sharding.DRAIN_MODES:
         raise ValueError(f"drain must be one of {frame_sharding.DRAIN_MODES}, got {drain!r}")
     if drain == "per-rank" and overlay is not None:
@@ -689,6 +675,31 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
             raise ValueError("the debug video of an overlay run needs debug_window (frames per overlay context)")
         if not 1 <= int(debug.jpeg_quality) <= 100:
             raise ValueError(f"jpeg_quality must be in [1, 100], got {debug.jpeg_quality}")
+
+
+def _frame_stream(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements,too-many-branches
+    prepare: Callable[[MultiNetwork, torch.device], _BlendInputs],
+    network_paths: List[Path],
+    output_side_length: Optional[int],
+    frames_per_call: int,
+    overlay: Optional[OverlayParameters],
+    networks: Optional[MultiNetwork],
+    timings: Optional[Dict[str, object]],
+    drain: str,
+    on_total: Optional[Callable[[int], None]],
+    jpeg_quality: Optional[int],
+    debug: Optional[DebugVideo],
+    noise_seed: Optional[int] = None,
+) -> Iterator[Tuple[int, int, np.ndarray]]:
+    """
+    The frame stream both commands share, behind their argument checks: rank 0 prepares the per-frame network inputs
+    (`prepare(networks, device)` -> _BlendInputs: latent matrices [N, 18, L] or z vectors [N, L]), a failure there and in
+    `on_total` is relayed to every rank, then scatter, synthesis (by network across windows of pieces), the ordered chunks,
+    the overlay stage, the encode, the debug composer, the rings and the timings. See projection_file_blend_frame_chunks
+    for what it yields and for the life time of a yielded chunk.
+    :param noise_seed: (z vectors only) frame k of the run reads the noise planes of (noise_seed, layer, k), k its global
+    number, however the run is cut into calls, windows, networks and ranks; None: fresh planes per engine call.
+    """
     rank = dist.get_rank() if dist.is_initialized() else 0
     world_size = dist.get_world_size() if dist.is_initialized() else 1
     device = torch.device("cuda", torch.cuda.current_device())
@@ -700,10 +711,7 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
         failure = None
         if rank == 0:
             try:
-                inputs = _prepare_blend_inputs(
-                    wav, networks, frames_to_visualize, output_fps, alpha, fft_roll_enabled, fft_amplitude_range,
-                    projection_file_path, blend_depth, overlay is not None, device, timings, want_debug=debug is not None,
-                )
+                inputs = prepare(networks, device)
             except Exception as error:  # pylint: disable=broad-except
                 failure = error
         try:  # (a bad projection file or WAV on rank 0 must not leave the other ranks waiting in the broadcast below)
@@ -742,7 +750,12 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
         indices = frame_sharding.scatter_for_stream(inputs.indices, num_frames, frames_per_call, device)
         side = _common_output_side(networks, np.asarray(networks.network_indices), output_side_length)
         num_networks = len(set(networks.network_paths))
-        synthesize_piece = _WindowSynthesizer(dlatents, indices, networks, side, frames_per_call, 1 if num_networks == 1 else STREAM_WINDOW_PIECES_PER_NETWORK * num_networks)
+        # (with a noise seed a frame's planes follow its GLOBAL number: this rank's frames are those of its stream order)
+        sample_ids = np.asarray(frame_sharding.stream_order(num_frames, world_size, frames_per_call, rank), dtype=np.int64) if noise_seed is not None else None
+        synthesize_piece = _WindowSynthesizer(
+            dlatents, indices, networks, side, frames_per_call, 1 if num_networks == 1 else STREAM_WINDOW_PIECES_PER_NETWORK * num_networks,
+            noise_seed=noise_seed, sample_ids=sample_ids,
+        )
         stage = None
         mask_layers = None
         if overlay is not None and rank == 0:
@@ -859,6 +872,73 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
             networks.unload()
 
 
+def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,too-many-locals,too-many-statements,too-many-branches
+    wav: List[str],
+    network_paths: List[Path],
+    frames_to_visualize: Optional[int],
+    output_fps: float,
+    output_side_length: int,
+    alpha: float,
+    fft_roll_enabled: bool,
+    fft_amplitude_range: Tuple[int, int],
+    projection_file_path: str,
+    blend_depth: int,
+    frames_per_call: int = DEFAULT_STREAM_BATCH,
+    overlay: Optional[OverlayParameters] = None,
+    networks: Optional[MultiNetwork] = None,
+    timings: Optional[Dict[str, object]] = None,
+    drain: str = "rank0",
+    on_total: Optional[Callable[[int], None]] = None,
+    jpeg_quality: Optional[int] = None,
+    *,
+    debug: Optional[DebugVideo] = None,
+) -> Iterator[Tuple[int, int, np.ndarray]]:
+    """
+    The frame stream of the reference's pipeline (gance/projection_file_blend.py:343 hands an iterator of frames to
+    the video writer): a generator of (first_frame_index, total_frames, frames [n, S, S, 3] uint8) in frame order.
+    Nothing holds all frames: per chunk, every rank synthesises `frames_per_call` frames, one gather lands the chunk
+    in order on rank 0 while the next chunk is already being synthesised, rank 0 runs the eye-tracking overlay on it
+    if `overlay` is given (in HBM; see _StreamingOverlay) and drains it to a pinned host ring (`frames` is a view of
+    a ring slot: consume or copy it before advancing the generator twice more). With several networks the engine
+    calls are batched by network across a window of pieces (_WindowSynthesizer).
+    Collective under `torch.distributed`: every rank must exhaust the generator; only rank 0 receives chunks. If a rank
+    fails, every rank leaves the generator with an exception (frame_sharding.exchange_status).
+    :param networks: networks already resident (not unloaded at the end); default: load `network_paths`, unload after.
+    :param timings: if given, rank 0 records the wall-clock split of the call there (milliseconds).
+    :param drain: "rank0" (default): the RCCL gather lands every chunk on rank 0, which alone receives chunks -- for
+    consumers of the ordered stream in one place (the overlay stage; an encoder fed by rank 0). "per-rank": no gather; EVERY
+    rank receives its own pieces (first_frame_index of the piece, total, frames) and drains them over its own PCIe link
+    into its own pinned ring -- for host-bound legs: at 2160^2 a frame is 14 MB, one link sustains ~57 GB/s pinned,
+    i.e. ~4 000 frames/s through rank 0 alone, less than four GPUs synthesise (DESIGN.md section 7). Not with `overlay`
+    (its run-length filter needs the ordered stream in one place).
+    :param on_total: called once on every rank with the total frame count as soon as it is known, rank 0 first and the
+    other ranks after rank 0's call has returned (so rank 0 can create an output file the others then open).
+    :param jpeg_quality: None (default): chunks of raw frames as above. 1..100: rank 0 encodes every released chunk (after
+    the overlay stage, if any) on the reader stream with torch.ops.gance.jpeg_encode, at most `frames_per_call` frames per
+    call, and drains only the offsets and the compressed bytes to a pinned host ring: the generator yields
+    (first_frame_index, total_frames, EncodedFrames) and raw frames never reach the host; timings["bytes_to_host"] counts
+    the compressed bytes. Needs drain="rank0" and an output side that is a multiple of 16.
+    :param debug: None (default): nothing changes. A DebugVideo: rank 0 also composes the debug frames of every released
+    chunk in HBM on the reader stream (gance_amd/debug_video/compose.py: output, foreground, final images, synthesis
+    inputs, overlay computation, overlay binary mask, side by side), encodes them with torch.ops.gance.jpeg_encode_rect at
+    `debug.jpeg_quality`, drains them through a second encoded ring and hands them to `debug.on_encoded` in frame order.
+    What the generator yields is unchanged. With the overlay on, composed debug frames wait in HBM until the contexts of
+    their window are complete: at most one debug window plus one chunk (timings["debug_frames_held_max"]). Needs
+    drain="rank0"; with `overlay`, `debug.window` must be given.
+    """
+    _check_stream_arguments(drain, overlay, jpeg_quality, output_side_length, debug)
+
+    def prepare(resident: MultiNetwork, device: torch.device) -> _BlendInputs:
+        return _prepare_blend_inputs(
+            wav, resident, frames_to_visualize, output_fps, alpha, fft_roll_enabled, fft_amplitude_range,
+            projection_file_path, blend_depth, overlay is not None, device, timings, want_debug=debug is not None,
+        )
+
+    yield from _frame_stream(
+        prepare, network_paths, output_side_length, frames_per_call, overlay, networks, timings, drain, on_total, jpeg_quality, debug
+    )
+
+
 def projection_file_blend_frames(  # pylint: disable=too-many-arguments,too-many-locals
     wav: List[str],
     network_paths: List[Path],
@@ -895,6 +975,118 @@ def projection_file_blend_frames(  # pylint: disable=too-many-arguments,too-many
 def _npy_path(output_path: str) -> str:
     """`np.save` appends `.npy` when the suffix is missing: the streamed writer lands in the same file."""
     return output_path if output_path.endswith(".npy") else output_path + ".npy"
+
+
+def check_output_arguments(output_format: str, output_side_length: Optional[int], jpeg_quality: int, output_fps: float) -> bool:
+    """
+    The output checks both commands make before any device is touched; True: the output is a video.
+    :raises ValueError: an unknown output_format; "avi" with a side that is not a multiple of 16, a jpeg_quality outside
+    1..100 or a frame rate AVI cannot hold.
+    """
+    if output_format not in ("npy", "avi"):
+        raise ValueError(f"output_format must be \"npy\" or \"avi\", got {output_format!r}")
+    encode = output_format == "avi"
+    if encode:
+        # (output_side_length None: the networks' own side, checked by the stream once the networks are loaded)
+        if output_side_length is not None and int(output_side_length) % 16 != 0:
+            raise ValueError(f"the Motion-JPEG writer needs an output side that is a multiple of 16, got {output_side_length}")
+        if not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
+        mjpeg_avi.frame_rate_fraction(output_fps)  # (a rate AVI cannot hold is refused before any work)
+    return encode
+
+
+def check_debug_arguments(  # pylint: disable=too-many-arguments
+    debug_path: Optional[str], debug_side_length: Optional[int], debug_window: Optional[int], overlay_enabled: bool, jpeg_quality: int, output_fps: float
+) -> Optional[int]:
+    """
+    The debug-video checks both commands make before any device is touched; the side of its panels (None: no debug video).
+    :raises ValueError: `debug_path` without a valid `debug_side_length`, with the overlay on and no `debug_window`, with a
+    jpeg_quality outside 1..100 or a frame rate AVI cannot hold.
+    """
+    if debug_path is None:
+        return None
+    debug_side = validate_side_length(debug_side_length)
+    if overlay_enabled and debug_window is None:
+        raise ValueError("the debug video of an overlay run needs debug_window (frames per overlay context)")
+    if not 1 <= int(jpeg_quality) <= 100:
+        raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
+    mjpeg_avi.frame_rate_fraction(output_fps)
+    return debug_side
+
+
+def write_frame_stream(  # pylint: disable=too-many-arguments,too-many-locals
+    chunks_of: Callable[[Callable[[int], None], Optional[int], Optional[DebugVideo]], Iterator[Tuple[int, int, object]]],
+    wav: List[str],
+    output_path: Optional[str],
+    output_fps: float,
+    output_side_length: Optional[int],
+    debug_path: Optional[str],
+    debug_side: Optional[int],
+    debug_window: Optional[int],
+    debug_panels: int,
+    drain: str,
+    encode: bool,
+    jpeg_quality: int,
+) -> None:
+    """
+    Opens the outputs of a command and writes its frame stream into them, chunk by chunk: the `.npy` memory map or the
+    Motion-JPEG AVI at `output_path`, and the debug AVI of `debug_panels` square panels per frame at `debug_path`.
+    `chunks_of(on_total, jpeg_quality or None, debug)` is the command's generator (projection_file_blend_frame_chunks,
+    noise_blend_frame_chunks) with everything else bound.
+    """
+    # frame chunks go straight from the pinned ring into the (memory-mapped) output file: nothing holds the video
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    state: Dict[str, object] = {"writer": None, "total": 0}
+
+    def open_output(total: int) -> None:
+        # rank 0 creates the file (the frame side is known up front: every frame is resized to output_side_length); with
+        # drain="per-rank" the other ranks then map the same file and write their own pieces into it
+        state["total"] = total
+        if debug_path is not None and rank == 0:
+            state["debug_writer"] = mjpeg_avi.MjpegAviWriter(
+                debug_path, debug_side, output_fps, wavs=wav, width=debug_panels * debug_side, height=debug_side
+            )
+        if output_path is None or (rank != 0 and drain != "per-rank"):
+            return
+        if encode:
+            if output_side_length is not None:
+                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, output_side_length, output_fps, wavs=wav)
+            else:  # the side is the networks': the writer opens with the first chunk
+                mjpeg_avi.read_concatenated_wavs(wav)  # (mismatched WAVs are refused before synthesis starts)
+                state["avi_side_pending"] = True
+        elif rank == 0:
+            state["writer"] = np.lib.format.open_memmap(
+                _npy_path(output_path), mode="w+", dtype=np.uint8, shape=(total, output_side_length, output_side_length, 3)
+            )
+        elif total > 0:
+            state["writer"] = np.load(_npy_path(output_path), mmap_mode="r+")
+
+    def write_debug_frames(_first: int, encoded: EncodedFrames) -> None:  # (chunks arrive in frame order on rank 0)
+        for index in range(len(encoded)):
+            state["debug_writer"].add_frame(encoded.frame(index))
+
+    debug = DebugVideo(debug_side, debug_window, write_debug_frames, jpeg_quality=int(jpeg_quality)) if debug_path is not None else None
+    try:
+        for first, _total, frames in chunks_of(open_output, int(jpeg_quality) if encode else None, debug):
+            if encode and state.get("avi_side_pending") and state["writer"] is None:
+                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, frames.side, output_fps, wavs=wav)
+            if state["writer"] is None:
+                continue
+            if encode:  # (chunks arrive in frame order on rank 0)
+                for index in range(len(frames)):
+                    state["writer"].add_frame(frames.frame(index))
+            else:
+                state["writer"][first : first + len(frames)] = frames
+        if encode and state.get("avi_side_pending") and state["writer"] is None:  # no frames: an empty video
+            state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, 0, output_fps, wavs=wav)
+    finally:
+        if encode and state["writer"] is not None:
+            state["writer"].close()
+        if state.get("debug_writer") is not None:
+            state["debug_writer"].close()
+    if state["writer"] is not None and not encode:
+        state["writer"].flush()
 
 
 def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-locals
@@ -945,16 +1137,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     before any synthesis; with output_side_length None the networks' own side, checked once they are loaded); `debug_path`
     without a `debug_side_length` that is a multiple of 16, or with the overlay on and no `debug_window` (before any synthesis).
     """
-    if output_format not in ("npy", "avi"):
-        raise ValueError(f"output_format must be \"npy\" or \"avi\", got {output_format!r}")
-    encode = output_format == "avi"
-    if encode:
-        # (output_side_length None: the networks' own side, checked by the stream once the networks are loaded)
-        if output_side_length is not None and int(output_side_length) % 16 != 0:
-            raise ValueError(f"the Motion-JPEG writer needs an output side that is a multiple of 16, got {output_side_length}")
-        if not 1 <= int(jpeg_quality) <= 100:
-            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
-        mjpeg_avi.frame_rate_fraction(output_fps)  # (a rate AVI cannot hold is refused before any work)
+    encode = check_output_arguments(output_format, output_side_length, jpeg_quality, output_fps)
     drain = drain or os.environ.get("GANCE_STREAM_DRAIN", "rank0")
     overlay_enabled = all(param is not None for param in (phash_distance, bbox_distance, track_length))
     overlay_music_mask_enabled = all(
@@ -962,14 +1145,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     )
     if overlay_music_mask_enabled and not overlay_enabled:
         raise ValueError("Overlay music mask without overlay being enabled is not supported!")
-    debug_side = None
-    if debug_path is not None:
-        debug_side = validate_side_length(debug_side_length)
-        if overlay_enabled and debug_window is None:
-            raise ValueError("the debug video of an overlay run needs debug_window (frames per overlay context)")
-        if not 1 <= int(jpeg_quality) <= 100:
-            raise ValueError(f"jpeg_quality must be in [1, 100], got {jpeg_quality}")
-        mjpeg_avi.frame_rate_fraction(output_fps)
+    debug_side = check_debug_arguments(debug_path, debug_side_length, debug_window, overlay_enabled, jpeg_quality, output_fps)
     overlay = (
         OverlayParameters(
             phash_distance, bbox_distance, track_length, complexity_change_rolling_sum_window, complexity_change_threshold
@@ -979,60 +1155,15 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     )
     if overlay is not None or encode or debug_path is not None:
         drain = "rank0"
-    # frame chunks go straight from the pinned ring into the (memory-mapped) output file: nothing holds the video
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    state: Dict[str, object] = {"writer": None, "total": 0}
+    debug_panels = panel_layout(final_images=True, overlay=overlay_enabled, mask=overlay_music_mask_enabled).panel_count
 
-    def open_output(total: int) -> None:
-        # rank 0 creates the file (the frame side is known up front: every frame is resized to output_side_length); with
-        # drain="per-rank" the other ranks then map the same file and write their own pieces into it
-        state["total"] = total
-        if debug_path is not None and rank == 0:
-            debug_panels = 3 + (2 if overlay_enabled else 0) + (1 if overlay_music_mask_enabled else 0)
-            state["debug_writer"] = mjpeg_avi.MjpegAviWriter(
-                debug_path, debug_side, output_fps, wavs=wav, width=debug_panels * debug_side, height=debug_side
-            )
-        if output_path is None or (rank != 0 and drain != "per-rank"):
-            return
-        if encode:
-            if output_side_length is not None:
-                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, output_side_length, output_fps, wavs=wav)
-            else:  # the side is the networks': the writer opens with the first chunk
-                mjpeg_avi.read_concatenated_wavs(wav)  # (mismatched WAVs are refused before synthesis starts)
-                state["avi_side_pending"] = True
-        elif rank == 0:
-            state["writer"] = np.lib.format.open_memmap(
-                _npy_path(output_path), mode="w+", dtype=np.uint8, shape=(total, output_side_length, output_side_length, 3)
-            )
-        elif total > 0:
-            state["writer"] = np.load(_npy_path(output_path), mmap_mode="r+")
-
-    def write_debug_frames(_first: int, encoded: EncodedFrames) -> None:  # (chunks arrive in frame order on rank 0)
-        for index in range(len(encoded)):
-            state["debug_writer"].add_frame(encoded.frame(index))
-
-    debug = DebugVideo(debug_side, debug_window, write_debug_frames, jpeg_quality=int(jpeg_quality)) if debug_path is not None else None
-    try:
-        for first, _total, frames in projection_file_blend_frame_chunks(
+    def chunks_of(on_total, quality, debug):
+        return projection_file_blend_frame_chunks(
             wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled,
-            fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=open_output,
-            jpeg_quality=int(jpeg_quality) if encode else None, debug=debug,
-        ):
-            if encode and state.get("avi_side_pending") and state["writer"] is None:
-                state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, frames.side, output_fps, wavs=wav)
-            if state["writer"] is None:
-                continue
-            if encode:  # (chunks arrive in frame order on rank 0)
-                for index in range(len(frames)):
-                    state["writer"].add_frame(frames.frame(index))
-            else:
-                state["writer"][first : first + len(frames)] = frames
-        if encode and state.get("avi_side_pending") and state["writer"] is None:  # no frames: an empty video
-            state["writer"] = mjpeg_avi.MjpegAviWriter(output_path, 0, output_fps, wavs=wav)
-    finally:
-        if encode and state["writer"] is not None:
-            state["writer"].close()
-        if state.get("debug_writer") is not None:
-            state["debug_writer"].close()
-    if state["writer"] is not None and not encode:
-        state["writer"].flush()
+            fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=on_total,
+            jpeg_quality=quality, debug=debug,
+        )
+
+    write_frame_stream(
+        chunks_of, wav, output_path, output_fps, output_side_length, debug_path, debug_side, debug_window, debug_panels, drain, encode, int(jpeg_quality)
+    )
