@@ -235,6 +235,16 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
          ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
     ),
+    "gance_debug_scatter3d_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_debug_draw_scatter3d_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+         ctypes.c_void_p],
+    ),
     "gance_vec_rms_rolling_max": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p],
@@ -258,7 +268,7 @@ SIGNATURES = {
 # libgance_hip_prev.so) may lack them, and only a call of the missing entry fails there
 ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
-    "gance_debug_draw_panels_u8",
+    "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -877,6 +887,59 @@ def debug_draw_panels_device(  # pylint: disable=too-many-arguments
             d_chrome or None, side, axes_array, len(axes) if axes is not None else 1, marks_array,
             len(marks) if marks is not None else 1, d_frames or None, batch, d_out or None, out_frame_stride, out_row_stride,
             stream or None,
+        ),
+    )
+
+
+class DebugView3d(ctypes.Structure):
+    """`gance_debug_view3d` of include/gance_hip.h: the rectangle, limits, view vectors, sizes and marker of the 3-D view."""
+
+    _fields_ = [
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("x_min", ctypes.c_double), ("x_max", ctypes.c_double), ("y_min", ctypes.c_double), ("y_max", ctypes.c_double),
+        ("z_min", ctypes.c_double), ("z_max", ctypes.c_double), ("c_min", ctypes.c_double), ("c_max", ctypes.c_double),
+        ("right", ctypes.c_double * 3), ("up", ctypes.c_double * 3), ("toward", ctypes.c_double * 3),
+        ("point_size", ctypes.c_int32), ("marker_size", ctypes.c_int32), ("marker_rgb", ctypes.c_uint8 * 3), ("reserved0", ctypes.c_uint8),
+        ("reserved1", ctypes.c_int32), ("marker_x", ctypes.c_double), ("marker_z", ctypes.c_double),
+    ]
+
+
+def debug_scatter3d_device(  # pylint: disable=too-many-arguments
+    d_chrome: int, side: int, view: Optional[DebugView3d], d_values: int, dtype: int, num_vectors: int, vector_length: int,
+    vector_stride: int, d_lut: int, d_keys: int, d_template: int, stream: int = 0,
+) -> None:
+    """
+    The template of a run's 3-D view: the chrome [side][side][3] (HBM) with the cloud of the values on top ([num_vectors]
+    vectors of `vector_length`, `vector_stride` elements apart, DEBUG_DTYPES float32 or float64), coloured through the
+    LUT [256][3], into d_template; d_keys is a workspace of side * side int64. Asynchronous on `stream`; see
+    include/gance_hip.h.
+    :raises ValueError: a missing pointer, a bad side, alignment, rectangle, limits, view vector, size, dtype or count.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_debug_scatter3d_u8(
+            d_chrome or None, side, ctypes.byref(view) if view is not None else None, d_values or None, dtype, num_vectors, vector_length,
+            vector_stride, d_lut or None, d_keys or None, d_template or None, stream or None,
+        ),
+    )
+
+
+def debug_draw_scatter3d_device(  # pylint: disable=too-many-arguments
+    d_template: int, side: int, view: Optional[DebugView3d], d_frames: int, batch: int, d_out: int, out_frame_stride: int,
+    out_row_stride: int, stream: int = 0,
+) -> None:
+    """
+    The 3-D panel of `batch` debug frames: the template copied to every frame, the marker stamped at y = the cursor of the
+    frame's record (DEBUG_FRAME_DTYPE [batch] in HBM). Output addressing as `debug_draw_panels_device`. Asynchronous.
+    :raises ValueError: a missing pointer, bad sizes, strides or alignment, or a view the library refuses.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_debug_draw_scatter3d_u8(
+            d_template or None, side, ctypes.byref(view) if view is not None else None, d_frames or None, batch, d_out or None,
+            out_frame_stride, out_row_stride, stream or None,
         ),
     )
 

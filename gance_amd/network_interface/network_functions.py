@@ -87,6 +87,11 @@ class LoadedNetwork:
         """`network.input_shape[1]` (network_functions.py:191)."""
         return self.engine.vector_length
 
+    @property
+    def resolution(self) -> int:
+        """Side of the images the network makes."""
+        return self.engine.resolution
+
     def create_images_vector(self, data: np.ndarray, randomize_noise: bool = True, noise_seed: Optional[int] = None) -> np.ndarray:
         """
         z (B, L) -> uint8 (B, H, W, 3): mapping, truncation psi = 1.2, synthesis (network_functions.py:144-158).
@@ -204,6 +209,12 @@ class MultiNetwork:
     def expected_vector_length(self: "MultiNetwork") -> int:
         """Vector length reported by the first network (network_functions.py:609-614)."""
         return self._expected_vector_length
+
+    @property  # type: ignore
+    @_raise_exception_if_unloaded
+    def resolution(self: "MultiNetwork") -> int:
+        """Side of the first network's images: the default height of `vector_synthesis`'s visualisation."""
+        return int(self._network_at(0).resolution)
 
     def __enter__(self: "MultiNetwork") -> Optional["MultiNetwork"]:
         """Load; `None` if the networks cannot be loaded onto the GPU (network_functions.py:516-529)."""

@@ -433,6 +433,37 @@ int gance_debug_place_panels_u8(const uint8_t* d_src, int32_t src_count, int32_t
 int gance_debug_draw_panels_u8(const uint8_t* d_chrome, int32_t side, const gance_debug_axis* axes, int32_t num_axes,
                                const gance_debug_mark* marks, int32_t num_marks, const gance_debug_frame* d_frames, int32_t batch,
                                uint8_t* d_out, int64_t out_frame_stride, int64_t out_row_stride, void* stream);
+/* The 3-D view of the synthesis inputs (plot_vectors_3d / draw_y_point of gance/data_into_network_visualization/vectors_3d.py,
+ * network_visualization.py:133-142, 269-285): every element of every input vector of the run as a point (x = sample
+ * number, y = vector number, z = value) coloured by its value, and a marker that moves along y. The rasterisation rule is
+ * in DESIGN.md section 9 item 8 and gance_amd/csrc/scatter3d.hip. The view is orthographic: u_k = (p_k - lo_k) /
+ * (hi_k - lo_k) - 0.5, then the dot products with `right` (to the right on the panel), `up` and `toward` (towards the
+ * viewer: nearer points hide farther ones). All limits finite with min != max; no view vector all zero. */
+typedef struct gance_debug_view3d {
+    int32_t x, y, width, height; /* pixel rectangle inside the panel the projected unit cube is fitted to */
+    double x_min, x_max, y_min, y_max, z_min, z_max;
+    double c_min, c_max; /* the values mapped onto LUT entries 0 .. 255 */
+    double right[3], up[3], toward[3];
+    int32_t point_size, marker_size; /* side of the square stamped per point / for the marker, 1 .. 64 pixels */
+    uint8_t marker_rgb[3];
+    uint8_t reserved0;
+    int32_t reserved1;
+    double marker_x, marker_z; /* the marker of a frame sits at (marker_x, frame.cursor, marker_z) */
+} gance_debug_view3d;
+/* the template of a run: d_chrome [side][side][3] (device) with the cloud on top, into d_template [side][side][3] (both
+ * 16-byte aligned). Point (n, i) reads d_values[n * vector_stride + i] (device, GANCE_DEBUG_F32 or GANCE_DEBUG_F64,
+ * vector_stride >= vector_length in elements: 18 L reads row 0 of [N][18][L]); a value that is not finite is not drawn.
+ * At every pixel the point with the largest (depth level, n * vector_length + i) shows, as d_lut[c] ([256][3], device).
+ * d_keys: a workspace of side * side 64-bit words (device), zeroed here. num_vectors * vector_length in [1, 2^40).
+ * Asynchronous on `stream`, no host synchronisation; the bytes are a pure function of the arguments. */
+int gance_debug_scatter3d_u8(const uint8_t* d_chrome, int32_t side, const gance_debug_view3d* view, const void* d_values, int32_t dtype,
+                             int64_t num_vectors, int64_t vector_length, int64_t vector_stride, const uint8_t* d_lut, uint64_t* d_keys,
+                             uint8_t* d_template, void* stream);
+/* one panel of `batch` consecutive frames (d_out and the strides as above): d_template copied to every frame with the
+ * marker at y = d_frames[b].cursor stamped on top in marker_rgb, opaque, clipped to the rectangle (not drawn where the
+ * cursor is not finite) */
+int gance_debug_draw_scatter3d_u8(const uint8_t* d_template, int32_t side, const gance_debug_view3d* view, const gance_debug_frame* d_frames,
+                                  int32_t batch, uint8_t* d_out, int64_t out_frame_stride, int64_t out_row_stride, void* stream);
 
 #ifdef __cplusplus
 }
