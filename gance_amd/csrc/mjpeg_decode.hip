@@ -1,0 +1,811 @@
+// Baseline JPEG decoder for frames in HBM: gance_jpeg_parse_header / gance_jpeg_decode_bounds / gance_jpeg_decode_u8 of
+// include/gance_hip.h, the reverse of mjpeg.hip. Input: baseline sequential JFIF (SOF0, 8 bit), three components sampled
+// 2x1 / 1x1 / 1x1 (4:2:2) in one interleaved scan, any 8-bit DQT, any DHT or none (then the Annex K tables), any DRI or
+// none, width and height in [1, 8192]. Output: uint8 [batch][height][width][3] RGB, equal to libjpeg's default decode:
+//
+//   entropy decode      jdhuff.c decode_mcu: DC difference and AC run/size symbols with EXTEND; 0xFF 0x00 reads as 0xFF; the
+//                       DC predictors restart with every restart segment
+//   dequantise + IDCT   jidctint.c jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, columns then rows, the sample saturated
+//                       to 0..255 as libjpeg-turbo's SIMD islow does (jidctint-sse2 / -avx2 / -neon pack with saturation;
+//                       the C fallback's range-limit table wraps past +-512 instead: see DESIGN.md section 9 item 9)
+//   chroma upsampling   jdsample.c h2v1_fancy_upsample over the true downsampled width ceil(W / 2)
+//   colour              jdcolor.c ycc_rgb_convert: 16-bit fixed point, arithmetic shifts, clamped
+//
+// Four launches on the caller's stream, no atomics on pixels, every frame independent of the others:
+//   1. mjpeg_marker_scan_kernel   one workgroup per frame: the RSTn markers of its entropy-coded data compacted in order
+//                                 into marker positions, the end of the data (EOI), and the frame's status when the
+//                                 marker count or sequence is wrong (such a frame is not decoded)
+//   2. mjpeg_entropy_kernel       one thread per restart segment: Huffman decode through a 9-bit look-ahead table in LDS
+//                                 (longer codes by the canonical maxcode walk), int16 coefficients in natural order staged
+//                                 in a private LDS slot and written as whole 128-byte blocks
+//   3. mjpeg_idct_kernel          one thread per 8x8 block: dequantise, IDCT, range limit -> Y, Cb, Cr planes
+//   4. mjpeg_colour_kernel        one thread per 16 pixels of a row: chroma upsampling across block edges, colour, RGB
+// Bounds: every read of compressed bytes lies inside the frame's scan range [scan_begin, scan_begin + scan_bytes), every
+// coefficient index is below 64, a segment decodes at most its own MCUs, and a code that is not in the table ends the
+// segment. The Huffman look-up tables are built on the host once per distinct set of tables of a call.
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/gance_hip.h"
+#include "kernels.h"
+#include "mjpeg_tables.h"
+
+namespace gance_mjpeg_decode {
+
+using gance_mjpeg::natural_of_zigzag;
+
+constexpr int kMaxSide = 8192;
+constexpr int kLookBits = 9;
+constexpr int kScanThreads = 256;
+constexpr int kScanChunk = 16;  // bytes per thread and tile of the marker scan
+constexpr int kEntropyThreads = 64;
+
+// Decoder view of one Huffman table (jdhuff.c jpeg_make_d_derived_tbl)
+struct DeviceTable {
+    uint16_t fast[1 << kLookBits];  // by the next 9 bits: (code length << 8) | symbol; 0 = a longer code, or none
+    int32_t maxcode[17];            // [l] the largest code of length l, -1 = no code of that length
+    int32_t valoff[17];             // code c of length l is values[valoff[l] + c]
+    uint8_t values[256];
+};
+struct alignas(16) TableSet {
+    DeviceTable huff[3][2];  // [component][0 = DC, 1 = AC]
+    uint16_t quant[3][64];   // natural order
+};
+struct alignas(16) FrameDesc {
+    int64_t scan_begin;  // of the entropy-coded data inside d_data
+    int32_t scan_bytes;
+    int32_t restart_interval;
+    int32_t segments;     // ceil(MCUs / restart_interval), 1 without restart markers
+    int32_t marker_base;  // of this frame's segments - 1 entries of marker_pos
+    int32_t table_set;
+    int32_t reserved;
+};
+
+// ---- sizes -------------------------------------------------------------------------------------------------------
+struct Layout {
+    int64_t mcu_cols, mcu_rows, mcus;  // per frame; an MCU is 16 x 8 pixels: Y left, Y right, Cb, Cr
+    int64_t luma_width, chroma_width, plane_rows;
+    int64_t params_bytes, marker_bytes, end_bytes, coef_bytes, luma_bytes, chroma_bytes, workspace_bytes;
+    int64_t max_markers;
+};
+
+static int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
+
+static Layout layout_of(int64_t batch, int64_t width, int64_t height) {
+    Layout l{};
+    l.mcu_cols = (width + 15) / 16;
+    l.mcu_rows = (height + 7) / 8;
+    l.mcus = l.mcu_cols * l.mcu_rows;
+    l.luma_width = l.mcu_cols * 16;
+    l.chroma_width = l.mcu_cols * 8;
+    l.plane_rows = l.mcu_rows * 8;
+    l.max_markers = batch * (l.mcus - 1);  // a restart interval of one MCU
+    l.params_bytes = round16(batch * (int64_t)sizeof(FrameDesc)) + batch * (int64_t)sizeof(TableSet);
+    l.marker_bytes = round16(l.max_markers * 4);
+    l.end_bytes = round16(batch * 4);
+    l.coef_bytes = batch * l.mcus * 4 * 64 * 2;
+    l.luma_bytes = batch * l.plane_rows * l.luma_width;
+    l.chroma_bytes = batch * l.plane_rows * l.chroma_width;
+    l.workspace_bytes = l.params_bytes + l.marker_bytes + l.end_bytes + l.coef_bytes + l.luma_bytes + 2 * l.chroma_bytes;
+    return l;
+}
+
+// ---- 1. marker scan ----------------------------------------------------------------------------------------------
+template <typename T>
+__device__ T block_exclusive_scan(T value, T* scratch, T* total) {
+    const int tid = threadIdx.x;
+    scratch[tid] = value;
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        const T add = tid >= d ? scratch[tid - d] : 0;
+        __syncthreads();
+        scratch[tid] += add;
+        __syncthreads();
+    }
+    const T inclusive = scratch[tid];
+    *total = scratch[kScanThreads - 1];
+    __syncthreads();
+    return inclusive - value;
+}
+
+// One workgroup per frame. Inside entropy-coded data 0xFF is followed by 0x00 (a stuffed data byte), 0xFF (fill), 0xD0..0xD7
+// (RSTn) or another marker, which ends the data (EOI). marker_pos receives the positions of the first segments - 1 RSTn
+// in order, scan_end the end of the data, or -1 for a frame that is not decoded; status the reason.
+__global__ void __launch_bounds__(kScanThreads) mjpeg_marker_scan_kernel(const uint8_t* __restrict__ data, const FrameDesc* __restrict__ frames,
+                                                                         int32_t* __restrict__ marker_pos, int32_t* __restrict__ scan_end,
+                                                                         int32_t* __restrict__ status) {
+    __shared__ int scratch[kScanThreads];
+    __shared__ int s_end, s_bad;
+    const int frame = blockIdx.x, tid = threadIdx.x;
+    const FrameDesc f = frames[frame];
+    const uint8_t* scan = data + f.scan_begin;
+    const int n = f.scan_bytes, expected = f.segments - 1;
+    if (tid == 0) s_end = n, s_bad = 0;
+    __syncthreads();
+    int carry = 0;
+    for (int base = 0; base < n; base += kScanThreads * kScanChunk) {
+        const int p0 = base + tid * kScanChunk;
+        uint8_t b[kScanChunk + 1];
+        if (p0 + kScanChunk + 1 <= n) {
+#pragma unroll
+            for (int i = 0; i < kScanChunk / 4; ++i) {
+                uint32_t w;
+                __builtin_memcpy(&w, scan + p0 + 4 * i, 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[4 * i + j] = (uint8_t)(w >> (8 * j));
+            }
+            b[kScanChunk] = scan[p0 + kScanChunk];
+        } else {
+#pragma unroll
+            for (int j = 0; j <= kScanChunk; ++j) b[j] = p0 + j < n ? scan[p0 + j] : 0;
+        }
+        int count = 0, end = n;
+        uint32_t restarts = 0;
+#pragma unroll
+        for (int j = 0; j < kScanChunk; ++j) {
+            const int v = b[j + 1];  // 0 past the end: a last byte 0xFF is no marker
+            if (b[j] != 0xFF || v == 0 || v == 0xFF) continue;
+            if (v >= 0xD0 && v <= 0xD7) restarts |= 1u << j, ++count;
+            else end = min(end, p0 + j);
+        }
+        if (!__syncthreads_or(count | (end < n))) continue;
+        int sum;
+        int index = carry + block_exclusive_scan(count, scratch, &sum);
+#pragma unroll
+        for (int j = 0; j < kScanChunk; ++j) {
+            if (!(restarts >> j & 1)) continue;
+            if (index < expected) {
+                marker_pos[f.marker_base + index] = p0 + j;
+                if (b[j + 1] != 0xD0 + (index & 7)) s_bad = 1;
+            }
+            ++index;
+        }
+        if (end < n) atomicMin(&s_end, end);
+        carry += sum;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int reason = GANCE_JPEG_OK;
+        // fewer markers than the picture needs and no EOI: the data stops before the picture does
+        if (carry != expected) reason = (carry < expected && s_end == n) ? GANCE_JPEG_TRUNCATED : GANCE_JPEG_MARKER_MISMATCH;
+        else if (s_bad) reason = GANCE_JPEG_MARKER_MISMATCH;
+        status[frame] = reason;
+        scan_end[frame] = reason == GANCE_JPEG_OK ? s_end : -1;
+    }
+}
+
+// ---- 2. entropy decode ---------------------------------------------------------------------------------------------
+// Bits of one restart segment [pos, end) of `p`, MSB first in `acc`. Past the end zero bits are appended and counted in
+// `pad`: the segment was cut short iff more bits were taken than it held (bits < pad).
+struct BitReader {
+    const uint8_t* p;
+    int pos, end;
+    uint64_t acc = 0;
+    int bits = 0, pad = 0;
+    __device__ BitReader(const uint8_t* data, int first, int last) : p(data), pos(first), end(last) {}
+    // at least 32 bits afterwards (call with bits <= 32)
+    __device__ __forceinline__ void refill() {
+        if (pos + 4 <= end) {
+            uint32_t w;
+            __builtin_memcpy(&w, p + pos, 4);
+            const uint32_t inverted = ~w;
+            if (((inverted - 0x01010101u) & ~inverted & 0x80808080u) == 0) {  // no byte is 0xFF
+                acc |= (uint64_t)__builtin_bswap32(w) << (32 - bits);
+                bits += 32;
+                pos += 4;
+                return;
+            }
+        }
+        while (bits <= 56) {
+            uint32_t b = 0;
+            if (pos < end) {
+                b = p[pos];
+                if (b != 0xFF) ++pos;
+                else if (pos + 1 < end && p[pos + 1] == 0) pos += 2;
+                else pos = end, b = 0, pad += 8;  // fill bytes or a cut stuffing pair: nothing more to read
+            } else {
+                pad += 8;
+            }
+            acc |= (uint64_t)b << (56 - bits);
+            bits += 8;
+        }
+    }
+    __device__ __forceinline__ uint32_t peek(int n) const { return (uint32_t)(acc >> (64 - n)); }  // 1 <= n <= 32
+    __device__ __forceinline__ void skip(int n) { acc <<= n, bits -= n; }
+    __device__ __forceinline__ bool overrun() const { return bits < pad; }
+};
+
+// The next symbol (with at least 16 bits in the reader), or -1 for a code that is not in the table
+__device__ __forceinline__ int decode_symbol(BitReader& reader, const uint16_t* __restrict__ fast, const DeviceTable& table) {
+    const uint32_t entry = fast[reader.peek(kLookBits)];
+    if (entry != 0) {
+        reader.skip((int)(entry >> 8));
+        return (int)(entry & 0xFF);
+    }
+    const int code16 = (int)reader.peek(16);
+    for (int length = kLookBits + 1; length <= 16; ++length) {
+        const int code = code16 >> (16 - length);
+        if (code <= table.maxcode[length]) {
+            const int index = table.valoff[length] + code;
+            if (index < 0 || index > 255) return -1;
+            reader.skip(length);
+            return table.values[index];
+        }
+    }
+    return -1;
+}
+
+// jdhuff.c HUFF_EXTEND: the `size`-bit field `value` as a signed coefficient
+__device__ __forceinline__ int extend(int value, int size) { return value < (1 << (size - 1)) ? value - (1 << size) + 1 : value; }
+
+// grid (ceil(max segments / 64), batch), one wave per workgroup. coef: [frame][mcu][4][64] int16, natural order.
+__global__ void __launch_bounds__(kEntropyThreads) mjpeg_entropy_kernel(const uint8_t* __restrict__ data, const FrameDesc* __restrict__ frames,
+                                                                        const TableSet* __restrict__ sets, const int32_t* __restrict__ marker_pos,
+                                                                        const int32_t* __restrict__ scan_end, int32_t* __restrict__ status,
+                                                                        int16_t* __restrict__ coef, int mcus) {
+    __shared__ uint16_t fast[6][1 << kLookBits];
+    __shared__ uint32_t slots[32 * kEntropyThreads];  // word w of thread t's block at [w * 64 + t]: no bank conflicts
+    __shared__ uint8_t natural[64];
+    const int frame = blockIdx.y, tid = threadIdx.x;
+    const FrameDesc f = frames[frame];
+    const int frame_end = scan_end[frame];
+    if ((int)blockIdx.x * kEntropyThreads >= f.segments || frame_end < 0) return;
+    const TableSet& set = sets[f.table_set];
+    for (int i = tid; i < 6 * 256; i += kEntropyThreads) {
+        const int t = i >> 8;
+        ((uint32_t*)fast[t])[i & 255] = ((const uint32_t*)set.huff[t >> 1][t & 1].fast)[i & 255];
+    }
+    for (int i = tid; i < 32 * kEntropyThreads; i += kEntropyThreads) slots[i] = 0;
+    natural[tid] = (uint8_t)natural_of_zigzag(tid);
+    __syncthreads();
+    const int segment = blockIdx.x * kEntropyThreads + tid;
+    if (segment >= f.segments) return;
+
+    const int* markers = marker_pos + f.marker_base;
+    int last = segment == f.segments - 1 ? frame_end : markers[segment];
+    int first = segment == 0 ? 0 : markers[segment - 1] + 2;
+    last = max(0, min(last, f.scan_bytes));
+    first = max(0, min(first, last));
+    const int mcu_begin = f.restart_interval > 0 ? segment * f.restart_interval : 0;
+    const int mcu_end = f.restart_interval > 0 ? min(mcus, mcu_begin + f.restart_interval) : mcus;
+
+    BitReader reader(data + f.scan_begin, first, last);
+    int16_t* slot = (int16_t*)slots;
+    int predictor[3] = {0, 0, 0};
+    int reason = GANCE_JPEG_OK;
+    for (int mcu = mcu_begin; mcu < mcu_end && reason == GANCE_JPEG_OK; ++mcu) {
+        for (int kind = 0; kind < 4 && reason == GANCE_JPEG_OK; ++kind) {
+            const int c = kind < 2 ? 0 : kind - 1;
+            if (reader.bits <= 32) reader.refill();
+            int symbol = decode_symbol(reader, fast[2 * c], set.huff[c][0]);
+            if (symbol < 0 || symbol > 15) {
+                reason = GANCE_JPEG_INVALID_CODE;
+                break;
+            }
+            if (symbol > 0) {
+                const int value = (int)reader.peek(symbol);
+                reader.skip(symbol);
+                predictor[c] += extend(value, symbol);
+            }
+            slot[tid * 2] = (int16_t)predictor[c];
+            for (int k = 1; k < 64;) {
+                if (reader.bits <= 32) reader.refill();
+                symbol = decode_symbol(reader, fast[2 * c + 1], set.huff[c][1]);
+                if (symbol < 0) {
+                    reason = GANCE_JPEG_INVALID_CODE;
+                    break;
+                }
+                const int run = symbol >> 4, size = symbol & 15;
+                if (size == 0) {
+                    if (run != 15) break;  // end of block
+                    k += 16;
+                    continue;
+                }
+                k += run;
+                if (k > 63) {
+                    reason = GANCE_JPEG_INVALID_CODE;
+                    break;
+                }
+                const int value = extend((int)reader.peek(size), size);
+                reader.skip(size);
+                const int n = natural[k];
+                slot[((n >> 1) * kEntropyThreads + tid) * 2 + (n & 1)] = (int16_t)value;
+                ++k;
+            }
+            if (reason == GANCE_JPEG_OK && reader.overrun()) reason = GANCE_JPEG_TRUNCATED;
+            uint4* dst = (uint4*)(coef + (((int64_t)frame * mcus + mcu) * 4 + kind) * 64);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                uint32_t* w = slots + 4 * i * kEntropyThreads + tid;
+                dst[i] = make_uint4(w[0], w[kEntropyThreads], w[2 * kEntropyThreads], w[3 * kEntropyThreads]);
+                w[0] = w[kEntropyThreads] = w[2 * kEntropyThreads] = w[3 * kEntropyThreads] = 0;
+            }
+        }
+    }
+    if (reason != GANCE_JPEG_OK) atomicMax(status + frame, reason);
+}
+
+// ---- 3. dequantisation and IDCT ------------------------------------------------------------------------------------
+constexpr int kConstBits = 13, kPass1Bits = 2;
+constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
+              FIX_0_899976223 = 7373, FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137,
+              FIX_1_961570560 = 16069, FIX_2_053119869 = 16819, FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// jpeg_idct_islow on one column / row: 8 values at stride `step`, descaled by `shift`
+template <int shift>
+__device__ __forceinline__ void idct_1d(int* d, int step) {
+    int z2 = d[2 * step], z3 = d[6 * step];
+    int z1 = (z2 + z3) * FIX_0_541196100;
+    int tmp2 = z1 + z3 * -FIX_1_847759065;
+    int tmp3 = z1 + z2 * FIX_0_765366865;
+    z2 = d[0 * step], z3 = d[4 * step];
+    int tmp0 = (z2 + z3) * (1 << kConstBits), tmp1 = (z2 - z3) * (1 << kConstBits);
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = d[7 * step], tmp1 = d[5 * step], tmp2 = d[3 * step], tmp3 = d[1 * step];
+    z1 = tmp0 + tmp3, z2 = tmp1 + tmp2, z3 = tmp0 + tmp2;
+    int z4 = tmp1 + tmp3;
+    const int z5 = (z3 + z4) * FIX_1_175875602;
+    tmp0 *= FIX_0_298631336, tmp1 *= FIX_2_053119869, tmp2 *= FIX_3_072711026, tmp3 *= FIX_1_501321110;
+    z1 *= -FIX_0_899976223, z2 *= -FIX_2_562915447;
+    z3 = z3 * -FIX_1_961570560 + z5;
+    z4 = z4 * -FIX_0_390180644 + z5;
+    tmp0 += z1 + z3, tmp1 += z2 + z4, tmp2 += z2 + z3, tmp3 += z1 + z4;
+    d[0 * step] = descale(tmp10 + tmp3, shift), d[7 * step] = descale(tmp10 - tmp3, shift);
+    d[1 * step] = descale(tmp11 + tmp2, shift), d[6 * step] = descale(tmp11 - tmp2, shift);
+    d[2 * step] = descale(tmp12 + tmp1, shift), d[5 * step] = descale(tmp12 - tmp1, shift);
+    d[3 * step] = descale(tmp13 + tmp0, shift), d[4 * step] = descale(tmp13 - tmp0, shift);
+}
+
+// The level shift and saturation of libjpeg-turbo's SIMD islow IDCT (signed saturating packs, then + 128). The C
+// fallback's sample_range_limit[value & 0x3FF] gives the same for |value| < 512 and wraps beyond; the decoders PIL
+// ships run the SIMD path.
+__host__ __device__ __forceinline__ uint32_t range_limit(int value) { return (uint32_t)min(255, max(0, value + 128)); }
+
+// One thread per block, numbered kind-major inside a frame so that a wave works on one component's table and plane.
+__global__ void __launch_bounds__(256) mjpeg_idct_kernel(const int16_t* __restrict__ coef, const FrameDesc* __restrict__ frames,
+                                                         const TableSet* __restrict__ sets, int mcus, int mcu_cols, int64_t blocks,
+                                                         uint8_t* __restrict__ luma, uint8_t* __restrict__ chroma_b, uint8_t* __restrict__ chroma_r) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= blocks) return;
+    const int64_t frame = t / (4 * (int64_t)mcus);
+    const int within = (int)(t - frame * 4 * mcus);
+    const int kind = within / mcus, mcu = within - kind * mcus;
+    const int c = kind < 2 ? 0 : kind - 1;
+    const uint16_t* quant = sets[frames[frame].table_set].quant[c];
+    const uint4* src = (const uint4*)(coef + ((frame * mcus + mcu) * 4 + kind) * 64);
+    int d[64];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint4 v = src[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            d[8 * i + 2 * j] = (int)(int16_t)(w[j] & 0xFFFF) * quant[8 * i + 2 * j];
+            d[8 * i + 2 * j + 1] = (int)(int16_t)(w[j] >> 16) * quant[8 * i + 2 * j + 1];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) idct_1d<kConstBits - kPass1Bits>(d + i, 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) idct_1d<kConstBits + kPass1Bits + 3>(d + 8 * i, 1);
+    const int mcu_row = mcu / mcu_cols, mcu_col = mcu - mcu_row * mcu_cols;
+    const int64_t plane_rows = (int64_t)(mcus / mcu_cols) * 8;
+    uint8_t* plane;
+    int64_t width, x0;
+    if (kind < 2) plane = luma, width = (int64_t)mcu_cols * 16, x0 = mcu_col * 16 + kind * 8;
+    else plane = kind == 2 ? chroma_b : chroma_r, width = (int64_t)mcu_cols * 8, x0 = mcu_col * 8;
+    uint8_t* dst = plane + (frame * plane_rows + mcu_row * 8) * width + x0;
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+        uint2 row;
+        row.x = range_limit(d[8 * y]) | range_limit(d[8 * y + 1]) << 8 | range_limit(d[8 * y + 2]) << 16 | range_limit(d[8 * y + 3]) << 24;
+        row.y = range_limit(d[8 * y + 4]) | range_limit(d[8 * y + 5]) << 8 | range_limit(d[8 * y + 6]) << 16 | range_limit(d[8 * y + 7]) << 24;
+        *(uint2*)(dst + y * width) = row;  // 8-byte aligned: planes start 16-byte aligned, widths are multiples of 8
+    }
+}
+
+// ---- 4. upsampling and colour --------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(255, max(0, v)); }
+
+// One thread per 16 pixels of an output row. `wide`: width is a multiple of 16 and d_out is 16-byte aligned, so the 48
+// bytes go out as three 16-byte stores.
+__global__ void __launch_bounds__(256) mjpeg_colour_kernel(const uint8_t* __restrict__ luma, const uint8_t* __restrict__ chroma_b,
+                                                           const uint8_t* __restrict__ chroma_r, int width, int height, int mcu_cols,
+                                                           int64_t plane_rows, int64_t groups, int wide, uint8_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= groups) return;
+    const int group = (int)(t % mcu_cols);
+    const int64_t line = t / mcu_cols;  // frame * height + y
+    const int64_t frame = line / height;
+    const int y = (int)(line - frame * height);
+    const int chroma_width = (width + 1) / 2;  // the component's true width: the upsampler's edges are there
+    const uint4 luma16 = *(const uint4*)(luma + (frame * plane_rows + y) * ((int64_t)mcu_cols * 16) + group * 16);
+    const uint32_t lw[4] = {luma16.x, luma16.y, luma16.z, luma16.w};
+    uint8_t rgb[48];
+    const uint8_t* planes[2] = {chroma_b, chroma_r};
+    int up[2][16];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const uint8_t* row = planes[p] + (frame * plane_rows + y) * ((int64_t)mcu_cols * 8);
+        const int i0 = group * 8;
+        const uint2 v = *(const uint2*)(row + i0);
+        int in[10];  // in[1 + i] = sample i0 + i; in[0] and in[9] the neighbours
+#pragma unroll
+        for (int i = 0; i < 4; ++i) in[1 + i] = (v.x >> (8 * i)) & 0xFF, in[5 + i] = (v.y >> (8 * i)) & 0xFF;
+        in[0] = i0 > 0 ? row[i0 - 1] : 0;
+        in[9] = i0 + 8 < chroma_width ? row[i0 + 8] : 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int index = i0 + i;
+            up[p][2 * i] = index == 0 ? in[1 + i] : (3 * in[1 + i] + in[i] + 1) >> 2;
+            up[p][2 * i + 1] = index >= chroma_width - 1 ? in[1 + i] : (3 * in[1 + i] + in[2 + i] + 2) >> 2;
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+        const int luminance = (lw[x >> 2] >> (8 * (x & 3))) & 0xFF;
+        const int cb = up[0][x] - 128, cr = up[1][x] - 128;
+        rgb[3 * x] = (uint8_t)clamp255(luminance + ((91881 * cr + 32768) >> 16));
+        rgb[3 * x + 1] = (uint8_t)clamp255(luminance + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+        rgb[3 * x + 2] = (uint8_t)clamp255(luminance + ((116130 * cb + 32768) >> 16));
+    }
+    uint8_t* dst = out + (line * width + group * 16) * 3;
+    if (wide) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                w[j] = rgb[16 * i + 4 * j] | rgb[16 * i + 4 * j + 1] << 8 | rgb[16 * i + 4 * j + 2] << 16 | (uint32_t)rgb[16 * i + 4 * j + 3] << 24;
+            ((uint4*)dst)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    } else {
+        const int count = min(16, width - group * 16) * 3;
+#pragma unroll
+        for (int i = 0; i < 48; ++i)
+            if (i < count) dst[i] = rgb[i];
+    }
+}
+
+// ---- host: header parsing ------------------------------------------------------------------------------------------
+static int fail(const std::string& message) { return gance::set_last_error(GANCE_ERR_INVALID_ARGUMENT, message); }
+
+// counts sum to at most 256, the code is not over-subscribed, DC symbols are categories 0..11
+static bool table_error(const uint8_t bits[16], const uint8_t* values, bool dc, std::string* why) {
+    int count = 0, code = 0;
+    for (int length = 1; length <= 16; ++length) {
+        count += bits[length - 1];
+        code += bits[length - 1];
+        if (code > (1 << length)) return *why = "over-subscribed Huffman table", true;
+        code <<= 1;
+    }
+    if (count > 256) return *why = "Huffman table with more than 256 codes", true;
+    if (dc)
+        for (int i = 0; i < count; ++i)
+            if (values[i] > 11) return *why = "DC Huffman table with a category above 11", true;
+    return false;
+}
+
+static void annex_k_tables(gance_jpeg_info* info) {
+    using namespace gance_mjpeg;
+    for (int c = 0; c < 3; ++c) {
+        const bool chroma = c > 0;
+        std::memset(info->huff_values[c], 0, sizeof(info->huff_values[c]));
+        std::memcpy(info->huff_bits[c][0], chroma ? kDcChromaBits : kDcLumaBits, 16);
+        std::memcpy(info->huff_values[c][0], kDcValues, sizeof(kDcValues));
+        std::memcpy(info->huff_bits[c][1], chroma ? kAcChromaBits : kAcLumaBits, 16);
+        std::memcpy(info->huff_values[c][1], chroma ? kAcChromaValues : kAcLumaValues, sizeof(kAcLumaValues));
+    }
+}
+
+static int parse_header(const uint8_t* file, uint64_t size, gance_jpeg_info* info) {
+    struct Huffman {
+        bool defined = false;
+        uint8_t bits[16] = {}, values[256] = {};
+    };
+    Huffman huffman[2][4];
+    uint8_t quant[4][64];
+    bool quant_defined[4] = {}, any_dht = false, have_frame = false;
+    int quant_of[3] = {};
+    std::memset(info, 0, sizeof(*info));
+    const std::string cut = "JPEG header cut short";
+    if (size < 4 || file[0] != 0xFF || file[1] != 0xD8) return fail(size < 4 ? cut : "not a JPEG file (no SOI)");
+    uint64_t at = 2;
+    for (;;) {
+        if (at + 4 > size) return fail(cut);
+        if (file[at] != 0xFF) return fail("JPEG header: marker expected at byte " + std::to_string(at));
+        const int marker = file[at + 1];
+        if (marker == 0xFF) {  // fill byte
+            ++at;
+            continue;
+        }
+        if (marker == 0xD9) return fail("JPEG file without a scan");
+        if (marker == 0x01 || (marker >= 0xD0 && marker <= 0xD7)) {  // no length
+            at += 2;
+            continue;
+        }
+        const uint64_t length = (uint64_t)file[at + 2] << 8 | file[at + 3];
+        if (length < 2 || at + 2 + length > size) return fail(cut);
+        const uint8_t* body = file + at + 4;
+        const uint64_t body_bytes = length - 2;
+        at += 2 + length;
+        if (marker == 0xDB) {
+            for (uint64_t i = 0; i < body_bytes;) {
+                const int precision = body[i] >> 4, id = body[i] & 15;
+                if (precision != 0) return fail("unsupported JPEG: 16-bit DQT");
+                if (id > 3) return fail("JPEG header: quantisation table id " + std::to_string(id));
+                if (i + 65 > body_bytes) return fail(cut);
+                for (int z = 0; z < 64; ++z) quant[id][natural_of_zigzag(z)] = body[i + 1 + z];
+                quant_defined[id] = true;
+                i += 65;
+            }
+        } else if (marker == 0xC4) {
+            for (uint64_t i = 0; i < body_bytes;) {
+                const int cls = body[i] >> 4, id = body[i] & 15;
+                if (cls > 1 || id > 3) return fail("JPEG header: Huffman table class " + std::to_string(cls) + " id " + std::to_string(id));
+                if (i + 17 > body_bytes) return fail(cut);
+                Huffman& table = huffman[cls][id];
+                int count = 0;
+                for (int k = 0; k < 16; ++k) count += body[i + 1 + k];
+                std::string why;
+                if (table_error(body + i + 1, nullptr, false, &why)) return fail("invalid JPEG: " + why);  // the counts alone
+                if (i + 17 + count > body_bytes) return fail(cut);
+                std::memcpy(table.bits, body + i + 1, 16);
+                std::memset(table.values, 0, 256);
+                std::memcpy(table.values, body + i + 17, count);
+                if (table_error(table.bits, table.values, cls == 0, &why)) return fail("invalid JPEG: " + why);
+                table.defined = any_dht = true;
+                i += 17 + count;
+            }
+        } else if (marker == 0xC0) {
+            if (have_frame) return fail("JPEG header: more than one SOF");
+            if (body_bytes < 6) return fail(cut);
+            if (body[0] != 8) return fail("unsupported JPEG: " + std::to_string(body[0]) + "-bit samples (12-bit samples are not baseline)");
+            info->height = body[1] << 8 | body[2];
+            info->width = body[3] << 8 | body[4];
+            const int components = body[5];
+            if (components == 1) return fail("unsupported JPEG: grey (one component); only 4:2:2 colour is decoded");
+            if (components != 3) return fail("unsupported JPEG: " + std::to_string(components) + " components");
+            if (body_bytes < 6 + 9) return fail(cut);
+            int sampling[3];
+            for (int c = 0; c < 3; ++c) {
+                sampling[c] = body[6 + 3 * c + 1];
+                quant_of[c] = body[6 + 3 * c + 2];
+                if (quant_of[c] > 3) return fail("JPEG header: quantisation table id " + std::to_string(quant_of[c]));
+            }
+            if (sampling[1] != 0x11 || sampling[2] != 0x11 || sampling[0] != 0x21) {
+                const char* name = sampling[1] == 0x11 && sampling[2] == 0x11
+                                       ? (sampling[0] == 0x22 ? "4:2:0" : (sampling[0] == 0x11 ? "4:4:4" : "this chroma sampling"))
+                                       : "this chroma sampling";
+                return fail(std::string("unsupported JPEG: ") + name + "; only 4:2:2 (2x1, 1x1, 1x1) is decoded");
+            }
+            if (info->width < 1 || info->width > kMaxSide || info->height < 1 || info->height > kMaxSide)
+                return fail("unsupported JPEG: " + std::to_string(info->width) + " x " + std::to_string(info->height) +
+                            ", width and height must be in [1, " + std::to_string(kMaxSide) + "]");
+            have_frame = true;
+        } else if (marker >= 0xC1 && marker <= 0xCF && marker != 0xC8 && marker != 0xCC) {
+            return fail(std::string("unsupported JPEG: ") + (marker == 0xC2 ? "progressive" : (marker == 0xC1 ? "extended sequential" : "not baseline")) +
+                        " (SOF" + std::to_string(marker - 0xC0) + "); only baseline SOF0 is decoded");
+        } else if (marker == 0xDD) {
+            if (body_bytes < 2) return fail(cut);
+            info->restart_interval = body[0] << 8 | body[1];
+        } else if (marker == 0xDA) {
+            if (!have_frame) return fail("JPEG header: SOS before SOF");
+            if (body_bytes < 1) return fail(cut);
+            if (body[0] != 3) return fail("unsupported JPEG: more than one scan (a scan of " + std::to_string(body[0]) + " of the 3 components)");
+            if (body_bytes < 1 + 6 + 3) return fail(cut);
+            if (body[7] != 0 || body[8] != 63 || body[9] != 0) return fail("unsupported JPEG: a scan that is not baseline (spectral selection or approximation)");
+            if (!any_dht) annex_k_tables(info);
+            info->has_huffman_tables = any_dht;
+            for (int c = 0; c < 3; ++c) {
+                const int dc = body[2 + 2 * c] >> 4, ac = body[2 + 2 * c] & 15;
+                if (dc > 3 || ac > 3) return fail("JPEG header: Huffman table id in SOS");
+                if (any_dht) {
+                    if (!huffman[0][dc].defined || !huffman[1][ac].defined) return fail("invalid JPEG: the scan uses a Huffman table the file does not define");
+                    std::memcpy(info->huff_bits[c][0], huffman[0][dc].bits, 16);
+                    std::memcpy(info->huff_values[c][0], huffman[0][dc].values, 256);
+                    std::memcpy(info->huff_bits[c][1], huffman[1][ac].bits, 16);
+                    std::memcpy(info->huff_values[c][1], huffman[1][ac].values, 256);
+                }
+                if (!quant_defined[quant_of[c]]) return fail("invalid JPEG: a component uses a quantisation table the file does not define");
+                std::memcpy(info->quant[c], quant[quant_of[c]], 64);
+            }
+            info->scan_offset = at;
+            info->scan_bytes = size - at;
+            return GANCE_OK;
+        }
+        // APPn, COM and anything else with a length: skipped
+    }
+}
+
+// ---- host: tables of a call ----------------------------------------------------------------------------------------
+static void derive_table(const uint8_t bits[16], const uint8_t* values, DeviceTable* table) {
+    std::memset(table, 0, sizeof(*table));
+    std::memcpy(table->values, values, 256);
+    int code = 0, k = 0;
+    for (int length = 1; length <= 16; ++length) {
+        table->valoff[length] = k - code;
+        for (int i = 0; i < bits[length - 1]; ++i, ++k, ++code) {
+            if (length > kLookBits) continue;
+            const int spare = kLookBits - length;
+            for (int j = 0; j < (1 << spare); ++j) table->fast[(code << spare) + j] = (uint16_t)(length << 8 | values[k]);
+        }
+        table->maxcode[length] = bits[length - 1] ? code - 1 : -1;
+        code <<= 1;
+    }
+}
+
+static size_t tables_offset() { return offsetof(gance_jpeg_info, quant); }
+static size_t tables_bytes() { return sizeof(gance_jpeg_info) - tables_offset(); }
+
+// The pinned buffer the per-call tables are copied from. One call at a time fills it; the next waits for the previous
+// call's copy (not its kernels) through `copied`.
+struct Staging {
+    std::mutex mutex;
+    void* host = nullptr;
+    size_t capacity = 0;
+    hipEvent_t copied = nullptr;
+};
+static Staging g_staging;
+
+static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch, void* d_workspace,
+                  uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream_ptr) {
+    if (batch < 1) return fail("batch must be >= 1");
+    const int width = infos[0].width, height = infos[0].height;
+    if (width < 1 || width > kMaxSide || height < 1 || height > kMaxSide)
+        return fail("width and height must be in [1, " + std::to_string(kMaxSide) + "], got " + std::to_string(width) + " x " + std::to_string(height));
+    if ((uintptr_t)d_workspace % 16 != 0) return fail("workspace must be 16-byte aligned");
+    if (h_offsets[0] < 0) return fail("offsets must not be negative");
+    const Layout l = layout_of(batch, width, height);
+    if (l.max_markers > INT32_MAX) return fail("batch of " + std::to_string(batch) + " frames of this size: split the call");
+
+    std::vector<FrameDesc> descs((size_t)batch);
+    std::vector<const gance_jpeg_info*> distinct;
+    int64_t marker_base = 0;
+    int max_segments = 1;
+    for (int32_t b = 0; b < batch; ++b) {
+        const gance_jpeg_info& info = infos[b];
+        const std::string name = "frame " + std::to_string(b);
+        const int64_t file_bytes = h_offsets[b + 1] - h_offsets[b];
+        if (file_bytes < 0 || file_bytes > INT32_MAX) return fail(name + ": a file of " + std::to_string(file_bytes) + " bytes");
+        if (info.width != width || info.height != height)
+            return fail(name + " is " + std::to_string(info.width) + " x " + std::to_string(info.height) + ", frame 0 is " +
+                        std::to_string(width) + " x " + std::to_string(height) + ": the frames of one call must have one size");
+        if (info.scan_offset > (uint64_t)file_bytes || info.scan_offset + info.scan_bytes != (uint64_t)file_bytes)
+            return fail(name + ": the scan range does not end with the file");
+        if (info.restart_interval < 0 || info.restart_interval > 65535) return fail(name + ": restart interval " + std::to_string(info.restart_interval));
+        for (int c = 0; c < 3; ++c)
+            for (int cls = 0; cls < 2; ++cls) {
+                std::string why;
+                if (table_error(info.huff_bits[c][cls], info.huff_values[c][cls], cls == 0, &why)) return fail(name + ": " + why);
+            }
+        int set = -1;
+        for (int s = (int)distinct.size() - 1; s >= 0 && set < 0; --s)
+            if (std::memcmp((const char*)distinct[s] + tables_offset(), (const char*)&info + tables_offset(), tables_bytes()) == 0) set = s;
+        if (set < 0) set = (int)distinct.size(), distinct.push_back(&info);
+        FrameDesc& d = descs[b];
+        d.scan_begin = h_offsets[b] + (int64_t)info.scan_offset;
+        d.scan_bytes = (int32_t)info.scan_bytes;
+        d.restart_interval = info.restart_interval;
+        d.segments = info.restart_interval > 0 ? (int32_t)((l.mcus + info.restart_interval - 1) / info.restart_interval) : 1;
+        d.marker_base = (int32_t)marker_base;
+        d.table_set = set;
+        d.reserved = 0;
+        marker_base += d.segments - 1;
+        if (d.segments > max_segments) max_segments = d.segments;
+    }
+    if (workspace_bytes < (uint64_t)l.workspace_bytes)
+        return fail("workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.workspace_bytes) +
+                    " needed (gance_jpeg_decode_bounds)");
+
+    int device_count = 0;
+    if (hipGetDeviceCount(&device_count) != hipSuccess || device_count == 0)
+        return gance::set_last_error(GANCE_ERR_NO_DEVICE, "no HIP device visible; libgance_hip has no CPU path");
+    gance::DeviceGuard guard(gance::device_of_pointer(d_data));  // launch where the bytes live
+    if (guard.status() != hipSuccess)
+        return gance::set_last_error(GANCE_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.status()));
+    hipStream_t stream = (hipStream_t)stream_ptr;
+
+    const size_t desc_bytes = (size_t)round16(batch * (int64_t)sizeof(FrameDesc));
+    const size_t upload_bytes = desc_bytes + distinct.size() * sizeof(TableSet);
+    {
+        std::lock_guard<std::mutex> lock(g_staging.mutex);
+        hipError_t err = hipSuccess;
+        if (g_staging.copied != nullptr) {
+            err = hipEventSynchronize(g_staging.copied);
+            (void)hipEventDestroy(g_staging.copied);
+            g_staging.copied = nullptr;
+        }
+        if (err == hipSuccess && g_staging.capacity < upload_bytes) {
+            if (g_staging.host != nullptr) (void)hipHostFree(g_staging.host);
+            g_staging.host = nullptr, g_staging.capacity = 0;
+            err = hipHostMalloc(&g_staging.host, upload_bytes, hipHostMallocPortable);
+            if (err == hipSuccess) g_staging.capacity = upload_bytes;
+        }
+        if (err == hipSuccess) {
+            char* host = (char*)g_staging.host;
+            std::memset(host, 0, desc_bytes);
+            std::memcpy(host, descs.data(), (size_t)batch * sizeof(FrameDesc));
+            TableSet* sets = (TableSet*)(host + desc_bytes);
+            for (size_t s = 0; s < distinct.size(); ++s) {
+                for (int c = 0; c < 3; ++c) {
+                    derive_table(distinct[s]->huff_bits[c][0], distinct[s]->huff_values[c][0], &sets[s].huff[c][0]);
+                    derive_table(distinct[s]->huff_bits[c][1], distinct[s]->huff_values[c][1], &sets[s].huff[c][1]);
+                    for (int i = 0; i < 64; ++i) sets[s].quant[c][i] = distinct[s]->quant[c][i];
+                }
+            }
+            err = hipMemcpyAsync(d_workspace, host, upload_bytes, hipMemcpyHostToDevice, stream);
+        }
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&g_staging.copied, hipEventDisableTiming);
+        if (err == hipSuccess) err = hipEventRecord(g_staging.copied, stream);
+        if (err != hipSuccess) return gance::set_last_error(GANCE_ERR_HIP, std::string("mjpeg decode tables: ") + hipGetErrorString(err));
+    }
+
+    char* ws = (char*)d_workspace;
+    const FrameDesc* d_frames = (const FrameDesc*)ws;
+    const TableSet* d_sets = (const TableSet*)(ws + desc_bytes);
+    char* at = ws + l.params_bytes;
+    int32_t* marker_pos = (int32_t*)at;
+    at += l.marker_bytes;
+    int32_t* scan_end = (int32_t*)at;
+    at += l.end_bytes;
+    int16_t* coef = (int16_t*)at;
+    at += l.coef_bytes;
+    uint8_t* luma = (uint8_t*)at;
+    at += l.luma_bytes;
+    uint8_t* chroma_b = (uint8_t*)at;
+    uint8_t* chroma_r = (uint8_t*)(at + l.chroma_bytes);
+
+    mjpeg_marker_scan_kernel<<<(unsigned)batch, kScanThreads, 0, stream>>>(d_data, d_frames, marker_pos, scan_end, d_status);
+    const dim3 entropy_grid((unsigned)((max_segments + kEntropyThreads - 1) / kEntropyThreads), (unsigned)batch);
+    mjpeg_entropy_kernel<<<entropy_grid, kEntropyThreads, 0, stream>>>(d_data, d_frames, d_sets, marker_pos, scan_end, d_status, coef, (int)l.mcus);
+    const int64_t blocks = (int64_t)batch * l.mcus * 4;
+    mjpeg_idct_kernel<<<(unsigned)((blocks + 255) / 256), 256, 0, stream>>>(coef, d_frames, d_sets, (int)l.mcus, (int)l.mcu_cols, blocks, luma, chroma_b,
+                                                                           chroma_r);
+    const int64_t groups = (int64_t)batch * height * l.mcu_cols;
+    const int wide = width % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+    mjpeg_colour_kernel<<<(unsigned)((groups + 255) / 256), 256, 0, stream>>>(luma, chroma_b, chroma_r, width, height, (int)l.mcu_cols, l.plane_rows,
+                                                                             groups, wide, d_out);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return gance::set_last_error(GANCE_ERR_HIP, std::string("mjpeg decode launch: ") + hipGetErrorString(err));
+    return GANCE_OK;
+}
+
+}  // namespace gance_mjpeg_decode
+
+extern "C" {
+
+int gance_jpeg_parse_header(const uint8_t* file, uint64_t file_bytes, gance_jpeg_info* info) {
+    using namespace gance_mjpeg_decode;
+    if (file == nullptr || info == nullptr) return fail("NULL argument to gance_jpeg_parse_header");
+    return parse_header(file, file_bytes, info);
+}
+
+int gance_jpeg_decode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t total_bytes, uint64_t* workspace_bytes) {
+    using namespace gance_mjpeg_decode;
+    if (workspace_bytes == nullptr) return fail("NULL argument to gance_jpeg_decode_bounds");
+    if (batch < 1) return fail("batch must be >= 1");
+    if (width < 1 || width > kMaxSide || height < 1 || height > kMaxSide)
+        return fail("width and height must be in [1, " + std::to_string(kMaxSide) + "], got " + std::to_string(width) + " x " + std::to_string(height));
+    // (the layout is sized by the geometry alone; total_bytes is part of the query so that it may depend on it)
+    (void)total_bytes;
+    *workspace_bytes = (uint64_t)layout_of(batch, width, height).workspace_bytes;
+    return GANCE_OK;
+}
+
+int gance_jpeg_decode_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch, void* d_workspace,
+                         uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream) {
+    using namespace gance_mjpeg_decode;
+    if (d_data == nullptr || h_offsets == nullptr || infos == nullptr || d_workspace == nullptr || d_out == nullptr || d_status == nullptr)
+        return fail("NULL argument to gance_jpeg_decode_u8");
+    return decode(d_data, h_offsets, infos, batch, d_workspace, workspace_bytes, d_out, d_status, stream);
+}
+
+}  // extern "C"

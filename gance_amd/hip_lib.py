@@ -9,7 +9,7 @@ MI355X is visible, calls raise: there is no CPU fallback in the product path.
 import ctypes
 import os
 from pathlib import Path
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch  # noqa: F401  pylint: disable=unused-import
@@ -225,6 +225,16 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_jpeg_parse_header": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "gance_jpeg_decode_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_jpeg_decode_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_debug_place_panels_u8": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
@@ -268,7 +278,8 @@ SIGNATURES = {
 # libgance_hip_prev.so) may lack them, and only a call of the missing entry fails there
 ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
-    "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8",
+    "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8", "gance_jpeg_parse_header",
+    "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -815,6 +826,65 @@ def jpeg_encode_rect_device(  # pylint: disable=too-many-arguments
         lib,
         lib.gance_jpeg_encode_rect_u8(
             d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
+        ),
+    )
+
+
+JPEG_STATUS_REASONS = {0: "ok", 1: "truncated data", 2: "invalid Huffman code", 3: "restart marker mismatch"}
+
+
+class JpegInfo(ctypes.Structure):
+    """`gance_jpeg_info` of include/gance_hip.h: what `jpeg_parse_header` reads from one JFIF file."""
+
+    _fields_ = [
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+        ("has_huffman_tables", ctypes.c_int32), ("scan_offset", ctypes.c_uint64), ("scan_bytes", ctypes.c_uint64),
+        ("quant", ctypes.c_uint8 * 64 * 3), ("huff_bits", ctypes.c_uint8 * 16 * 2 * 3), ("huff_values", ctypes.c_uint8 * 256 * 2 * 3),
+    ]
+
+
+def jpeg_parse_header(data: Union[bytes, bytearray, memoryview, np.ndarray], info: Optional[JpegInfo] = None) -> JpegInfo:
+    """
+    The description of one JFIF file (host bytes), read on the host: sizes, restart interval, where the entropy-coded data
+    lies, and the tables. `info`: an element of a `JpegInfo` array to fill instead of a new one.
+    :raises ValueError: a header cut short, a file the decoder does not take (progressive, 4:2:0, 4:4:4, grey, 12-bit
+    samples, a 16-bit DQT, more than one scan) or an invalid Huffman table; the message names the reason.
+    """
+    lib = load_library()
+    buffer = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    info = JpegInfo() if info is None else info
+    _value_error_on_invalid_argument(lib, lib.gance_jpeg_parse_header(buffer.ctypes.data, buffer.size, ctypes.byref(info)))
+    return info
+
+
+def jpeg_decode_bounds(batch: int, width: int, height: int, total_bytes: int) -> int:
+    """Workspace bytes of one `jpeg_decode_device` call of `batch` files of width x height that total `total_bytes`.
+    :raises ValueError: batch < 1, or width or height outside [1, 8192]."""
+    lib = load_library()
+    workspace = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_jpeg_decode_bounds(batch, width, height, total_bytes, ctypes.byref(workspace)))
+    return int(workspace.value)
+
+
+def jpeg_decode_device(  # pylint: disable=too-many-arguments
+    d_data: int, offsets: np.ndarray, infos: "ctypes.Array[JpegInfo]", d_workspace: int, workspace_bytes: int, d_out: int,
+    d_status: int, stream: int = 0,
+) -> None:
+    """
+    Baseline 4:2:2 JFIF files in HBM (file b at d_data[offsets[b]:offsets[b + 1]], `offsets` int64 [batch + 1] and `infos`
+    [batch] on the host) to uint8 [batch][height][width][3] RGB at d_out, equal to libjpeg's default decode; d_status
+    [batch] int32 receives a key of `JPEG_STATUS_REASONS` per frame. Asynchronous on `stream`.
+    :raises ValueError: frames of different sizes, descriptions that do not fit the offsets, a workspace below `jpeg_decode_bounds`.
+    """
+    lib = load_library()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    batch = len(infos)
+    if offsets.shape != (batch + 1,):
+        raise ValueError(f"offsets must be [{batch + 1}] for {batch} descriptions, got {offsets.shape}")
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_jpeg_decode_u8(
+            d_data, offsets.ctypes.data, ctypes.addressof(infos), batch, d_workspace, workspace_bytes, d_out, d_status, stream or None
         ),
     )
 

@@ -9,6 +9,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.blend(audio, latent_row0, blend)       [samples] f32, [F, L] f32 -> ([N, depth, L] f32, [N] i32)
     torch.ops.gance.jpeg_encode_rect(frames, quality)      [B, H, W, 3] u8  -> the same for frames that are not square
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
+    torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
 without synchronising, so the ops compose with torch code and with `torch.distributed` collectives in stream
@@ -20,9 +21,11 @@ The ops are thin: they validate shapes, allocate the outputs with torch and pass
 ctypes binding (gance_amd/hip_lib.py). There is no CPU implementation: on a CPU tensor an op raises.
 """
 
+import ctypes
 import weakref
 from typing import Tuple
 
+import numpy as np
 import torch
 
 from gance_amd import hip_lib
@@ -281,3 +284,73 @@ def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
     batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     _, capacity = hip_lib.jpeg_encode_rect_bounds(batch, width, height)
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+def _jpeg_headers(data: torch.Tensor, offsets: torch.Tensor) -> Tuple[np.ndarray, "ctypes.Array[hip_lib.JpegInfo]"]:
+    """
+    (host offsets, descriptions) of the files of a `jpeg_decode` call. Only each file's first bytes cross to the host:
+    the header is a few hundred bytes, and a parse that runs out of them is repeated with more.
+    """
+    host_offsets = offsets.detach().cpu().numpy().astype(np.int64)
+    batch = host_offsets.shape[0] - 1
+    if batch < 1 or host_offsets[0] < 0 or np.any(np.diff(host_offsets) < 0) or host_offsets[-1] > data.numel():
+        raise ValueError(f"offsets must be [B + 1] non-decreasing positions inside the {data.numel()} bytes of data, B >= 1")
+    infos = (hip_lib.JpegInfo * batch)()
+    head_bytes = 1024
+    while True:
+        spans = [(int(host_offsets[b]), int(min(host_offsets[b] + head_bytes, host_offsets[b + 1]))) for b in range(batch)]
+        index = torch.cat([torch.arange(first, last, device=data.device) for first, last in spans])
+        heads = data[index].cpu().numpy()
+        at, retry = 0, False
+        for b, (first, last) in enumerate(spans):
+            head = heads[at : at + last - first]
+            at += last - first
+            try:
+                hip_lib.jpeg_parse_header(head, infos[b])
+            except ValueError as error:
+                if "cut short" in str(error) and last < host_offsets[b + 1]:
+                    retry = True
+                    break
+                raise ValueError(f"frame {b}: {error}") from None
+            infos[b].scan_bytes = int(host_offsets[b + 1]) - first - infos[b].scan_offset
+        if not retry:
+            return host_offsets, infos
+        head_bytes *= 16
+
+
+@torch.library.custom_op("gance::jpeg_decode", mutates_args=(), device_types="cuda")
+def jpeg_decode(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """
+    The reverse of `jpeg_encode` / `jpeg_encode_rect`, and the frame decode of frames_in_video (video_common.py:229-298):
+    file b at data[offsets[b]:offsets[b + 1]] (baseline 4:2:2 JFIF of one size, any tables and restart interval; `offsets`
+    on either device) to RGB [B, H, W, 3] u8, pixel for pixel what libjpeg decodes. The headers and the per-frame status
+    cross to the host once per call, so the op synchronises.
+    :raises ValueError: a file the decoder does not take, or a frame whose data is bad: the first such frame and the reason.
+    """
+    _require_cuda(data, torch.uint8, "data")
+    if data.dim() != 1 or offsets.dim() != 1 or offsets.dtype != torch.int64:
+        raise ValueError("data must be [bytes] uint8 and offsets [B + 1] int64")
+    data = data.contiguous()
+    host_offsets, infos = _jpeg_headers(data, offsets)
+    batch, width, height = len(infos), infos[0].width, infos[0].height
+    workspace_bytes = hip_lib.jpeg_decode_bounds(batch, width, height, int(host_offsets[-1] - host_offsets[0]))
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=data.device)
+    frames = torch.empty((batch, height, width, 3), dtype=torch.uint8, device=data.device)
+    status = torch.empty((batch,), dtype=torch.int32, device=data.device)
+    hip_lib.jpeg_decode_device(
+        data.data_ptr(), host_offsets, infos, workspace.data_ptr(), workspace_bytes, frames.data_ptr(), status.data_ptr(), _stream(data)
+    )
+    host_status = status.cpu().numpy()
+    bad = np.flatnonzero(host_status)
+    if bad.size:
+        reason = hip_lib.JPEG_STATUS_REASONS.get(int(host_status[bad[0]]), f"status {int(host_status[bad[0]])}")
+        raise ValueError(f"frame {int(bad[0])}: {reason}")
+    return frames
+
+
+@jpeg_decode.register_fake
+def _(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    # the frame size is in the bytes: a data-dependent shape
+    context = torch.library.get_ctx()
+    height, width = context.new_dynamic_size(), context.new_dynamic_size()
+    return data.new_empty((offsets.shape[0] - 1, height, width, 3))

@@ -13,12 +13,15 @@ indices are held until `close()`. The layout is AVI 2.0 / OpenDML, because real 
 covers the first segment for AVI 1.0 readers; `dmlh` holds the total frame count. The audio is the input WAVs
 concatenated (as add_wavs_to_video's ffmpeg concat does), stored as PCM (format tag 1) or IEEE float (3), in chunks of
 about one second interleaved between the video frames.
+
+`MjpegAviReader` reads such a file back (and other Motion-JPEG AVIs): frame locations from the OpenDML indices, or from
+`idx1` when there are none; the JFIF bytes go to torch.ops.gance.jpeg_decode undecoded (gance_amd/video/video_common.py).
 """
 
 import struct
 from fractions import Fraction
 from pathlib import Path
-from typing import BinaryIO, List, Optional, Sequence, Tuple, Union
+from typing import BinaryIO, Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 from scipy.io import wavfile
@@ -295,6 +298,222 @@ class MjpegAviWriter:  # pylint: disable=too-many-instance-attributes
         f.close()
 
     def __enter__(self) -> "MjpegAviWriter":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
+class _Stream:  # pylint: disable=too-few-public-methods
+    """What `hdrl` says about one stream."""
+
+    def __init__(self) -> None:
+        self.kind = b""
+        self.scale, self.rate, self.length = 1, 0, 0
+        self.format = b""
+        self.super_index: Optional[bytes] = None
+
+
+class MjpegAviReader:  # pylint: disable=too-many-instance-attributes
+    """
+    The frames (as JFIF byte strings) and the audio of a Motion-JPEG AVI, e.g. one `MjpegAviWriter` wrote. Frame locations
+    come from the OpenDML indices (`indx` -> `ix00` of every RIFF segment), or from `idx1` (AVI 1.0: the first segment only)
+    when the file has none. A context manager; `close()` releases the file.
+    :raises ValueError: not a RIFF / AVI file, no video stream, a video stream that is not MJPG, a frame count (`dmlh`) that
+    the index does not bear out, or a first frame of zero length.
+    """
+
+    def __init__(self, path: Union[str, Path]) -> None:
+        self._path = Path(path)
+        self._file: BinaryIO = open(self._path, "rb")  # pylint: disable=consider-using-with
+        try:
+            self._parse()
+        except (struct.error, IndexError) as error:
+            self._file.close()
+            raise ValueError(f"{self._path}: damaged AVI headers ({error})") from None
+        except Exception:
+            self._file.close()
+            raise
+
+    # ---- RIFF ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _children(blob: bytes, at: int, end: int) -> Iterator[Tuple[bytes, int, int]]:
+        """(fourcc, start of data, size) of the chunks in blob[at:end]."""
+        while at + 8 <= end:
+            fourcc, size = struct.unpack_from("<4sI", blob, at)
+            yield fourcc, at + 8, size
+            at += 8 + size + (size & 1)
+
+    def _parse(self) -> None:  # pylint: disable=too-many-locals,too-many-branches,too-many-statements
+        f = self._file
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:] != b"AVI ":
+            raise ValueError(f"{self._path} is not a RIFF / AVI file")
+        riff_end = 8 + struct.unpack_from("<I", head, 4)[0]
+        streams: List[_Stream] = []
+        total_frames: Optional[int] = None
+        movi_at: Optional[int] = None  # of the 'movi' fourcc: what idx1 offsets count from
+        idx1: Optional[bytes] = None
+        at = 12
+        while at + 8 <= riff_end:
+            f.seek(at)
+            header = f.read(12)
+            if len(header) < 8:
+                break
+            fourcc, size = struct.unpack_from("<4sI", header)
+            if fourcc == b"LIST" and header[8:] == b"hdrl":
+                blob = f.read(size - 4)
+                for child, start, child_size in self._children(blob, 0, len(blob)):
+                    if child != b"LIST":
+                        continue
+                    kind = blob[start : start + 4]
+                    if kind == b"strl":
+                        stream = _Stream()
+                        for sub, sub_start, sub_size in self._children(blob, start + 4, start + child_size):
+                            if sub == b"strh":
+                                stream.kind = blob[sub_start : sub_start + 4]
+                                stream.scale, stream.rate = struct.unpack_from("<II", blob, sub_start + 20)
+                                stream.length = struct.unpack_from("<I", blob, sub_start + 32)[0]
+                            elif sub == b"strf":
+                                stream.format = blob[sub_start : sub_start + sub_size]
+                            elif sub == b"indx":
+                                stream.super_index = blob[sub_start : sub_start + sub_size]
+                        streams.append(stream)
+                    elif kind == b"odml":
+                        for sub, sub_start, _ in self._children(blob, start + 4, start + child_size):
+                            if sub == b"dmlh":
+                                total_frames = struct.unpack_from("<I", blob, sub_start)[0]
+            elif fourcc == b"LIST" and header[8:] == b"movi":
+                movi_at = at + 8
+            elif fourcc == b"idx1":
+                f.seek(at + 8)
+                idx1 = f.read(size)
+            at += 8 + size + (size & 1)
+
+        video = next((n for n, stream in enumerate(streams) if stream.kind == b"vids"), None)
+        if video is None:
+            raise ValueError(f"{self._path} has no video stream")
+        strf = streams[video].format
+        _, self.width, self.height, _, _, compression = struct.unpack_from("<IiiHH4s", strf)
+        if compression.upper() != b"MJPG":
+            raise ValueError(f"{self._path}: the video stream is {compression!r}, only MJPG (Motion-JPEG) can be read")
+        self.height = abs(self.height)
+        if streams[video].rate == 0 or streams[video].scale == 0:
+            raise ValueError(f"{self._path}: frame rate {streams[video].rate} / {streams[video].scale}")
+        self.fps_fraction = Fraction(streams[video].rate, streams[video].scale)
+        self.fps = float(self.fps_fraction)
+
+        chunks = self._indexed_chunks(streams[video], video, b"dc", movi_at, idx1)
+        from_opendml = chunks is not None and self._has_super_index(streams[video])
+        if chunks is None:
+            raise ValueError(f"{self._path} has neither OpenDML indices nor idx1")
+        self._frames: List[Tuple[int, int]] = []
+        for offset, size in chunks:
+            if size == 0:  # a dropped frame: the previous one shows again
+                if not self._frames:
+                    raise ValueError(f"{self._path}: the first frame has no data")
+                self._frames.append(self._frames[-1])
+            else:
+                self._frames.append((offset, size))
+        if from_opendml and total_frames is not None and total_frames != len(self._frames):
+            raise ValueError(f"{self._path}: dmlh counts {total_frames} frames, the indices hold {len(self._frames)}")
+        self.frame_count = len(self._frames)
+
+        self._audio_format: Optional[Tuple[int, int, int, int]] = None  # tag, channels, rate, bits per sample
+        self._audio_chunks: List[Tuple[int, int]] = []
+        audio = next((n for n, stream in enumerate(streams) if stream.kind == b"auds"), None)
+        if audio is not None:
+            tag, channels, rate, _, _, bits = struct.unpack_from("<HHIIHH", streams[audio].format)
+            self._audio_format = (tag, channels, rate, bits)
+            self._audio_chunks = self._indexed_chunks(streams[audio], audio, b"wb", movi_at, idx1) or []
+
+    @staticmethod
+    def _has_super_index(stream: _Stream) -> bool:
+        return stream.super_index is not None and len(stream.super_index) >= 24 and struct.unpack_from("<I", stream.super_index, 4)[0] > 0
+
+    def _indexed_chunks(
+        self, stream: _Stream, number: int, suffix: bytes, movi_at: Optional[int], idx1: Optional[bytes]
+    ) -> Optional[List[Tuple[int, int]]]:
+        """(offset of the data, size) of the stream's chunks in order, or None without any index."""
+        f = self._file
+        if self._has_super_index(stream):
+            indx = stream.super_index
+            assert indx is not None
+            _, _, index_type, entries = struct.unpack_from("<HBBI", indx)
+            chunks: List[Tuple[int, int]] = []
+            if index_type == 1:  # the indx is itself a chunk index
+                return self._standard_index(indx)
+            for i in range(entries):
+                offset, size, _ = struct.unpack_from("<QII", indx, 24 + 16 * i)
+                f.seek(offset + 8)
+                chunks += self._standard_index(f.read(size - 8))
+            return chunks
+        if idx1 is None or movi_at is None:
+            return None
+        wanted = b"%02d" % number + suffix
+        entries = [struct.unpack_from("<4sIII", idx1, 16 * i) for i in range(len(idx1) // 16)]
+        # offsets count from the 'movi' fourcc; some writers count from the start of the file instead
+        base = movi_at
+        if entries:
+            f.seek(movi_at + entries[0][2])
+            if f.read(4) != entries[0][0]:
+                base = 0
+        return [(base + offset + 8, size) for fourcc, _, offset, size in entries if fourcc == wanted]
+
+    @staticmethod
+    def _standard_index(body: bytes) -> List[Tuple[int, int]]:
+        """AVISTDINDEX (without its chunk header): (offset of the data, size) per entry."""
+        _, _, _, entries, _, base, _ = struct.unpack_from("<HBBI4sQI", body)
+        return [
+            (base + offset, size & 0x7FFFFFFF)  # bit 31: not a key frame
+            for offset, size in (struct.unpack_from("<II", body, 24 + 8 * i) for i in range(entries))
+        ]
+
+    # ---- public ---------------------------------------------------------------------------------------------------
+    def frame_sizes(self, first: int, count: int) -> List[int]:
+        """Byte counts of frames [first, first + count)."""
+        return [size for _, size in self._frames[first : first + count]]
+
+    def read_frame_into(self, index: int, out: np.ndarray) -> None:
+        """Frame `index`'s JFIF file into the uint8 array `out` of exactly its size (e.g. a slice of a pinned buffer)."""
+        offset, size = self._frames[index]
+        self._file.seek(offset)
+        if self._file.readinto(memoryview(out)) != size:  # type: ignore[attr-defined]
+            raise ValueError(f"{self._path}: frame {index} lies past the end of the file")
+
+    def read_frame_bytes(self, first: int, count: int) -> List[bytes]:
+        """The JFIF files of frames [first, first + count), one `bytes` each."""
+        if first < 0 or count < 0 or first + count > self.frame_count:
+            raise IndexError(f"frames [{first}, {first + count}) of {self.frame_count}")
+        out = []
+        for offset, size in self._frames[first : first + count]:
+            self._file.seek(offset)
+            data = self._file.read(size)
+            if len(data) != size:
+                raise ValueError(f"{self._path}: a frame lies past the end of the file")
+            out.append(data)
+        return out
+
+    def read_audio(self) -> Optional[Tuple[int, np.ndarray]]:
+        """(sample rate, samples [n] or [n, channels]) as `read_concatenated_wavs` gave them to the writer; None without audio."""
+        if self._audio_format is None:
+            return None
+        tag, channels, rate, bits = self._audio_format
+        kinds: Dict[Tuple[int, int], str] = {(1, 8): "u1", (1, 16): "<i2", (1, 32): "<i4", (1, 64): "<i8", (3, 32): "<f4", (3, 64): "<f8"}
+        if (tag, bits) not in kinds:
+            raise ValueError(f"{self._path}: audio format tag {tag} with {bits} bits per sample")
+        parts = []
+        for offset, size in self._audio_chunks:
+            self._file.seek(offset)
+            parts.append(self._file.read(size))
+        samples = np.frombuffer(b"".join(parts), dtype=kinds[(tag, bits)])
+        return rate, (samples.reshape(-1, channels) if channels > 1 else samples)
+
+    def close(self) -> None:
+        """Release the file."""
+        self._file.close()
+
+    def __enter__(self) -> "MjpegAviReader":
         return self
 
     def __exit__(self, *exc) -> None:

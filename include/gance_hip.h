@@ -380,6 +380,45 @@ int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t wi
                               void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                               int64_t* d_offsets, void* stream);
 
+/* ---- Motion-JPEG frame decoder -----------------------------------------------------------------
+ * The other half of the encoder above, and what frames_in_video (gance/image_sources/video_common.py:229-298) gets from
+ * cv2.VideoCapture: baseline sequential JFIF files (SOF0, 8 bit, three components sampled 2x1 / 1x1 / 1x1, one
+ * interleaved scan, any 8-bit DQT, any DHT or none (then the Annex K tables, the "AVI1" form), any DRI or none, width
+ * and height in [1, 8192]) decoded in HBM to uint8 [batch][height][width][3] RGB, equal pixel for pixel to libjpeg's
+ * default decode (jidctint.c jpeg_idct_islow with samples saturated to 0..255, jdsample.c h2v1_fancy_upsample, jdcolor.c
+ * ycc_rgb_convert). Restart segments decode in parallel; a file without DRI is one segment (correct, slow).
+ * gance_jpeg_parse_header: host only; `file` [file_bytes] is one JFIF file (host memory), `info` receives its
+ * description: sizes, restart interval (0 = none), where the entropy-coded data starts (scan_offset) and how many bytes
+ * follow it to the end of the file (scan_bytes: the EOI is found on the device), and per component (Y, Cb, Cr) the
+ * quantisation table (natural order) and the DC / AC Huffman tables (code counts per length 1..16, then the symbols).
+ * Returns GANCE_ERR_INVALID_ARGUMENT with the reason in gance_last_error for a file that is cut short or not of the
+ * form above (progressive or another SOFn, 4:2:0, 4:4:4, grey, 12-bit samples, a 16-bit DQT, more than one scan) or whose
+ * Huffman tables are not valid (more than 256 codes, an over-subscribed code, a DC category above 11).
+ * gance_jpeg_decode_bounds: host only; the workspace one decode call of `batch` frames of width x height whose files
+ * total `total_bytes` needs.
+ * gance_jpeg_decode_u8: d_data (device) holds the batch's files, frame b at [h_offsets[b], h_offsets[b + 1]) (h_offsets
+ * [batch + 1] and infos [batch] on the host, infos[b] as parsed from frame b: all of one width and height); d_workspace
+ * (device, 16-byte aligned); d_out (device) [batch][height][width][3]; d_status [batch] int32 (device) receives
+ * GANCE_JPEG_OK or the first reason frame b could not be decoded: its pixels are then unspecified, every other frame's
+ * are unaffected. No read leaves a frame's own byte range. Asynchronous on `stream` (the tables travel through a pinned
+ * buffer the library owns); a frame's pixels are a pure function of its bytes, the same whatever the batch.
+ * Returns GANCE_ERR_INVALID_ARGUMENT before touching a device for a NULL pointer, frames of different sizes, a
+ * description parse_header would not produce for the frame's range, or a workspace below the bounds. */
+enum { GANCE_JPEG_OK = 0, GANCE_JPEG_TRUNCATED = 1, GANCE_JPEG_INVALID_CODE = 2, GANCE_JPEG_MARKER_MISMATCH = 3 };
+typedef struct gance_jpeg_info {
+    int32_t width, height;
+    int32_t restart_interval;    /* MCUs (16 x 8 pixels) per restart segment, 0 = no restart markers */
+    int32_t has_huffman_tables;  /* 0: the file has no DHT and the Annex K tables were filled in */
+    uint64_t scan_offset, scan_bytes;
+    uint8_t quant[3][64];
+    uint8_t huff_bits[3][2][16]; /* [component][0 = DC, 1 = AC] */
+    uint8_t huff_values[3][2][256];
+} gance_jpeg_info;
+int gance_jpeg_parse_header(const uint8_t* file, uint64_t file_bytes, gance_jpeg_info* info);
+int gance_jpeg_decode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t total_bytes, uint64_t* workspace_bytes);
+int gance_jpeg_decode_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch,
+                         void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
+
 /* ---- debug-video panels ------------------------------------------------------------------------
  * Replaces the per-frame matplotlib drawing of the debug video: fig.canvas.draw() per frame in
  * render_current_matplotlib_frame (gance/data_into_network_visualization/visualization_common.py) under
