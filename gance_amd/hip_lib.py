@@ -255,6 +255,12 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
          ctypes.c_void_p],
     ),
+    "gance_debug_draw_text_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
+    ),
+    "gance_debug_font_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "gance_vec_rms_rolling_max": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p],
@@ -279,7 +285,7 @@ SIGNATURES = {
 ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
     "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8", "gance_jpeg_parse_header",
-    "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8",
+    "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8", "gance_debug_draw_text_u8", "gance_debug_font_columns",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -959,6 +965,36 @@ def debug_draw_panels_device(  # pylint: disable=too-many-arguments
             stream or None,
         ),
     )
+
+
+def debug_draw_text_device(  # pylint: disable=too-many-arguments
+    d_text: int, text_stride: int, x: int, y: int, max_width: int, scale: int, colour: Tuple[int, int, int], side: int, batch: int,
+    d_out: int, out_frame_stride: int, out_row_stride: int, stream: int = 0,
+) -> None:
+    """
+    One line of text per frame on one panel of `batch` debug frames, on top of what is there (draw it after
+    `debug_draw_panels_device`): frame b shows the bytes at d_text + b * text_stride (HBM) up to the first NUL or
+    `text_stride`, in the 5 x 7 font at `scale`, with its top-left corner at (x, y), in `colour` (r, g, b), clipped to the
+    panel and to `max_width` columns. Output addressing as `debug_draw_panels_device`. Asynchronous on `stream`.
+    :raises ValueError: a missing pointer, bad side, strides, alignment, text_stride, scale, max_width, position or batch.
+    """
+    lib = load_library()
+    red, green, blue = (int(channel) & 0xFF for channel in colour)
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_debug_draw_text_u8(
+            d_text or None, text_stride, x, y, max_width, scale, red | (green << 8) | (blue << 16), side, batch, d_out or None,
+            out_frame_stride, out_row_stride, stream or None,
+        ),
+    )
+
+
+def debug_font_columns() -> bytes:
+    """The 475 column bytes of the library's 5 x 7 font, ' ' to '~' (host only, no GPU needed)."""
+    lib = load_library()
+    table = (ctypes.c_uint8 * 475)()
+    _check(lib, lib.gance_debug_font_columns(table, ctypes.c_uint64(475)))
+    return bytes(table)
 
 
 class DebugView3d(ctypes.Structure):

@@ -22,10 +22,11 @@ API (the part of h5py's the projection reader uses): `File(path)` -> `.attrs` (d
 `group[name]`, `np.array(dataset)`, `.close()`.
 """
 
+import mmap
 import struct
 import zlib
 from pathlib import Path
-from typing import Any, Dict, Iterator, List, Optional, Tuple
+from typing import Any, Dict, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -46,9 +47,12 @@ class _Datatype:
 
 
 class _Reader:
-    """The file image and the low-level structure parsers."""
+    """
+    The file image (bytes, or a read-only mmap: every slice taken of it below is a `bytes` copy) and the low-level
+    structure parsers.
+    """
 
-    def __init__(self, data: bytes) -> None:
+    def __init__(self, data: Union[bytes, mmap.mmap]) -> None:
         self.data = data
         if data[:8] != SIGNATURE:
             raise UnsupportedHdf5("not an HDF5 file (superblock signature at offset 0)")
@@ -62,6 +66,13 @@ class _Reader:
         # root group symbol table entry follows base, free-space, end-of-file and driver addresses
         self.root_header = self.u64(pos + 32 + 8)
         self._heap_cache: Dict[int, Dict[int, bytes]] = {}
+
+    def _terminator(self, start: int) -> int:
+        """Offset of the first NUL at or after `start` (`find`: an mmap has no `index`)."""
+        end = self.data.find(b"\x00", start)
+        if end < 0:
+            raise ValueError("subsection not found")
+        return end
 
     def u8(self, pos: int) -> int:
         return self.data[pos]
@@ -106,7 +117,7 @@ class _Reader:
             raise UnsupportedHdf5("local heap signature")
         segment = self.u64(heap_address + 24)
         start = segment + offset
-        end = self.data.index(b"\x00", start)
+        end = self._terminator(start)
         return self.data[start:end].decode("utf-8")
 
     def group_links(self, btree: int, heap: int) -> Dict[str, int]:
@@ -155,11 +166,11 @@ class _Reader:
             at = body + used
             names = []
             for _ in range(members):
-                end = self.data.index(b"\x00", at)
+                end = self._terminator(at)
                 names.append(self.data[at:end].decode("utf-8"))
                 length = end - at + 1
                 at += length if version >= 3 else (length + 7) // 8 * 8
-            values = np.frombuffer(self.data, dtype=base.dtype, count=members, offset=at)
+            values = np.frombuffer(self.data[at : at + members * base.size], dtype=base.dtype, count=members)
             at += members * base.size
             return _Datatype("enum", size, base.dtype, base=base, enum={int(v): n for v, n in zip(values, names)}), at - pos
         if cls == 9:  # variable length
@@ -419,16 +430,32 @@ class Group:
 
 
 class File(Group):
-    """Read-only HDF5 file (the whole file is read into memory: projection files without histories are MBs)."""
+    """
+    Read-only HDF5 file, mapped into memory read-only: a projection file without histories is MBs, one with the latent
+    histories of a long projection is GBs, and only the datasets that are read are ever touched.
+    """
 
     def __init__(self, name, mode: str = "r") -> None:
         if mode != "r":
             raise ValueError("hdf5_lite is read-only")
-        reader = _Reader(Path(name).read_bytes())
-        super().__init__(reader, "/", reader.root_header + reader.base_address)
+        self._map: Optional[mmap.mmap] = None
+        with open(Path(name), "rb") as handle:  # (the mapping outlives the descriptor)
+            try:
+                self._map = mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ)
+            except ValueError as error:  # an empty file cannot be mapped
+                raise UnsupportedHdf5("not an HDF5 file (empty)") from error
+        try:
+            reader = _Reader(self._map)
+            super().__init__(reader, "/", reader.root_header + reader.base_address)
+        except BaseException:
+            self.close()
+            raise
 
     def close(self) -> None:
-        """Nothing to release (no file handle is kept)."""
+        """Release the mapping. Safe to call twice."""
+        if self._map is not None:
+            self._map.close()
+            self._map = None
 
     def __enter__(self) -> "File":
         return self

@@ -12,15 +12,20 @@ Two containers:
   read with h5py when it is importable and otherwise with this package's own pure-Python reader of the HDF5
   subset the reference's writer produces (hdf5_lite.py; real h5py-written fixtures in tests/golden/);
 * `.npz`, this implementation's container for environments without h5py: arrays `final_latents`
-  [F][W][L] float32, optional `target_images` / `final_images` [F][H][W][3] uint8 and a JSON
-  string `attributes` with the same attribute names.
+  [F][W][L] float32, optional `target_images` / `final_images` [F][H][W][3] uint8, optional
+  `latents_histories_<frame>` [steps][W][L] float32 (one array per projected frame, ragged across frames)
+  and a JSON string `attributes` with the same attribute names.
+
+The latent histories (`ProjectionFileReader.latents_histories`, :139-142, 188-194) and the reference's one-shot
+helpers (:303-457) serve gance_amd/projection/projection_visualization.py.
 """
 
+import itertools
 import json
 from dataclasses import dataclass, field, fields
 from pathlib import Path
 from types import TracebackType
-from typing import Any, Dict, Iterator, Optional, Tuple, Type
+from typing import Any, Dict, Iterator, List, Optional, Sequence, Tuple, Type
 
 import numpy as np
 
@@ -31,6 +36,7 @@ LATEST_VERSION = 2
 TARGET_IMAGES_GROUP_NAME = "target_images"
 FINAL_LATENTS_GROUP_NAME = "final_latents"
 FINAL_IMAGE_GROUP_NAME = "final_images"
+LATENTS_HISTORIES_GROUP_NAME = "latents_histories"
 
 
 @dataclass
@@ -136,6 +142,33 @@ class ProjectionFileReader:
         """The network's rendering of each final latent."""
         return (RGBInt8ImageType(image) for image in self._datasets(FINAL_IMAGE_GROUP_NAME))
 
+    @property
+    def latents_histories(self) -> Iterator[Iterator[SingleMatrix]]:
+        """
+        Per projected frame, the (W, L) latents of every projection step, early steps first. HDF5: the sub-groups
+        `latents_histories/latents_histories_<frame>` with datasets `latents_histories_<frame>_step_<step>` of (1, W, L)
+        float32 (projector_file_writer.py:749-755, 871-877); groups and datasets are each ordered by their trailing
+        integer, not by name (`step_10` comes after `step_2`). An empty or missing group yields nothing.
+
+        `images_histories` and `noises_histories` are not read: the reference's writer files them under each other's
+        names (the images group is created for the noises at :753 and filled with them at :865-869), so what a reader
+        of either group would return is not what its name says.
+        """
+        if self._npz is not None:
+            prefix = LATENTS_HISTORIES_GROUP_NAME + "_"
+            names = sorted((name for name in self._npz.files if name.startswith(prefix)), key=_trailing_int)
+            return ((SingleMatrix(step) for step in self._npz[name]) for name in names)
+        if LATENTS_HISTORIES_GROUP_NAME not in self._h5:
+            return iter(())
+        histories = self._h5[LATENTS_HISTORIES_GROUP_NAME]
+
+        def steps(group) -> Iterator[SingleMatrix]:
+            for name in sorted(group.keys(), key=_trailing_int):
+                item = np.array(group[name])
+                yield SingleMatrix(item[0] if item.ndim == 3 else item)
+
+        return (steps(histories[name]) for name in sorted(histories.keys(), key=_trailing_int))
+
     def close(self) -> None:
         """Release the file."""
         if self._h5 is not None:
@@ -180,6 +213,75 @@ def load_final_latents_matrices_label(projection_file_path: Path) -> MatricesLab
         return final_latents_matrices_label(reader)
 
 
+def _matrices_label(matrices: Iterator[SingleMatrix], label: str) -> MatricesLabel:
+    """The matrices concatenated along the last axis under `label`; an empty iterator is a StopIteration, as in the reference."""
+    collected = list(matrices)
+    if not collected:
+        raise StopIteration(f"Iterator labeled: {label} was empty!")
+    return MatricesLabel(data=ConcatenatedMatrices(np.concatenate(collected, axis=-1)), vector_length=collected[0].shape[-1], label=label)
+
+
+def _step_of_each_history(histories: Iterator[Iterator[SingleMatrix]], step: int) -> Iterator[SingleMatrix]:
+    """Entry `step` of every history, ending at the first history that is too short to have one (:303-319)."""
+    for history in histories:
+        taken = list(itertools.islice(history, step, step + 1))
+        if not taken:
+            return
+        yield taken[0]
+
+
+def projection_history_step_matrices_label(reader: ProjectionFileReader, projection_step: int) -> MatricesLabel:
+    """Step `projection_step` of every frame's latent history, concatenated like the final latents (:322-344)."""
+    attributes = reader.projection_attributes
+    return _matrices_label(
+        _step_of_each_history(reader.latents_histories, projection_step),
+        f"{Path(attributes.original_target_path).name} proj by {Path(attributes.original_network_path).name} step {projection_step}",
+    )
+
+
+def network_outputs_at_projection_step(projection_file_path: Path, network_interface, projection_step_to_take: int) -> Iterator[RGBInt8ImageType]:
+    """
+    One-shot helper: the image `network_interface.create_image_matrix` (a NetworkInterface of
+    gance_amd.network_interface.network_functions) makes of step `projection_step_to_take` of every frame's history (:347-371).
+    """
+    with load_projection_file(projection_file_path) as reader:
+        latents = list(_step_of_each_history(reader.latents_histories, projection_step_to_take))
+    for matrix in latents:
+        yield network_interface.create_image_matrix(matrix)
+
+
+def network_outputs_at_final_latents(projection_file_path: Path, network_interface) -> Iterator[RGBInt8ImageType]:
+    """One-shot helper: the network's image of every frame's final latents (:400-417)."""
+    with load_projection_file(projection_file_path) as reader:
+        latents = list(reader.final_latents)
+    for matrix in latents:
+        yield network_interface.create_image_matrix(matrix)
+
+
+def final_latents_at_frame(projection_file_path: Path, frame_number: int) -> SingleMatrix:
+    """One-shot helper: the final latents of projected frame `frame_number` (:387-397)."""
+    with load_projection_file(projection_file_path) as reader:
+        return next(itertools.islice(reader.final_latents, frame_number, frame_number + 1))
+
+
+def final_images(projection_file_path: Path) -> Iterator[RGBInt8ImageType]:
+    """One-shot helper: the final image of every projected frame (:420-430)."""
+    with load_projection_file(projection_file_path) as reader:
+        yield from reader.final_images
+
+
+def target_images(projection_file_path: Path) -> Iterator[RGBInt8ImageType]:
+    """One-shot helper: the target image of every projected frame (:433-443)."""
+    with load_projection_file(projection_file_path) as reader:
+        yield from reader.target_images
+
+
+def projection_attributes(projection_file_path: Path) -> ProjectionAttributes:
+    """One-shot helper: the file's metadata (:446-454)."""
+    with load_projection_file(projection_file_path) as reader:
+        return reader.projection_attributes
+
+
 def verify_projection_file_assumptions(projection_file_path: Path) -> None:
     """Every row of every final latent matrix is identical (projection_file_reader.py:236-260)."""
     with load_projection_file(projection_file_path) as reader:
@@ -188,7 +290,9 @@ def verify_projection_file_assumptions(projection_file_path: Path) -> None:
                 assert np.array_equal(matrix[0], row)
 
 
-def write_projection_npz(  # pylint: disable=too-many-arguments
+# (`target_images` and `final_images` below are this function's parameters, as they always were; inside it they hide the
+# one-shot helpers of the same names above, which it does not use)
+def write_projection_npz(  # pylint: disable=too-many-arguments,redefined-outer-name
     path: Path,
     final_latents: np.ndarray,
     projection_fps: float,
@@ -197,8 +301,13 @@ def write_projection_npz(  # pylint: disable=too-many-arguments
     original_target_path: str = "synthetic.mp4",
     original_network_path: str = "synthetic.pkl",
     final_images: Optional[np.ndarray] = None,
+    latents_histories: Optional[Sequence[np.ndarray]] = None,
 ) -> None:
-    """Write the `.npz` container (synthetic projections for tests and benchmarks)."""
+    """
+    Write the `.npz` container (synthetic projections for tests and benchmarks). `latents_histories`: per projected
+    frame an array [steps][W][L] (ragged across frames), stored as `latents_histories_<frame>`; it sets
+    `latents_histories_enabled`. Without it the file is what it was before histories existed.
+    """
     latents = np.asarray(final_latents, dtype=np.float32)
     attributes = {
         "version_number": LATEST_VERSION,
@@ -210,9 +319,13 @@ def write_projection_npz(  # pylint: disable=too-many-arguments
         "original_fps": float(projection_fps),
         "original_frame_count": int(latents.shape[0]),
     }
+    if latents_histories is not None:
+        attributes["latents_histories_enabled"] = True
     arrays = {"attributes": np.array(json.dumps(attributes)), FINAL_LATENTS_GROUP_NAME: latents}
     if target_images is not None:
         arrays[TARGET_IMAGES_GROUP_NAME] = np.asarray(target_images, dtype=np.uint8)
     if final_images is not None:
         arrays[FINAL_IMAGE_GROUP_NAME] = np.asarray(final_images, dtype=np.uint8)
+    for frame, history in enumerate(latents_histories if latents_histories is not None else ()):
+        arrays[f"{LATENTS_HISTORIES_GROUP_NAME}_{frame}"] = np.asarray(history, dtype=np.float32)
     np.savez(str(path), **arrays)

@@ -503,6 +503,20 @@ int gance_debug_scatter3d_u8(const uint8_t* d_chrome, int32_t side, const gance_
  * cursor is not finite) */
 int gance_debug_draw_scatter3d_u8(const uint8_t* d_template, int32_t side, const gance_debug_view3d* view, const gance_debug_frame* d_frames,
                                   int32_t batch, uint8_t* d_out, int64_t out_frame_stride, int64_t out_row_stride, void* stream);
+/* Per-frame text on one panel of `batch` consecutive frames (d_out and the strides as above), written ON TOP of what is
+ * there: call it after gance_debug_draw_panels_u8. The string of frame b is the bytes d_text[b * text_stride ...] (device)
+ * up to the first NUL, or all text_stride bytes; a byte outside 32 .. 126 is drawn as '?'. Glyph i of the 5 x 7 font
+ * (gance_amd/csrc/debug_font.h) covers the columns x + i * 6 * scale ... + 5 * scale - 1 and the rows y ... y + 7 * scale - 1;
+ * a pixel whose glyph bit is set becomes `rgb` (0x00BBGGRR: red in the low byte), opaque; no other pixel is written.
+ * Pixels are clipped to the panel and to the columns [x, x + max_width). side a multiple of 16 in [16, 4096], text_stride
+ * in [1, 256], scale in [1, 64], max_width >= 1, x and y in [0, side), batch >= 1, d_out and both strides 16-byte aligned,
+ * out_row_stride >= 3 * side and out_frame_stride >= a whole panel ((side - 1) rows + 3 * side). Asynchronous on `stream`, no host
+ * synchronisation; the bytes are a pure function of the arguments. */
+int gance_debug_draw_text_u8(const uint8_t* d_text, int32_t text_stride, int32_t x, int32_t y, int32_t max_width, int32_t scale,
+                             uint32_t rgb, int32_t side, int32_t batch, uint8_t* d_out, int64_t out_frame_stride,
+                             int64_t out_row_stride, void* stream);
+/* the font's table: 95 glyphs x 5 column bytes, bit 0 = top row (host only, no GPU needed); count must be 475 */
+int gance_debug_font_columns(uint8_t* h_out, uint64_t count);
 
 #ifdef __cplusplus
 }
