@@ -214,6 +214,9 @@ struct gance_engine {
     int debug_stop_after = 0;
     bool keep_skip_image = false;  // the caller will read the final fp32 skip image out of ybuf
     int last_act_layer = 0, last_act_c = 0, last_act_side = 0;
+    // the fp32 skip image the last ToRGB of the last eagerly launched call stored (nullptr: none ran, or it stored bytes only)
+    const float* last_rgb_y = nullptr;
+    int last_rgb_side = 0, last_rgb_batch = 0;
     hipStream_t last_stream = nullptr;
 };
 
@@ -564,6 +567,8 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
 
     int ycur = 0;  // ybuf index holding the current skip image
     bool have_y = false;
+    e->last_rgb_y = nullptr;
+    e->last_rgb_batch = B;
     const float* x_in = e->pool + e->const_off;  // zero-bordered [512][6][12], shared by the batch
     long long x_b_stride = 0;
     for (int li = 0; li < (int)plan.size(); ++li) {
@@ -592,6 +597,8 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                 o.epilogue = gance::kEpilogueRgb;
                 if (int rc = run_conv(e, li, step, x_in, x_b_stride, res, res, o, B, stream, &rgb)) return rc;
                 ycur = 1 - ycur;
+                e->last_rgb_y = (d_f32 != nullptr || e->keep_skip_image) ? e->ws->ybuf[ycur] : nullptr;
+                e->last_rgb_side = res;
                 break;
             }
             case Form::Direct:
@@ -660,7 +667,8 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
 
         if (step.torgb[0] != '\0') {
             const bool last = (c.res_log2 == e->res_log2);
-            const bool skip_y_store = step.may_skip_y_store && d_u8 != nullptr && d_f32 == nullptr && !e->keep_skip_image;
+            // (a call stopped by a debug tap keeps the image: gance_engine_debug_read_skip_image reads it)
+            const bool skip_y_store = step.may_skip_y_store && d_u8 != nullptr && d_f32 == nullptr && !e->keep_skip_image && e->debug_stop_after <= 0;
             const gance::ToRgbArgs t = torgb_args(e, ri, step, x_in, have_y ? e->ws->ybuf[ycur] : nullptr, e->ws->ybuf[have_y ? 1 - ycur : ycur],
                                                   last ? d_u8 : nullptr, skip_y_store, B);
             const double px = (double)B * res * res;
@@ -670,6 +678,8 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
             GANCE_HIP_CHECK(gance::launch_torgb(t, stream));
             if (have_y) ycur = 1 - ycur;
             have_y = true;
+            e->last_rgb_y = skip_y_store ? nullptr : e->ws->ybuf[ycur];
+            e->last_rgb_side = res;
         }
     }
     if (d_f32 != nullptr && (int)plan.size() == (int)e->convs.size()) {
@@ -1204,6 +1214,7 @@ static int host_call(gance_engine* e, const float* h_in, size_t in_floats, int b
         }
     }
     if (rc) return rc;
+    if (!plain) e->last_rgb_y = nullptr;  // (a replayed graph's launches were recorded by another call)
     if (e->debug_stop_after > 0) {
         GANCE_HIP_CHECK(hipStreamSynchronize(hs));
         hipEventRecord(ws->last_use, hs);
@@ -1372,6 +1383,24 @@ int gance_engine_debug_read_activation(gance_engine* engine, int32_t batch, floa
             std::memcpy(h_out + (bc * R + y) * R, &tmp[bc * act_plane(R) + (size_t)(y + 1) * (R + 8) + 4],
                         R * sizeof(float));
     if (out_channels) *out_channels = C;
+    if (out_side) *out_side = R;
+    return GANCE_OK;
+}
+
+int gance_engine_debug_read_skip_image(gance_engine* engine, int32_t batch, float* h_out, uint64_t max_floats, int32_t* out_side) {
+    if (engine == nullptr || h_out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (engine->last_rgb_y == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_skip_image: the engine's last call stored no fp32 skip image");
+    if (batch != engine->last_rgb_batch)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_skip_image: the engine's last call had " +
+                                                    std::to_string(engine->last_rgb_batch) + " frames, not " + std::to_string(batch));
+    gance::DeviceGuard guard(engine->cfg.device);
+    GANCE_HIP_CHECK(guard.status());
+    const int R = engine->last_rgb_side;
+    const size_t n = (size_t)batch * 3 * R * R;
+    if (n == 0 || n > max_floats) return fail(GANCE_ERR_INVALID_ARGUMENT, "skip image does not fit");
+    GANCE_HIP_CHECK(hipDeviceSynchronize());
+    GANCE_HIP_CHECK(hipMemcpy(h_out, engine->last_rgb_y, n * sizeof(float), hipMemcpyDeviceToHost));
     if (out_side) *out_side = R;
     return GANCE_OK;
 }

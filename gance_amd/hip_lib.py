@@ -144,6 +144,9 @@ SIGNATURES = {
             ctypes.POINTER(ctypes.c_int32),
         ],
     ),
+    "gance_engine_debug_read_skip_image": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _F32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)]
+    ),
     "gance_blend_create": (
         ctypes.c_int,
         [ctypes.POINTER(BlendConfig), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)],
@@ -286,6 +289,7 @@ ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
     "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8", "gance_jpeg_parse_header",
     "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8", "gance_debug_draw_text_u8", "gance_debug_font_columns",
+    "gance_engine_debug_read_skip_image",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -589,6 +593,40 @@ class Engine:
                 ),
             )
             return out.reshape(batch, channels.value, side.value, side.value)
+        finally:
+            self._lib.gance_engine_debug_stop_after(self._handle, 0)
+
+    def debug_image_after(self, dlatents: np.ndarray, num_conv_layers: int) -> np.ndarray:
+        """
+        Run only the first `num_conv_layers` conv layers and return the fp32 skip image [B, 3, res, res] the last ToRGB of that
+        call left. Stopped after an up layer this is the image of the resolution before it, whose Conv1 ran as it does in a whole
+        call (with the up layer's style on its stores where the plan has that); stopped after a Conv1, the same layer without it.
+        """
+        self._require_open()
+        dl = _f32(dlatents)
+        batch = dl.shape[0]
+        convs = sg2_spec.make_spec(self.resolution).convs
+        if not 1 <= num_conv_layers <= len(convs):
+            raise ValueError(f"num_conv_layers must be in [1, {len(convs)}], got {num_conv_layers}")
+        _check(self._lib, self._lib.gance_engine_debug_stop_after(self._handle, num_conv_layers))
+        try:
+            _check(
+                self._lib,
+                self._lib.gance_synthesize_w_host(self._handle, dl.ctypes.data_as(_F32P), batch, None, None),
+            )
+            last = convs[num_conv_layers - 1]
+            res = 2 ** (last.res_log2 - 1 if last.up else last.res_log2)
+            side = ctypes.c_int32()
+            out = np.empty((batch, 3, res, res), dtype=np.float32)
+            _check(
+                self._lib,
+                self._lib.gance_engine_debug_read_skip_image(
+                    self._handle, batch, out.ctypes.data_as(_F32P), ctypes.c_uint64(out.size), ctypes.byref(side)
+                ),
+            )
+            if side.value != res:
+                raise RuntimeError(f"the skip image is {side.value} wide, expected {res}")
+            return out
         finally:
             self._lib.gance_engine_debug_stop_after(self._handle, 0)
 

@@ -170,6 +170,14 @@ int gance_engine_debug_stop_after(gance_engine* engine, int32_t num_conv_layers)
 int gance_engine_debug_read_activation(gance_engine* engine, int32_t batch, float* h_out,
                                        uint64_t max_floats, int32_t* out_channels,
                                        int32_t* out_side);
+/*
+ * Debug: the fp32 skip image [batch][3][side][side] that the last ToRGB of the engine's last call left in the workspace, to
+ * host memory: after a call stopped by gance_engine_debug_stop_after, the image of the resolution it stopped in (stopped after
+ * an up layer: of the resolution before it, whose Conv1 then ran exactly as in a whole call). GANCE_ERR_INVALID_ARGUMENT when
+ * no ToRGB of that call stored an fp32 image (a bytes-only call of the largest resolutions; a call replayed from a graph),
+ * when `batch` is not that call's, or when the image exceeds `max_floats`.
+ */
+int gance_engine_debug_read_skip_image(gance_engine* engine, int32_t batch, float* h_out, uint64_t max_floats, int32_t* out_side);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Audio -> latent: spectrogram, fft-roll, alpha blend with projected latents                  */

@@ -189,6 +189,21 @@ def synthesis_layer(
     return apply_bias_act(x, _t(variables, f"{scope}/bias", dtype), "lrelu")
 
 
+def torgb_layer(
+    x: torch.Tensor, y_prev: Optional[torch.Tensor], dlatents: torch.Tensor, variables: Variables, res_log2: int
+) -> torch.Tensor:
+    """
+    One image step of `G_synthesis_stylegan2`, architecture 'skip' (its `torgb()` after `upsample()`): upsample_2d of the previous
+    resolution's image `y_prev` [B, 3, R/2, R/2] (None at 4x4) plus the modulated 1x1 conv of the activation `x` [B, C, R, R]
+    (no demodulation, dlatent row res_log2 * 2 - 3) plus bias. g_synthesis calls this at every resolution, so a ToRGB checked
+    in isolation is checked against exactly the arithmetic of the whole chain.
+    """
+    scope = f"G_synthesis/{2**res_log2}x{2**res_log2}/ToRGB"
+    t = modulated_conv2d_layer(x, dlatents[:, res_log2 * 2 - 3], variables, scope, 1, demodulate=False)
+    t = apply_bias_act(t, _t(variables, f"{scope}/bias", x.dtype), "linear")
+    return t if y_prev is None else upsample_2d(y_prev) + t
+
+
 def g_synthesis(
     dlatents: torch.Tensor,
     variables: Variables,
@@ -210,19 +225,13 @@ def g_synthesis(
     def layer(x: torch.Tensor, layer_idx: int, scope: str, up: bool) -> torch.Tensor:
         return synthesis_layer(x, dlatents, variables, ConvLayerRef(layer_idx, scope, up), noise_override)
 
-    def torgb(x: torch.Tensor, y: Optional[torch.Tensor], res: int) -> torch.Tensor:
-        scope = f"G_synthesis/{2**res}x{2**res}/ToRGB"
-        t = modulated_conv2d_layer(x, dlatents[:, res * 2 - 3], variables, scope, 1, demodulate=False)
-        t = apply_bias_act(t, _t(variables, f"{scope}/bias", dtype), "linear")
-        return t if y is None else y + t
-
     x = _t(variables, "G_synthesis/4x4/Const/const", dtype).repeat(batch, 1, 1, 1)
     x = layer(x, 0, "4x4/Conv", up=False)
     if collect is not None:
         collect.append(x)
     if stop_after == 1:
         return x
-    y = torgb(x, None, 2)
+    y = torgb_layer(x, None, dlatents, variables, 2)
     for res in range(3, res_log2 + 1):
         side = 2 ** res
         x = layer(x, res * 2 - 5, f"{side}x{side}/Conv0_up", up=True)
@@ -235,8 +244,7 @@ def g_synthesis(
             collect.append(x)
         if stop_after == res * 2 - 3:
             return x
-        y = upsample_2d(y)
-        y = torgb(x, y, res)
+        y = torgb_layer(x, y, dlatents, variables, res)
     return y
 
 

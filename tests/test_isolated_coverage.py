@@ -5,6 +5,10 @@ tests/isolated_small_cases.py (tests/test_isolated_small_layers_gpu.py, on a 128
 Layers from 256^2 up: the batches of tests/test_isolated_layers_gpu.py. A planner change that produces a new production form fails
 here, without a device, until an isolated check reaches it. gance_engine_describe_plan shares plan_call and the name-building code
 with the launch loop (tests/test_engine_plan.py).
+
+The image branch (ToRGB, skip image, bytes) is tied in the same way: every (ToRGB launch, "+rgb" on the conv in front of it) form the
+planner produces at any resolution, for both networks, and the two more of conv_form="direct", is reached by the case table of
+tests/isolated_image_cases.py (tests/test_isolated_image_gpu.py).
 """
 
 import json
@@ -15,6 +19,7 @@ from pathlib import Path
 
 import pytest
 
+import isolated_image_cases as image_cases
 import isolated_small_cases as cases
 from gance_amd import hip_lib
 
@@ -27,32 +32,43 @@ lib = ctypes.CDLL(sys.argv[1])
 num_cus, max_batch = int(sys.argv[2]), int(sys.argv[3])
 out = ctypes.create_string_buffer(1 << 16)
 plans = {}
-for resolution in json.loads(sys.argv[4]):
-    config = (ctypes.c_int32 * 4)(resolution, max_batch, 0, 0)  # gance_engine_config: resolution, max_batch, device, flags (default)
-    plans[resolution] = {}
+for resolution, flags in json.loads(sys.argv[4]):
+    config = (ctypes.c_int32 * 4)(resolution, max_batch, 0, flags)  # gance_engine_config: resolution, max_batch, device, flags
+    plans[f"{resolution}/{flags}"] = {}
     for batch in range(1, max_batch + 1):
         status = lib.gance_engine_describe_plan(config, ctypes.c_int32(num_cus), ctypes.c_int32(batch), out, ctypes.c_uint64(len(out)))
         assert status == 0, status
-        plans[resolution][batch] = out.value.decode().split()
+        plans[f"{resolution}/{flags}"][batch] = out.value.decode().split()
 print(json.dumps(plans))
 """
 
 
 @pytest.fixture(scope="module")
-def plans() -> dict:
-    """{resolution: {batch: {layer_idx: conv launch name}}} for the 1024^2 and 128^2 networks, default flags, 256 CUs, 1 ... 64 frames."""
+def launch_names() -> dict:
+    """{(resolution, conv_form): {batch: [launch names]}} for the 1024^2 and 128^2 networks with default flags and the 1024^2 one with
+    conv_form="direct", 256 CUs, 1 ... 64 frames."""
     if not hip_lib.LIBRARY_PATH.exists():
         import __graft_entry__  # pylint: disable=import-outside-toplevel
 
         __graft_entry__.build()
     env = {key: value for key, value in os.environ.items() if not key.startswith("GANCE_TUNE_")}
     child = subprocess.run(
-        [sys.executable, "-c", _CHILD, str(hip_lib.LIBRARY_PATH), str(cases.NUM_CUS), str(BATCHES[-1]), json.dumps([1024, 128])],
+        [sys.executable, "-c", _CHILD, str(hip_lib.LIBRARY_PATH), str(cases.NUM_CUS), str(BATCHES[-1]),
+         json.dumps([[1024, 0], [128, 0], [1024, hip_lib.GANCE_FLAG_DIRECT_CONV]])],
         check=True, env=env, capture_output=True, text=True, timeout=120,
     )
     return {
-        int(resolution): {int(batch): cases.conv_launches(names) for batch, names in by_batch.items()}
-        for resolution, by_batch in json.loads(child.stdout).items()
+        (int(key.split("/")[0]), "auto" if key.endswith("/0") else "direct"): {int(batch): names for batch, names in by_batch.items()}
+        for key, by_batch in json.loads(child.stdout).items()
+    }
+
+
+@pytest.fixture(scope="module")
+def plans(launch_names: dict) -> dict:
+    """{resolution: {batch: {layer_idx: conv launch name}}} for the 1024^2 and 128^2 networks, default flags, 256 CUs, 1 ... 64 frames."""
+    return {
+        resolution: {batch: cases.conv_launches(names) for batch, names in by_batch.items()}
+        for (resolution, conv_form), by_batch in launch_names.items() if conv_form == "auto"
     }
 
 
@@ -98,3 +114,68 @@ def test_every_large_layer_form_the_planner_produces_is_run_by_the_isolated_laye
     produced = {(idx, plans[1024][batch][idx]) for batch in BATCHES for idx in large}
     reached = _reached(plans[1024], [(batch, large) for batch in cases.LARGE_LAYER_BATCHES])
     assert produced == reached, f"not reached: {sorted(produced - reached)}"
+
+
+def test_the_image_case_table_is_well_formed() -> None:
+    assert sorted(image_cases.FORMS) == [4, 8, 16, 32, 64, 128, 256, 512, 1024]
+    assert sum(len(forms) for forms in image_cases.FORMS.values()) == 12
+    assert image_cases.NUM_CUS == cases.NUM_CUS
+    for resolution, forms in image_cases.FORMS.items():
+        firsts = [first for first, _, _ in forms]
+        assert firsts == sorted(set(firsts)) and firsts[0] == 1, resolution
+        network = 128 if resolution <= 128 else 1024
+        for first, name, partials in forms:  # every form is checked at the batch that first selects it, and ...
+            assert any(case[:3] == (network, "auto", first) and resolution in case[3] for case in image_cases.CASES), (resolution, first)
+            assert (name is None) == (partials == 0)
+        # ... in the last sample of a full call (<= 128^2) or of an odd one (the 1024^2 network)
+        assert any(case[:3] == (network, "auto", 64 if network == 128 else 3) and resolution in case[3] for case in image_cases.CASES)
+    for network, conv_form, batch, resolutions in image_cases.CASES:
+        assert network in (128, 1024) and 1 <= batch <= BATCHES[-1] and all(r <= network for r in resolutions)
+        assert conv_form == "auto" or resolutions == sorted(image_cases.DIRECT_FORMS)
+
+
+def test_every_image_form_the_planner_produces_has_an_isolated_case(launch_names: dict) -> None:
+    for key, by_batch in launch_names.items():
+        network, conv_form = key
+        produced = set()
+        for batch in BATCHES:
+            launches = image_cases.image_launches(by_batch[batch])
+            assert sorted(launches) == [r for r in image_cases.FORMS if r <= network], (key, batch)
+            for resolution, (torgb, conv) in launches.items():
+                if conv_form == "direct" and resolution <= 128:  # (the small kernel after a plain conv: the one-frame form of the table)
+                    assert image_cases.form_of(torgb, conv) == (f"torgb_{resolution}x{resolution}", ""), (key, batch, conv)
+                    continue
+                produced.add((resolution,) + image_cases.form_of(torgb, conv))
+                # the names the device test asserts on 256 CUs are the planner's, at every batch
+                name, partials = image_cases.expected_form(resolution, batch, conv_form)
+                kind, _, channels = conv.split("_")
+                if name is None:
+                    assert "+" not in kind and torgb != "", (key, batch, conv)
+                else:
+                    assert conv == name and (torgb == "") == ("+torgb" in name), (key, batch, conv)
+                if "+rgb" in kind:  # (F(4x4,3x3): a block holds 32 output channels of a pixel)
+                    assert kind.startswith("convV") and partials == int(channels.split("->")[1]) // 32, (key, batch, conv)
+                else:
+                    assert partials == 0, (key, batch, conv)
+        reached = set()
+        for case_network, case_form, batch, resolutions in image_cases.CASES:
+            if (case_network, case_form) == key:
+                launches = image_cases.image_launches(by_batch[batch])
+                reached |= {(resolution,) + image_cases.form_of(*launches[resolution]) for resolution in resolutions}
+        if key == (1024, "auto"):  # (its first six resolutions are checked on the 128^2 network, which plans them identically: below)
+            small = launch_names[(128, "auto")]
+            for batch in BATCHES:
+                assert {r: v for r, v in image_cases.image_launches(by_batch[batch]).items() if r <= 128} == image_cases.image_launches(small[batch])
+            produced = {form for form in produced if form[0] > 128}
+        assert produced == reached, f"{key}: not reached: {sorted(produced - reached)}"
+
+
+def test_the_default_image_forms_are_the_twelve_of_the_table(launch_names: dict) -> None:
+    produced = set()
+    for batch in BATCHES:
+        for resolution, (torgb, conv) in image_cases.image_launches(launch_names[(1024, "auto")][batch]).items():
+            produced.add((resolution, conv if "+rgb" in conv.split("_")[0] else None))
+    assert produced == {(resolution, name) for resolution, forms in image_cases.FORMS.items() for _, name, _ in forms}
+    direct = {(r, conv if "+" in conv.split("_")[0] else None)
+              for batch in BATCHES for r, (_, conv) in image_cases.image_launches(launch_names[(1024, "direct")][batch]).items() if r > 128}
+    assert direct == set(image_cases.DIRECT_FORMS.items())

@@ -146,3 +146,29 @@ def test_one_layer_continues_the_chain_bit_for_bit() -> None:
             assert torch.equal(ref.g_synthesis(dl, variables, resolution, noise_override=override, stop_after=n), chain[n - 1])
             got = ref.synthesis_layer(chain[n - 2], dl, variables, conv, noise_override=override)
             assert torch.equal(got, chain[n - 1]), f"conv layer {n} ({conv.scope})"
+
+
+def test_torgb_layer_and_synthesis_layer_chained_by_hand_are_the_chain_bit_for_bit(net32) -> None:
+    """
+    torgb_layer (one image step in isolation: tests/test_isolated_image_gpu.py feeds it the kernels' own activation and skip
+    image) and synthesis_layer chained by hand give g_synthesis's image exactly, in fp64, on the 32^2 network with every term
+    on (ToRGB biases included); 4x4 has no skip image; the same chain runs in float32 and tracks the fp64 one.
+    """
+    resolution = 32
+    spec = sg2_spec.make_spec(resolution)
+    assert any(np.abs(net32[f"G_synthesis/{2 ** r}x{2 ** r}/ToRGB/bias"]).max() > 0 for r in range(2, 6))
+    dl64 = torch.from_numpy(np.random.RandomState(9).randn(2, spec.num_layers, 512)).double()
+    images = {}
+    with torch.no_grad():
+        for dtype in (torch.float64, torch.float32):
+            dl = dl64.to(dtype)
+            x = torch.from_numpy(net32["G_synthesis/4x4/Const/const"]).to(dtype).repeat(2, 1, 1, 1)
+            y = None
+            for conv in spec.convs:
+                x = ref.synthesis_layer(x, dl, net32, conv)
+                if not conv.up:
+                    y = ref.torgb_layer(x, y, dl, net32, conv.res_log2)
+                    assert y.shape == (2, 3, 2 ** conv.res_log2, 2 ** conv.res_log2) and y.dtype == dtype
+            images[dtype] = y
+            assert torch.equal(y, ref.g_synthesis(dl, net32, resolution))
+    assert float((images[torch.float64] - images[torch.float32].double()).abs().max()) < 1e-4
