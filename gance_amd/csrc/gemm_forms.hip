@@ -24,9 +24,15 @@
 // TFLOP/s at 16x16: all 9 taps' flops). Here the three stages are three launches, the middle one the same GEMM kernel run as 36
 // independent products (one per Winograd position g; the rows of group g read B image g):
 //   1. winogemm_pack_kernel: V_g = (B^T (s x) B)_g of every 6 x 6 input window -> B image g, column n = sample * tiles + tile,
-//   2. tile_gemm_kernel: M_g[co][n] = sum_ci U_g[ci][co] V_g[ci][n], U = G w G^T (host, fp64, the matrices of winograd43_conv.hip),
+//   2. tile_gemm_kernel: M_g[co][n] = sum_ci U_g[ci][co] V_g[ci][n], U = G w G^T (host, fp64),
 //   3. winogemm_finish_kernel: A^T M A per (tile, channel), x demod, + noise + bias, leaky ReLU x sqrt 2 -> the bordered activation.
 // A quarter of the direct form's flops, every MFMA slot useful; 36 Cin N + 36 Cout N floats through HBM (150 MB at 16x16, batch 64).
+// The three transforms are separate code here, so this form takes the interpolation points 0, 1, -1, 1/2, -2, infinity instead of the
+// 0, +-1, +-2, infinity of winograd43_conv.hip (whose B^T and A^T are scheduled by hand): against fp64 the fp32 result is 2.2 ... 3 times
+// closer at K = 9 x 512 (a float32 restatement of both on a spatially rough 8x8 / 16x16 input: largest error of 16 samples 1.3e-5 /
+// 1.9e-5 of the output's range with +-2, 5.0e-6 / 6.4e-6 with 1/2, -2), at the same traffic; the transforms are a few more multiplies
+// in kernels that wait for memory. With +-2 the largest of 64 samples of the 8x8 layer reached 2.2e-5, past the 2e-5 the isolated
+// layer checks allow (tests/test_isolated_noise_gpu.py).
 //
 // (3) EXPERIMENT, off by default (GANCE_TUNE_GEMM_BF16X6 non-zero at engine creation): the same GEMMs on the bf16 matrix cores with fp32
 // accuracy. Each fp32 operand is split into three bf16 numbers that hold its 24 mantissa bits exactly (x = x0 + x1 + x2); a product is
@@ -327,24 +333,25 @@ __global__ __launch_bounds__(256) void winogemm_pack_kernel(const WinoGemmArgs p
         for (int r = 0; r < 6; ++r)
 #pragma unroll
             for (int c = 0; c < 6; ++c) d[r][c] = src[r * (p.W + 8) + c] * sv;
-        // B^T d: rows (4 d0 - 5 d2 + d4 | -4 d1 - 4 d2 + d3 + d4 | 4 d1 - 4 d2 - d3 + d4 | -2 d1 - d2 + 2 d3 + d4 | 2 d1 - d2 - 2 d3 + d4 | 4 d1 - 5 d3 + d5)
+        // B^T of the points 0, 1, -1, 1/2, -2, infinity: row j = the coefficients of prod over the other finite points (x - p), the
+        // last row of prod over all five
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
-            t[0][c] = 4.f * d[0][c] - 5.f * d[2][c] + d[4][c];
-            t[1][c] = -4.f * (d[1][c] + d[2][c]) + d[3][c] + d[4][c];
-            t[2][c] = 4.f * (d[1][c] - d[2][c]) - d[3][c] + d[4][c];
+            t[0][c] = d[0][c] - 1.5f * d[1][c] - 2.f * d[2][c] + 1.5f * d[3][c] + d[4][c];
+            t[1][c] = -d[1][c] + 0.5f * d[2][c] + 2.5f * d[3][c] + d[4][c];
+            t[2][c] = d[1][c] - 2.5f * d[2][c] + 0.5f * d[3][c] + d[4][c];
             t[3][c] = -2.f * d[1][c] - d[2][c] + 2.f * d[3][c] + d[4][c];
-            t[4][c] = 2.f * d[1][c] - d[2][c] - 2.f * d[3][c] + d[4][c];
-            t[5][c] = 4.f * d[1][c] - 5.f * d[3][c] + d[5][c];
+            t[4][c] = 0.5f * d[1][c] - d[2][c] - 0.5f * d[3][c] + d[4][c];
+            t[5][c] = d[1][c] - 1.5f * d[2][c] - 2.f * d[3][c] + 1.5f * d[4][c] + d[5][c];
         }
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
-            v[r][0] = 4.f * t[r][0] - 5.f * t[r][2] + t[r][4];
-            v[r][1] = -4.f * (t[r][1] + t[r][2]) + t[r][3] + t[r][4];
-            v[r][2] = 4.f * (t[r][1] - t[r][2]) - t[r][3] + t[r][4];
+            v[r][0] = t[r][0] - 1.5f * t[r][1] - 2.f * t[r][2] + 1.5f * t[r][3] + t[r][4];
+            v[r][1] = -t[r][1] + 0.5f * t[r][2] + 2.5f * t[r][3] + t[r][4];
+            v[r][2] = t[r][1] - 2.5f * t[r][2] + 0.5f * t[r][3] + t[r][4];
             v[r][3] = -2.f * t[r][1] - t[r][2] + 2.f * t[r][3] + t[r][4];
-            v[r][4] = 2.f * t[r][1] - t[r][2] - 2.f * t[r][3] + t[r][4];
-            v[r][5] = 4.f * t[r][1] - 5.f * t[r][3] + t[r][5];
+            v[r][4] = 0.5f * t[r][1] - t[r][2] - 0.5f * t[r][3] + t[r][4];
+            v[r][5] = t[r][1] - 1.5f * t[r][2] - 2.f * t[r][3] + 1.5f * t[r][4] + t[r][5];
         }
     } else {
 #pragma unroll
@@ -392,14 +399,15 @@ __global__ __launch_bounds__(256) void winogemm_finish_kernel(const WinoGemmArgs
     for (int r = 0; r < 6; ++r)
 #pragma unroll
         for (int c = 0; c < 6; ++c) m[r][c] = src[(size_t)(r * 6 + c) * group];
-    // A^T m: rows (m0 + m1 + m2 + m3 + m4 | m1 - m2 + 2 (m3 - m4) | m1 + m2 + 4 (m3 + m4) | m1 - m2 + 8 (m3 - m4) + m5)
+    // A^T m: row i = sum_j p_j^i m_j over the points 0, 1, -1, 1/2, -2, and m5 (infinity) in the last:
+    // (m0 + m1 + m2 + m3 + m4 | m1 - m2 + m3 / 2 - 2 m4 | m1 + m2 + m3 / 4 + 4 m4 | m1 - m2 + m3 / 8 - 8 m4 + m5)
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-        const float s12 = m[1][c] + m[2][c], d12 = m[1][c] - m[2][c], s34 = m[3][c] + m[4][c], d34 = m[3][c] - m[4][c];
-        t[0][c] = m[0][c] + s12 + s34;
-        t[1][c] = d12 + 2.f * d34;
-        t[2][c] = s12 + 4.f * s34;
-        t[3][c] = d12 + 8.f * d34 + m[5][c];
+        const float s12 = m[1][c] + m[2][c], d12 = m[1][c] - m[2][c];
+        t[0][c] = m[0][c] + s12 + (m[3][c] + m[4][c]);
+        t[1][c] = d12 + (0.5f * m[3][c] - 2.f * m[4][c]);
+        t[2][c] = s12 + (0.25f * m[3][c] + 4.f * m[4][c]);
+        t[3][c] = d12 + (0.125f * m[3][c] - 8.f * m[4][c]) + m[5][c];
     }
     const float d = p.d[(size_t)b * p.d_stride + co];
     const float bias = p.bias[co];
@@ -408,8 +416,9 @@ __global__ __launch_bounds__(256) void winogemm_finish_kernel(const WinoGemmArgs
     float* const dst = p.out + (size_t)b * p.out_b_stride + ((size_t)co * (p.H + 2) + oy0 + 1) * (p.W + 8) + ox0 + 4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const float s12 = t[r][1] + t[r][2], d12 = t[r][1] - t[r][2], s34 = t[r][3] + t[r][4], d34 = t[r][3] - t[r][4];
-        f32x4 y = {t[r][0] + s12 + s34, d12 + 2.f * d34, s12 + 4.f * s34, d12 + 8.f * d34 + t[r][5]};
+        const float s12 = t[r][1] + t[r][2], d12 = t[r][1] - t[r][2];
+        f32x4 y = {t[r][0] + s12 + (t[r][3] + t[r][4]), d12 + (0.5f * t[r][3] - 2.f * t[r][4]), s12 + (0.25f * t[r][3] + 4.f * t[r][4]),
+                   d12 + (0.125f * t[r][3] - 8.f * t[r][4]) + t[r][5]};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float v = y[c] * d + bias;
@@ -488,8 +497,9 @@ size_t winogemm_prod_floats(int B, int cout, int H, int W) { return (size_t)wino
 
 // A image of the 36 products: GEMM row m = position g * cout + channel, g = 6 r + c of U = G w G^T (r along y)
 void winogemm_arrange_weights(const float* w_in, int cin, int cout, float* w_out) {
-    const double G[6][3] = {{1. / 4, 0., 0.},          {-1. / 6, -1. / 6, -1. / 6}, {-1. / 6, 1. / 6, -1. / 6},
-                            {1. / 24, 1. / 12, 1. / 6}, {1. / 24, -1. / 12, 1. / 6}, {0., 0., 1.}};
+    // G of the points 0, 1, -1, 1/2, -2, infinity: row j = (1, p_j, p_j^2) / prod over the other finite points (p_j - p)
+    const double G[6][3] = {{1., 0., 0.},          {1. / 3, 1. / 3, 1. / 3}, {-1. / 3, 1. / 3, -1. / 3}, {-16. / 15, -8. / 15, -4. / 15},
+                            {1. / 15, -2. / 15, 4. / 15}, {0., 0., 1.}};
     const int chunks = cin / kGK;
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci) {

@@ -6,6 +6,11 @@ On 256 CUs with the default flags and no GANCE_TUNE_* knob, conv layers 0 ... 10
 distinct (layer, form) launches; FORMS lists them with the smallest batch that selects each (a form holds from its batch up to the
 next entry's). CASES visits every batch at which a form first appears and checks there only the layers whose form is new, plus the
 whole chain at one frame and at 64 (the batch bench.py and the stream issue: the forms of 18 frames, every launch at full occupancy).
+
+NOISE_CASES is the table of tests/test_isolated_noise_gpu.py, which runs the layers with a noise plane per sample
+(gance_engine_randomize_noise: sample b reads noise + b * noise_b_stride). It is derived from FORMS: every (layer, form) once, at the
+LARGEST batch that still selects it, so that as many samples as possible have b > 0. LARGE_NOISE_CASES are the calls that test makes
+of the 256^2 ... 1024^2 layers.
 """
 
 from typing import Dict, List, Tuple
@@ -41,6 +46,46 @@ CASES: List[Tuple[int, List[int]]] = [
     (18, [5]),
     (64, list(range(11))),
 ]
+
+MAX_BATCH = CASES[-1][0]  # the largest call FORMS describes
+
+
+def last_batch(layer_idx: int, form: int) -> int:
+    """The largest batch that selects the form-th entry of FORMS[layer_idx]: one below the next entry's first, MAX_BATCH for the last."""
+    forms = FORMS[layer_idx]
+    return forms[form + 1][0] - 1 if form + 1 < len(forms) else MAX_BATCH
+
+
+def _noise_cases() -> List[Tuple[int, List[int]]]:
+    by_batch: Dict[int, List[int]] = {}
+    for idx in sorted(FORMS):
+        for form in range(len(FORMS[idx])):
+            by_batch.setdefault(last_batch(idx, form), []).append(idx)
+    return sorted(by_batch.items())
+
+
+# (frames per call, layer_idx checked there with a noise plane per sample): each form at the last batch of its range
+NOISE_CASES: List[Tuple[int, List[int]]] = _noise_cases()
+
+# (conv_form, frames per call) of the per-sample-noise checks of layers 11 ... 16 (1024^2 network), which have one form each over
+# 2 ... 64 frames: 9 frames (one row segment at 1024^2: the geometry of 64-frame calls), and the direct form (the conv_mfma.hip
+# tiles; the debug tap on conv16+torgb runs the unfused launch). A case of 3 frames (4 row segments) passed and was left out for its
+# time (tests/test_isolated_noise_gpu.py).
+LARGE_NOISE_CASES: List[Tuple[str, int]] = [("auto", 9), ("direct", 2)]
+
+# conv_form -> {layer_idx: conv launch name} of layers 11 ... 16 in a 1024^2 call of 2 ... 64 frames on 256 CUs
+LARGE_NOISE_FORMS: Dict[str, Dict[int, str]] = {
+    "auto": {
+        11: "convTFp11_256x256_256->128/s3", 12: "convV12+rgb_256x256_128->128",
+        13: "convTFp13_512x512_128->64/s3", 14: "convV14+rgb_512x512_64->64",
+        15: "convTFp15_1024x1024_64->32/s3", 16: "convV16+rgb_1024x1024_32->32",
+    },
+    "direct": {
+        11: "convTF11_256x256_256->128/s3", 12: "conv12_256x256_128->128",
+        13: "convTF13_512x512_128->64/s3", 14: "conv14_512x512_64->64",
+        15: "convTF15_1024x1024_64->32/s3", 16: "conv16+torgb_1024x1024_32->32",
+    },
+}
 
 # the batches tests/test_isolated_layers_gpu.py runs the 256^2 ... 1024^2 layers at on 256 CUs (16 / 8 / 4 / 2 / 1 row segments)
 LARGE_LAYER_BATCHES = (1, 2, 3, 5, 9)

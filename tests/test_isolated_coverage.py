@@ -9,6 +9,10 @@ with the launch loop (tests/test_engine_plan.py).
 The image branch (ToRGB, skip image, bytes) is tied in the same way: every (ToRGB launch, "+rgb" on the conv in front of it) form the
 planner produces at any resolution, for both networks, and the two more of conv_form="direct", is reached by the case table of
 tests/isolated_image_cases.py (tests/test_isolated_image_gpu.py).
+
+The checks with a noise plane per sample (tests/test_isolated_noise_gpu.py) have a table of their own, NOISE_CASES, derived from FORMS:
+every (layer, form) once, at the last batch of its range. It is held here to the table it must come out as and to the planner, and
+the calls of the 256^2 ... 1024^2 layers to every form those layers take over 2 ... 64 frames.
 """
 
 import json
@@ -114,6 +118,67 @@ def test_every_large_layer_form_the_planner_produces_is_run_by_the_isolated_laye
     produced = {(idx, plans[1024][batch][idx]) for batch in BATCHES for idx in large}
     reached = _reached(plans[1024], [(batch, large) for batch in cases.LARGE_LAYER_BATCHES])
     assert produced == reached, f"not reached: {sorted(produced - reached)}"
+
+
+def test_the_noise_case_table_is_the_one_derived_from_the_forms() -> None:
+    assert cases.NOISE_CASES == [
+        (1, [3, 10]), (2, [9]), (3, [4, 8, 9]), (5, [5]), (7, [1, 7]), (8, [7]), (15, [2, 6, 7]), (17, [5]), (64, list(range(11))),
+    ]
+    assert cases.LARGE_NOISE_CASES == [("auto", 9), ("direct", 2)]  # (("auto", 3) was dropped for its time)
+
+
+def test_the_noise_cases_visit_every_small_layer_form_once_at_the_last_batch_of_its_range(plans: dict) -> None:
+    visits = [(idx, cases.expected_name(idx, batch), batch) for batch, layers in cases.NOISE_CASES for idx in layers]
+    forms = [(idx, name) for idx, by_first in cases.FORMS.items() for _, name in by_first]
+    assert sorted((idx, name) for idx, name, _ in visits) == sorted(forms)  # each exactly once
+    for idx, name, batch in visits:
+        # the planner's name at that batch is the expected one, on both networks ...
+        assert plans[1024][batch][idx] == name and plans[128][batch][idx] == name, (idx, batch)
+        # ... and the batch is the last that selects the form: no larger call does
+        assert batch <= cases.MAX_BATCH == BATCHES[-1] and all(plans[1024][b][idx] != name for b in BATCHES if b > batch), (idx, batch)
+
+
+def test_the_large_noise_batches_reach_every_form_of_two_to_64_frames(launch_names: dict) -> None:
+    large = list(range(cases.LAST_SMALL_LAYER + 1, 17))
+    for conv_form, forms in cases.LARGE_NOISE_FORMS.items():
+        by_batch = {batch: cases.conv_launches(names) for batch, names in launch_names[(1024, conv_form)].items()}
+        produced = {(idx, by_batch[batch][idx]) for batch in BATCHES[1:] for idx in large}
+        assert produced == set(forms.items())  # one form each over 2 ... 64 frames: the names the device test asserts on 256 CUs
+        for case_form, batch in cases.LARGE_NOISE_CASES:
+            if case_form == conv_form:
+                assert batch >= 2 and {(idx, by_batch[batch][idx]) for idx in large} == produced, (conv_form, batch)
+    assert sorted({form for form, _ in cases.LARGE_NOISE_CASES}) == sorted(cases.LARGE_NOISE_FORMS)
+
+
+def test_the_oracle_layer_for_another_plane_follows_from_its_result() -> None:
+    """with_other_plane of tests/test_isolated_noise_gpu.py (the sensitivity condition there) against a second call of the oracle layer."""
+    import numpy as np  # pylint: disable=import-outside-toplevel
+    import torch  # pylint: disable=import-outside-toplevel
+
+    import test_isolated_noise_gpu as noise_checks  # pylint: disable=import-outside-toplevel
+    from gance_amd.stylegan2 import spec as sg2_spec  # pylint: disable=import-outside-toplevel
+    from oracle import stylegan2_ref as ref  # pylint: disable=import-outside-toplevel
+
+    resolution = 8
+    spec = sg2_spec.make_spec(resolution)
+    variables = dict(sg2_spec.make_random_variables(resolution, seed=3, perturb=True))
+    rng = np.random.RandomState(0)
+    w = torch.from_numpy(rng.randn(1, spec.num_layers, 512))
+    x = torch.from_numpy(np.asarray(variables["G_synthesis/4x4/Const/const"], dtype=np.float64))
+    for conv in spec.convs:  # 4x4 Conv, 8x8 Conv0_up, 8x8 Conv1
+        strength = 0.5 * (-1) ** conv.layer_idx
+        variables[f"G_synthesis/{conv.scope}/noise_strength"] = np.float32(strength)
+        side = 2 ** conv.res_log2
+        own, other = rng.randn(2, side, side).astype(np.float32)
+        stored = np.asarray(variables[f"G_synthesis/noise{conv.layer_idx}"]).reshape(side, side)
+        with torch.no_grad():
+            want = ref.synthesis_layer(x, w, variables, conv, noise_override={conv.layer_idx: torch.from_numpy(own[None, None])})
+            for plane, override in ((other, {conv.layer_idx: torch.from_numpy(other[None, None])}), (stored, None)):
+                again = ref.synthesis_layer(x, w, variables, conv, noise_override=override).numpy()[0]
+                worked_out = noise_checks.with_other_plane(want.numpy()[0], own, plane, strength)
+                assert np.abs(again - want.numpy()[0]).max() > 0.1 * np.abs(again).max()  # (the planes matter)
+                assert np.abs(worked_out - again).max() < 1e-12 * np.abs(again).max()
+        x = want
 
 
 def test_the_image_case_table_is_well_formed() -> None:
