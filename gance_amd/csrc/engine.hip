@@ -483,8 +483,7 @@ gance::UpFirArgs upfir_args(const gance_engine* e, int li, const LayerStep& step
     gance::UpFirArgs u = step.up;
     u.pair_form = step.form == Form::UpFused16x ? 1 : 0;
     u.x = x;
-    u.w = e->pool + (step.form == Form::UpSplit ? caps.w[kUpfirSplit]
-                                                : (step.form == Form::UpFused16x ? caps.w[kUpfir16x] : (step.form == Form::UpFused16 ? caps.w[kUpfir16] : caps.w[kUpfir])));
+    u.w = e->pool + (step.form == Form::UpSplit ? caps.w[kUpfirSplit] : (step.form == Form::UpFused16x ? caps.w[kUpfir16x] : caps.w[kUpfir16]));
     u.s = e->ws->styles + e->conv_s_off[li];
     u.d = e->ws->demod + e->conv_d_off[li];
     u.noise = layer_noise(e, li, &u.noise_b_stride);
@@ -630,15 +629,13 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                                                             e->pool + e->conv_bias[li], x_out, B, c.cout, res, res, stream));
                 break;
             }
-            case Form::UpFused:
             case Form::UpFused16:
             case Form::UpFused16x:
             case Form::UpSplit: {
                 const gance::UpFirArgs u = upfir_args(e, li, step, x_in, x_b_stride, x_out, B, s_next);
                 StepScope scope(e, stream, step.name, 2.0 * 9 * (double)c.cin * c.cout * H * H * B,
                                 4.0 * ((double)B * c.cin * H * H + (double)B * c.cout * res * res + 9.0 * c.cin * c.cout));
-                GANCE_HIP_CHECK(step.form == Form::UpSplit ? gance::launch_upfir_split(u, stream)
-                                                           : (step.form == Form::UpFused ? gance::launch_upfir_fused(u, stream) : gance::launch_upfir16_fused(u, stream)));
+                GANCE_HIP_CHECK(step.form == Form::UpSplit ? gance::launch_upfir_split(u, stream) : gance::launch_upfir16_fused(u, stream));
                 break;
             }
             case Form::UpGemm:
@@ -910,8 +907,6 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
          [](const float* w, int ci, int co, int, float* out) { gance::winograd64_transform_weights(w, ci, co, out); }},
         {[](int ci, int co, int) { return gance::winograd43_weight_floats(ci, co); },
          [](const float* w, int ci, int co, int, float* out) { gance::winograd43_transform_weights(w, ci, co, out); }},
-        {[](int ci, int co, int) { return gance::upfir_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::upfir_arrange_weights(w, ci, co, kUpTapWeight, out); }},
         {[](int ci, int co, int) { return gance::upfir16_weight_floats(ci, co); },
          [](const float* w, int ci, int co, int, float* out) { gance::upfir16_arrange_weights(w, ci, co, kUpTapWeight, out); }},
         {[](int ci, int co, int split) { return gance::winogemm_weight_floats(ci, co) * (split ? 3 : 2) / 2; },
@@ -946,7 +941,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         {
             // the direct form's LDS image:
             // [m tile][K chunk][tap slot][KC][BM], slot t of an up layer = filter tap kUpTapWeight[t]
-            const int BM = layer_bm(c.cout), KC = layer_kc(c.cout, c.up, e->tune);
+            const int BM = layer_bm(c.cout), KC = layer_kc(c.cout, c.up);
             const int m_tiles = c.cout / BM, chunks = c.cin / KC;
             float* w = &pool[caps.direct_w];
             float* w2 = &pool[e->w2_off + w2_cursor];

@@ -38,15 +38,9 @@ int layer_bm(int cout) { return cout == 32 ? 32 : (cout == 64 ? 64 : 128); }
 // the only place that looks at the environment. All fields are read ONCE PER PROCESS (several size the workspace, which engines
 // share) except `engine`, read each time an engine is created (tests set those between engines of one process).
 struct Tuning {
-    int kc_conv = 4;   // GANCE_TUNE_KC_CONV = 4 or 8: K chunk (input channels per LDS stage) of the narrow stride-1 layers
-    int kc_up = 8;     // GANCE_TUNE_KC_UP = 8 or 4: the same of the narrow transposed convs
-    int kc_up128 = 4;  // GANCE_TUNE_KC_UP128 = 2: the wide transposed convs stage 2 input channels per chunk (tile 14)
     // GANCE_TUNE_STRIPS_MIN: smallest input side whose wide transposed conv takes the strip tiles; default 16. Strips pay once the
     // position grid has several tiles per side; below that the launch is latency-bound and extra blocks only hurt
     int strips_min = 16;
-    // GANCE_TUNE_UPFIR16: geometry of the fused up kernel. 0: always 32 channels per block, one block per CU (upfir_fused.hip); 1: 16
-    // channels per block, two blocks per CU (upfir16_fused.hip) wherever that kernel supports the layer.
-    int upfir16 = 1;
     // GANCE_TUNE_UPFIR16X = 0: the fused up layers whose input the 64-column strips tile stay in direct form; 1 (default): they run in
     // the pair form (F(2,2) along x) when their input arrives pre-scaled.
     int upfir16x = 1;
@@ -100,11 +94,7 @@ struct Tuning {
 Tuning read_tuning() {
     Tuning t;
     const auto number = [](const char* name, int unset) { const char* v = std::getenv(name); return v ? std::atoi(v) : unset; };
-    t.kc_conv = number("GANCE_TUNE_KC_CONV", 4) == 8 ? 8 : 4;
-    t.kc_up = number("GANCE_TUNE_KC_UP", 8) == 4 ? 4 : 8;
-    t.kc_up128 = number("GANCE_TUNE_KC_UP128", 4) == 2 ? 2 : 4;
     t.strips_min = number("GANCE_TUNE_STRIPS_MIN", 16);
-    t.upfir16 = number("GANCE_TUNE_UPFIR16", 1);
     t.upfir16x = number("GANCE_TUNE_UPFIR16X", 1);
     t.upgemm_min_columns = number("GANCE_TUNE_UPGEMM", 128);
     t.upgemm_buffer_columns = std::max(4096, number("GANCE_TUNE_UPGEMM_COLUMNS", 16384));
@@ -140,15 +130,16 @@ Tuning engine_tuning() {  // the process's values, with the per-engine ones as t
     return t;
 }
 
-int tuned_kc(bool up, const Tuning& tune) { return up ? tune.kc_up : tune.kc_conv; }
-int layer_kc(int cout, bool up, const Tuning& tune) { return layer_bm(cout) == 128 ? (up ? tune.kc_up128 : 4) : tuned_kc(up, tune); }
+// K chunk (input channels per LDS stage) of the direct form's tiles: 8 in the narrow transposed convs (Cout 32 / 64), 4 everywhere else
+int layer_kc(int cout, bool up) { return up && layer_bm(cout) != 128 ? 8 : 4; }
 
-int choose_tile(int cout, bool up, int OH, int OW, int B, const Tuning& tune) {
-    const bool kc4 = tuned_kc(up, tune) == 4;
-    if (cout == 32) return up ? (kc4 ? 12 : 6) : (kc4 ? 10 : 0);
-    if (cout == 64) return up ? (kc4 ? 13 : 7) : (kc4 ? 11 : 1);
-    if (up) return tune.kc_up128 == 2 ? 14 : 8;
-    const int first = 2, last = 5;
+// The direct form's tile (gance::kConvTiles) of a layer
+int choose_tile(int cout, bool up, int OH, int OW, int B) {
+    if (cout == 32) return up ? 6 : 4;  // 512 -> 1024 / the 1024^2 layers
+    if (cout == 64) return up ? 7 : 5;  // 256 -> 512 / the 512^2 layers
+    if (up) return 8;                   // every up layer with Cout >= 128: runtime geometry
+    // the stride-1 layers with Cout >= 128 (4^2 ... 256^2): the tile that covers the grid and the samples in the fewest blocks
+    const int first = 0, last = 3;
     int best = first;
     long best_tiles = -1;
     for (int id = first; id <= last; ++id) {
@@ -176,7 +167,7 @@ LayerPlan plan_layer(const ConvLayerHost& c, int B, const Tuning& tune) {
     const bool strips = c.up && layer_bm(c.cout) == 128 && res / 2 >= tune.strips_min;  // (Tuning::strips_min says why)
     const int grid = c.up ? (strips ? res / 2 : res / 2 + 1) : res;  // the tiled grid
     p.OH = p.OW = c.up ? res / 2 + 1 : res;
-    p.tile_id = choose_tile(c.cout, c.up, grid, grid, B, tune);
+    p.tile_id = choose_tile(c.cout, c.up, grid, grid, B);
     const auto& t = gance::kConvTiles[p.tile_id];
     p.tiles_x = ceil_div(grid, t.TW);
     p.tiles_y = ceil_div(grid, t.TH);
@@ -212,8 +203,7 @@ enum WeightImage {
     kWino,        // Winograd F(2x2,3x3), the round-1 32-channel kernel (winograd_conv.hip)
     kWino64,      // the same on 16x16x4 MFMAs (winograd64_conv.hip: layers with >= 64 output channels, and the 32-channel last layer)
     kWino43,      // Winograd F(4x4,3x3) (winograd43_conv.hip)
-    kUpfir,       // fused transposed conv + FIR, 32 channels per block (upfir_fused.hip)
-    kUpfir16,     // ... its 16-channel, two-blocks-per-CU geometry (upfir16_fused.hip)
+    kUpfir16,     // fused transposed conv + FIR on the fp32 matrix cores, 16 channels per block, two blocks per CU (upfir16_fused.hip)
     kWinoGemm,    // Winograd F(4x4,3x3) as 36 dense GEMMs, the stride-1 layers at 8x8 ... 128x128 (gemm_forms.hip)
     kUpGemm,      // scatter-form GEMM of the small up layers (gemm_forms.hip)
     kUpfirSplit,  // split-operand form of the fused up kernel (upfir_split.hip: three bf16 parts per value, six terms, fp32 accumulation)
@@ -240,13 +230,11 @@ LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, 
         // (the experiment's 256-row block tiles need Cout to be a multiple of 256: a 128-channel layer of a reduced network keeps the fp32 GEMM)
         k.gemm_split = c.cout % 256 == 0 ? tune.engine.gemm_bf16 : 0;
     } else {
-        const bool geometry16 = tune.upfir16 != 0 && gance::upfir16_supported(c.cin, c.cout, H, H);
-        k.has[kUpfir] = gance::upfir_supported(c.cin, c.cout, H, H) && !geometry16;  // (the 32-channel kernel's image only where the 16-channel kernel will not take the layer)
-        k.has[kUpfir16] = geometry16;
+        k.has[kUpfir16] = gance::upfir16_supported(c.cin, c.cout, H, H);
         k.has[kUpGemm] = tune.upgemm_min_columns > 0 && gance::upgemm_supported(c.cin, c.cout, H, H);
-        k.has[kUpfirSplit] = tune.engine.upfir_split != 0 && tune.upfir16 != 0 &&
+        k.has[kUpfirSplit] = tune.engine.upfir_split != 0 &&
                              (gance::upfirs_supported(c.cin, c.cout, H, H) || (tune.engine.upfir_split_narrow != 0 && gance::upfirs_narrow_supported(c.cin, c.cout, H, H)));
-        k.has[kUpfir16x] = tune.upfir16 != 0 && tune.upfir16x != 0 && gance::upfir16x_supported(c.cin, c.cout, H, H);
+        k.has[kUpfir16x] = tune.upfir16x != 0 && gance::upfir16x_supported(c.cin, c.cout, H, H);
         // (... 9 Cout to be a multiple of 256: the 128-channel layer keeps the fp32 GEMM)
         k.gemm_split = (9 * c.cout) % 256 == 0 ? tune.engine.gemm_bf16 : 0;
     }
@@ -261,9 +249,9 @@ enum class Form {
     Wino, WinoTorgb, Wino64, Wino43, WinoGemm,  // the stride-1 forms of WeightImage (WinoTorgb: kWino's own fused-ToRGB variant)
     UpTwoPass,     // conv_mfma.hip's transposed conv into parity planes + the FIR pass
     UpGemm,        // scatter-form GEMM + the FIR pass
-    UpFused, UpFused16, UpFused16x, UpSplit  // one fused launch: kUpfir, kUpfir16, kUpfir16x, kUpfirSplit
+    UpFused16, UpFused16x, UpSplit  // one fused launch: kUpfir16, kUpfir16x, kUpfirSplit
 };
-bool is_fused_up(Form f) { return f == Form::UpFused || f == Form::UpFused16 || f == Form::UpFused16x || f == Form::UpSplit; }
+bool is_fused_up(Form f) { return f == Form::UpFused16 || f == Form::UpFused16x || f == Form::UpSplit; }
 
 struct LayerStep {
     Form form = Form::Direct;
@@ -336,16 +324,16 @@ ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool 
 // Whether up layer idx runs as the fused kernel (transposed conv + FIR in one launch): where it is supported and fills
 // the chip; Tuning::upfir = 0 / 1 / 2 overrides the engine flags (never / auto / always). The layer BEFORE it has to know:
 // fed by a 16x16x4 Winograd launch the fused kernel takes its input pre-scaled by its style (plan_call's second pass).
-// split: the split-operand form (launch_upfir_split); fp32: the fp32-MFMA forms (launch_upfir16_fused / launch_upfir_fused)
-enum class UpFused { no, fp32, split };
-UpFused up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
+// split: the split-operand form (launch_upfir_split); fp32: the fp32-MFMA forms (launch_upfir16_fused)
+enum class FusedUp { no, fp32, split };
+FusedUp up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
     const ConvLayerHost& c = ctx.convs[idx];
     const LayerCaps& caps = ctx.caps[idx];
     const Tuning::PerEngine& knobs = ctx.tune.engine;
     const int H = (1 << c.res_log2) / 2, B = ctx.B;
     const int upfir_mode = ctx.tune.upfir >= 0 ? ctx.tune.upfir
                                                : ((ctx.flags & GANCE_FLAG_SPLIT_UPFIR) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_FUSED_UPFIR) ? 2 : 1));
-    if (!c.up || upfir_mode == 0 || (!caps.has[kUpfir] && !caps.has[kUpfir16])) return UpFused::no;
+    if (!c.up || upfir_mode == 0 || !caps.has[kUpfir16]) return FusedUp::no;
     gance::UpFirArgs u{};
     u.Cin = c.cin;
     // the split-operand form (upfir_split.hip; a block sweeps the image's height, or a row segment of it where whole images would leave
@@ -359,26 +347,23 @@ UpFused up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
         const bool narrow = !gance::upfirs_supported(c.cin, c.cout, H, H);
         if ((knobs.upfir_split == 2 && !narrow) || (u.total_blocks >= ctx.num_cus * 9 / 16 && 2 * H <= knobs.upfir_split_max_res)) {
             *plan = u;
-            return UpFused::split;
+            return FusedUp::split;
         }
         u = gance::UpFirArgs{};
         u.Cin = c.cin;
     }
-    if (caps.has[kUpfir16])
-        gance::upfir16_plan(B, c.cout, H, H, ctx.num_cus, &u);
-    else
-        gance::upfir_plan(B, c.cout, H, H, ctx.num_cus, &u);
+    gance::upfir16_plan(B, c.cout, H, H, ctx.num_cus, &u);
     const int steps_per_seg = u.rows_per_seg / u.step_rows;
     *plan = u;
     // (the narrow strip geometries -- inputs 32 and 16 wide -- have one or two steps per image: never cut into segments)
-    return (upfir_mode == 2 || (u.total_blocks >= ctx.num_cus * 3 / 4 && (u.segs == 1 || steps_per_seg >= 4))) ? UpFused::fp32 : UpFused::no;
+    return (upfir_mode == 2 || (u.total_blocks >= ctx.num_cus * 3 / 4 && (u.segs == 1 || steps_per_seg >= 4))) ? FusedUp::fp32 : FusedUp::no;
 }
 
 // The launch names of a layer's step, as gance_engine_step_info reports them (the launch loop and gance_engine_describe_plan both
 // read them from here). conv<N> direct form, convW F(2x2,3x3), convV F(4x4,3x3), convVG the same as 36 dense GEMMs (input transform +
 // GEMMs + output transform); +rgb: the ToRGB channel sum in the epilogue, +torgb: the whole ToRGB. convT the two-pass up layer,
 // convTG its scatter form (pack + GEMM + gather), convTF one fused up kernel, convTFp with its input pre-scaled by its style
-// (upfir_fused_pre_kernel); a trailing "/16": the 16-channel, two-blocks-per-CU geometry (upfir16_fused*_kernel), "/16x": its pair
+// (the *_pre_kernel variants); a trailing "/16": the fp32 form, 16 channels per block (upfir16_fused*_kernel), "/16x": its pair
 // form, "/s3": the split-operand form (upfirs_fused*_kernel: bf16 x 3 parts, six product terms, fp32 accumulation).
 void name_step(const ConvLayerHost& c, LayerStep* s) {
     const int res = 1 << c.res_log2;
@@ -390,7 +375,7 @@ void name_step(const ConvLayerHost& c, LayerStep* s) {
         case Form::WinoGemm: kind = "VG"; break;
         case Form::UpTwoPass: kind = "T"; break;
         case Form::UpGemm: kind = "TG"; break;
-        case Form::UpFused: case Form::UpFused16: case Form::UpFused16x: case Form::UpSplit: kind = s->input_prescaled ? "TFp" : "TF"; break;
+        case Form::UpFused16: case Form::UpFused16x: case Form::UpSplit: kind = s->input_prescaled ? "TFp" : "TF"; break;
     }
     const char* suffix = s->form == Form::UpFused16 ? "/16" : (s->form == Form::UpFused16x ? "/16x" : (s->form == Form::UpSplit ? "/s3" : ""));
     const bool absorbs_torgb = s->form == Form::DirectTorgb || s->form == Form::WinoTorgb;
@@ -442,13 +427,12 @@ std::vector<LayerStep> plan_call(const std::vector<ConvLayerHost>& convs, const 
                 s.form = Form::DirectSplitK;
             }
         } else {
-            const UpFused fused = up_runs_fused(ctx, li, &s.up);
+            const FusedUp fused = up_runs_fused(ctx, li, &s.up);
             // (the scatter form: at 4x4 / 8x8 inputs from Tuning::upgemm_min_columns columns up, at 32x32 / 64x64 inputs for calls this small)
             const bool scatter = caps[li].has[kUpGemm] && B * H * H >= tune.upgemm_min_columns &&
                                  B * H * H <= gance::upgemm_max_columns(c.cout, tune.upgemm_buffer_columns);
-            s.form = fused == UpFused::split ? Form::UpSplit
-                                             : (fused == UpFused::fp32 ? (caps[li].has[kUpfir16] ? Form::UpFused16 : Form::UpFused)
-                                                                       : (scatter ? Form::UpGemm : Form::UpTwoPass));
+            s.form = fused == FusedUp::split ? Form::UpSplit
+                                             : (fused == FusedUp::fp32 ? Form::UpFused16 : (scatter ? Form::UpGemm : Form::UpTwoPass));
         }
     }
     for (int li = 0; li < limit; ++li) {

@@ -103,7 +103,7 @@ struct ConvArgs {
                          // (randomize_noise=False), OH * OW = a plane per sample (gance_engine_randomize_noise: upstream
                          // draws tf.random_normal([N, 1, H, W]))
     int tiles_x, tiles_y, m_tiles;
-    int total_tiles;  // virtual blocks of the launch (set by launch_modconv; a persistent grid is smaller)
+    int total_tiles;  // blocks of the launch (set by launch_modconv): the XCD remap of the block ids needs the count
     // runtime-geometry launches (transposed conv, BM = 128): after the tiles_x*tiles_y main tiles
     // come row_tiles 1x64 tiles on the position row y' = H and col_tiles 64x1 tiles on x' = W
     int row_tiles, col_tiles;
@@ -140,7 +140,7 @@ struct ConvArgs {
 struct ConvTileInfo {
     int BM, TB, TH, TW, KC, up;
 };
-constexpr int kNumConvTiles = 15;
+constexpr int kNumConvTiles = 9;
 extern const ConvTileInfo kConvTiles[kNumConvTiles];
 
 hipError_t launch_modconv(int tile_id, const ConvArgs& args, int total_blocks, hipStream_t stream);
@@ -175,11 +175,12 @@ hipError_t launch_winograd43_conv(const ConvArgs& args, hipStream_t stream);
 bool winograd43_rgb_supported(int cout);
 int winograd43_rgb_partials(int cout);
 
-// Conv0_up as ONE kernel (upfir_fused.hip): transposed conv on the matrix cores + [1,3,3,1]^2 FIR + noise +
-// bias + leaky ReLU, for inputs >= 64 wide. Blocks sweep 64-column strips in steps of 8 position rows.
+// Conv0_up as ONE kernel (upfir16_fused.hip, upfir_split.hip): transposed conv on the matrix cores + [1,3,3,1]^2 FIR + noise +
+// bias + leaky ReLU. Blocks sweep column strips top to bottom in steps of step_rows position rows (upfir16_fused.hip's header
+// has the decomposition).
 struct UpFirArgs {
     const float* x;      // zero-bordered [B][Cin][H+2][W+8]
-    const float* w;      // [m tile of 32][chunk of 4][tap slot 0..8][4][32], runtime-scaled
+    const float* w;      // the launched kernel's weight image (upfir16_ / upfir16x_ / upfirs_arrange_weights), runtime-scaled
     const float* s;      // style: s[b * s_stride + ci]
     const float* d;      // demodulation: d[b * d_stride + co]
     const float* noise;  // [2H][2W] or nullptr; sample b reads noise + b * noise_b_stride
@@ -189,9 +190,9 @@ struct UpFirArgs {
     int s_stride, d_stride;
     float noise_strength;
     int noise_b_stride;  // 0 (one plane for the batch) or 4 H W (a plane per sample), as in ConvArgs
-    int m_tiles, strips, segs, rows_per_seg, total_blocks;  // set by upfir_plan
+    int m_tiles, strips, segs, rows_per_seg, total_blocks;  // set by upfir16_plan / upfirs_plan
     int step_rows;                                           // position rows per step (set by the plan: 8, or 16 in the narrow strip geometries of upfir16_fused.hip)
-    int stagger_phases, stagger_ticks;                       // set by upfir_plan: start delay (phase * ticks of 10 ns)
+    int stagger_phases, stagger_ticks;                       // set by the plan: start delay (phase * ticks of 10 ns)
     int debug_flags;  // timing ablations (GANCE_DEBUG_UPFIR): 1 no stores, 2 no epilogue at all, 4 no MFMA, 8 no DMA after the first chunk
     long long x_b_stride;
     // nullptr, or the style of the NEXT layer, s_next[b * s_stride + co]: folded into the leaky ReLU, i.e. the stored
@@ -200,13 +201,8 @@ struct UpFirArgs {
     int input_prescaled;  // x arrives multiplied by this layer's own style (its producer was given s_next): no style scale in the K loop
     int pair_form;        // upfir16 only: w is the pair-form image (upfir16x_arrange_weights): F(2,2) along x, 15 MFMAs per pair of columns instead of 18
 };
-bool upfir_supported(int cin, int cout, int H, int W);
-size_t upfir_weight_floats(int cin, int cout);
-void upfir_arrange_weights(const float* w_in /*[9][cin][cout] scaled*/, int cin, int cout, const int* up_tap_weight, float* w_out);
-void upfir_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* args);
-hipError_t launch_upfir_fused(const UpFirArgs& args, hipStream_t stream);
 
-// The same layer with 16 output channels per block and two blocks per CU (upfir16_fused.hip): w points at
+// The fp32 form, 16 output channels per block and two blocks per CU (upfir16_fused.hip): w points at
 // [m tile of 16][chunk of 8][1280 floats]; the plan gives every CU two blocks before it cuts row segments.
 bool upfir16_supported(int cin, int cout, int H, int W);
 size_t upfir16_weight_floats(int cin, int cout);

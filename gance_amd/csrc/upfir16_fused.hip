@@ -1,14 +1,34 @@
-// Conv0_up in ONE kernel, second geometry (round 4): 16 output channels per block, TWO blocks per CU.
+// Conv0_up in ONE kernel: stride-2 transposed modulated 3x3 convolution on the fp32 matrix cores, its [1,3,3,1] x [1,3,3,1] FIR,
+// noise, bias and leaky ReLU. 16 output channels per block, TWO blocks per CU (round 4).
 //
-// Same layer, same decomposition and same layout contracts as upfir_fused.hip (read its header first): stride-2 transposed
-// modulated 3x3 convolution as four parity classes on the fp32 matrix cores, [1,3,3,1] x [1,3,3,1] FIR, noise, bias, leaky
-// ReLU, one launch, the (2H+1)^2 intermediate T never in HBM; a block sweeps a strip of 64 position columns top to bottom in
-// steps of 8 position rows, the two halo position columns are one extra tile, the last three T rows of a step are carried in
-// LDS. Replaces, for the reference's synthesis call (gance/network_interface/network_functions.py:168), the un-vendored
-// `upsample_conv_2d` + `fused_bias_act` pair.
+// Replaces, for the reference's synthesis call (gance/network_interface/network_functions.py:168), the un-vendored
+// `upsample_conv_2d` (tf.nn.conv2d_transpose + upfirdn_2d.cu, pad 1/1, gain 4) followed by `fused_bias_act.cu` (SURVEY.md section 8
+// a18), and replaces this library's own two-pass form (conv_mfma.hip UP=true + aux_kernels.hip fir_epilogue_kernel) wherever a
+// launch fills the chip: the (2H+1)^2 intermediate T never goes to HBM. The layer then reads its input once and writes its output
+// once. upfir_split.hip is the same layer with its K loop on the bf16 matrix cores; it rests on everything said here.
 //
-// What is different, and why. upfir_fused.hip holds 32 channels x 8 x 64 positions x 4 classes = 256 accumulator registers per
-// lane: one wave per SIMD, one block per CU, and whatever a wave does besides MFMAs -- the FIR epilogue (a fifth of a step at
+// Decomposition. T[2y'+py][2x'+px] (four parity classes of a position (y',x') of the INPUT grid, the 9 filter taps split 4/2/2/1
+// over them) is what the matrix cores produce, exactly as in conv_mfma.hip. out[oy][ox] = sum_{a,b} k[a] k[b] T[oy+a-1][ox+b-1]
+// needs a halo of 3 T rows / columns around an output tile. A block therefore SWEEPS a column strip of 64 positions top to bottom
+// in steps of 8 position rows:
+//   * horizontally the two halo position columns (x' = X0-1: odd column parity only; x' = X0+64) are recomputed: 16 positions =
+//     one extra tile of 16 slots whose four classes are split over the four waves;
+//   * vertically nothing is recomputed: the last three T rows of a step stay in LDS (the carry, [16 channels][3 rows][132
+//     columns]) and are the top of the next step's FIR window. A block that starts below the image's top (a row segment, where
+//     whole strips would leave CUs idle: upfir16_plan) first runs a priming step for its carry.
+// A step = K loop (LDS-DMA ring of two slots, chunks of 8 input channels: weight image + haloed patch [8][9][72]), then the
+// epilogue in passes: accumulators -> LDS T window, barrier, every thread filters a strip of output rows x 4 columns of one
+// channel (two aligned ds_read_b128 per T row, horizontal taps carry demod * sqrt 2, vertical taps, + noise + bias, leaky ReLU)
+// and stores float4s. The next step's first chunk is fetched under the epilogue; its arrival is waited for BEFORE the first store
+// so that the K loop never waits behind the epilogue's stores (vmcnt counts in issue order).
+//
+// Layout contracts are those of conv_mfma.hip: zero-bordered activations [B][C][H+2][W+8], interior at [y+1][x+4]; borders are
+// never written, which is what makes every out-of-image tap and the T cells outside [0, 2H]^2 come out as exact zeros without a
+// bounds test.
+//
+// Why 16 channels and two blocks. The first form of this kernel (round 2, removed: HISTORY.md) held 32 channels x 8 x 64
+// positions x 4 classes = 256 accumulator registers per lane:
+// one wave per SIMD, one block per CU, and whatever a wave does besides MFMAs -- the FIR epilogue (a fifth of a step at
 // 1024^2), the accumulator dump, barriers, LDS latencies -- leaves the matrix pipe idle (0.59 of the roof at 1024^2, flat for
 // two rounds). Nothing inside one block can overlap them: the tile's results (262 KB per step) have nowhere to wait while the
 // next K loop runs. Two INDEPENDENT blocks per CU can: while one filters and stores, the other multiplies. That needs half the
@@ -27,10 +47,10 @@
 //   * the noise tile does not fit: the FIR threads load their noise rows from HBM, one pass ahead (the loads of pass p + 1
 //     are issued before the stores of pass p: gfx9 has ONE vector-memory counter, a load behind a store waits for it).
 //   * no block is special: nothing depends on which waves share a SIMD.
-// The halo tile (16 slots x 16 channels) is one more 16x16x4 tile whose four classes are split over the four waves, as before.
+// The halo tile (16 slots x 16 channels) is one more 16x16x4 tile whose four classes are split over the four waves.
 //
 // Three strip geometries (template Geo16<CT, RW>: CT column tiles of 16 per position row, RW position rows per wave, a step =
-// 4 RW rows): <4, 2> = strips of 64 columns, steps of 8 rows (inputs >= 64 wide, the layers upfir_fused.hip also takes);
+// 4 RW rows): <4, 2> = strips of 64 columns, steps of 8 rows (inputs >= 64 wide, as described above);
 // <2, 4> = 32 columns x 16 rows (the 32 -> 64 layer); <1, 4> = 16 columns x 16 rows, four tiles per wave (the 16 -> 32
 // layer): the layers that ran as two passes (transposed conv into T planes in HBM + FIR pass) until round 4. An epilogue pass
 // always covers four position rows (one per wave) x four channels: 4 RW passes per step.

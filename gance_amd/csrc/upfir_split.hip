@@ -28,8 +28,8 @@
 //     three 16-byte units: a bf16 MFMA holds the vector issue for 8 of its 16 cycles, the split rides in its shadow.
 //   * the weight fragments of a chunk (9 taps x 3 parts: 108 registers) live in REGISTERS, loaded from the split image in global
 //     memory one chunk ahead (27 x 16 bytes per lane, three per row): 128 accumulators + two sets of them + fragments and staging
-//     registers are > 256, so one wave per SIMD, one block per CU -- the FIR epilogue stays serial with the K loop as in the
-//     32-channel kernel; what pays for it is a K loop 0.5 x as long.
+//     registers are > 256, so one wave per SIMD, one block per CU -- the FIR epilogue stays serial with the K loop (no
+//     second block on the CU runs beside it, as in upfir16_fused.hip); what pays for it is a K loop 0.5 x as long.
 //   * the two halo position columns (x' = X0 - 1: odd column parity only; x' = X0 + 64) are one extra 16-slot tile as before, but
 //     its rows are never resident together: a per-chunk side buffer holds columns X0 - 2, X0 - 1, X0 + 63, X0 + 64 of the chunk's
 //     nine rows (144 staging tasks per chunk, written half a chunk ahead), read once per chunk by the 54 halo MFMAs (one class per

@@ -1,5 +1,5 @@
 """Dev check of the fused up kernel's 16-channel geometry: where does it differ from the fp64 oracle?
-    python tests/dev/debug_upfir16.py [resolution] [batch]   (GANCE_TUNE_UPFIR16=0 for the 32-channel geometry)"""
+    python tests/dev/debug_upfir16.py [resolution] [batch]"""
 import sys
 from pathlib import Path
 

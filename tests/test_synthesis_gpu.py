@@ -196,7 +196,7 @@ def test_fused_upsampling_layer_matches_oracle_layerwise(library, resolution: in
     """
     (The fp32 kernels: since round 5 the split-operand form would take the layers with inputs >= 64 wide at these batch sizes too --
     its own cases are test_split_operand_up_layers_match_oracle_layerwise -- so it is switched off here: GANCE_TUNE_UPFIR_SPLIT=0.)
-    Conv0_up as ONE kernel (upfir16_fused.hip / upfir_fused.hip: transposed conv + FIR + noise + bias + leaky ReLU),
+    Conv0_up as ONE kernel (upfir16_fused.hip: transposed conv + FIR + noise + bias + leaky ReLU),
     forced at a small batch: the planner then cuts the image into row segments (priming steps), 256^2 has
     two 64-column strips (recomputed halo columns) and 8 channel tiles; every term is switched on. The 16 -> 32 and
     32 -> 64 layers run in the kernel's 16- and 32-column strip geometries (steps of 16 position rows, two halo tiles).
@@ -222,7 +222,7 @@ def test_fused_upsampling_layer_matches_oracle_layerwise(library, resolution: in
             want = wants[n - 1].numpy()
             rel = np.abs(got - want).max() / np.abs(want).max()
             assert rel < 2e-5, f"conv layer {n} ({conv.scope}): rel err {rel}"
-        if conv_form == "winograd43" and os.environ.get("GANCE_TUNE_UPFIR16X", "1") != "0" and os.environ.get("GANCE_TUNE_UPFIR16", "1") != "0":
+        if conv_form == "winograd43" and os.environ.get("GANCE_TUNE_UPFIR16X", "1") != "0":
             engine.synthesize_w(dlatents)
             pair = [step.name for step in engine.steps() if step.name.endswith("/16x")]
             assert len(pair) == int(np.log2(resolution)) - 5, pair  # every up layer whose input is >= 32 wide

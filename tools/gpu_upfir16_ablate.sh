@@ -1,7 +1,7 @@
 #!/bin/bash
 # The 16-channel fused up kernel (upfir16_fused.hip): parity subset on the product build, per-launch times under the timing
 # ablations of the debug build (make -C gance_amd/csrc upfir16dbg; GANCE_DEBUG_UPFIR flag sets, wrong results by design) and
-# an occupancy / matrix-pipe counter pass of both geometries.
+# an occupancy / matrix-pipe counter pass.
 #   gpurun --timeout 1100 -- 'bash tools/gpu_upfir16_ablate.sh tag "0 2 32 16 1 4 8"'
 tag=${1:-a}
 flags=${2:-"0 2 32"}
@@ -18,10 +18,8 @@ done
 out=$PWD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 cd "$OLDPWD"
-for mode in 1 0; do
-  GANCE_TUNE_UPFIR16=$mode rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE \
-    --output-format csv -d $out/upfir16_pmc_$mode -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $out/upfir16_${tag}_pmc_$mode.err || exit 1
-  PMC_SPLIT="upfir_fused_pre_kernel:4;upfir16_fused_pre_kernel:4" python3 tools/pmc_summary.py $(find $out/upfir16_pmc_$mode -name "*counter_collection.csv") > $out/upfir16_${tag}_pmc_$mode.csv
-  rm -rf $out/upfir16_pmc_$mode
-  grep -E "^kernel|upfir" $out/upfir16_${tag}_pmc_$mode.csv
-done
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE \
+  --output-format csv -d $out/upfir16_pmc -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $out/upfir16_${tag}_pmc.err || exit 1
+PMC_SPLIT="upfir16_fused_pre_kernel:4" python3 tools/pmc_summary.py $(find $out/upfir16_pmc -name "*counter_collection.csv") > $out/upfir16_${tag}_pmc.csv
+rm -rf $out/upfir16_pmc
+grep -E "^kernel|upfir" $out/upfir16_${tag}_pmc.csv
