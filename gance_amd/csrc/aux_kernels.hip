@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void demod_kernel(const float* __restrict__ s,
         bool ok;
         skinny_block<true>(s + (size_t)b0 * ctot + L.s_off, (size_t)ctot, L.cin,
                            w2_pool + L.w2_off + co0, L.cout, nb, lds_in, lds_red, r, rb, ok);
-        if (ok) d[(size_t)(b0 + rb) * dtot + L.d_off + col] = 1.0f / sqrtf(r[0] + 1e-8f);
+        if (ok && col < L.cout) d[(size_t)(b0 + rb) * dtot + L.d_off + col] = 1.0f / sqrtf(r[0] + 1e-8f);  // (a 16-channel layer fills half a block)
     }
 }
 

@@ -700,6 +700,8 @@ const ConvTileInfo kConvTiles[kNumConvTiles] = {
     {32, 1, 16, 16, 8, 1},  // 6: transposed, Cout = 32 (512 -> 1024)
     {64, 1, 8, 16, 8, 1},   // 7: transposed, Cout = 64 (256 -> 512)
     {128, 1, 8, 8, 4, 1},   // 8: transposed, Cout >= 128: runtime geometry (8x8 + edge strips)
+    {16, 1, 4, 64, 16, 0},  // 9: Cout = 16, stride 1 (config-e at 1024^2): conv16_mfma.hip
+    {16, 1, 8, 32, 16, 1},  // 10: transposed, Cout = 16 (config-e, 512 -> 1024): conv16_mfma.hip
 };
 
 hipError_t launch_modconv(int tile_id, const ConvArgs& a, int total_blocks, hipStream_t stream) {
@@ -714,6 +716,7 @@ hipError_t launch_modconv(int tile_id, const ConvArgs& a, int total_blocks, hipS
         case 6: return launch_one<32, 1, 16, 16, 8, 1, 4, true>(a, total_blocks, stream);
         case 7: return launch_one<64, 1, 8, 16, 8, 2, 2, true>(a, total_blocks, stream);
         case 8: return launch_one<128, 1, 8, 8, 4, 4, 1, true, true>(a, total_blocks, stream);
+        case 9: case 10: return launch_modconv16(tile_id, a, total_blocks, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -1,4 +1,4 @@
-// libgance_hip.so: the StyleGAN2 config-f engine behind include/gance_hip.h.
+// libgance_hip.so: the StyleGAN2 engine (the skip generator of config-f and config-e) behind include/gance_hip.h.
 //
 // Owns one network's weights (re-laid-out for the kernels) and a workspace sized for max_batch
 // frames in HBM, and turns a batch of dlatents (or z vectors) into uint8 NHWC frames with a fixed
@@ -54,29 +54,34 @@ constexpr int kDlatent = 512;
 constexpr int kMappingLayers = 8;
 constexpr float kMappingLrmul = 0.01f;
 
-int nf(int stage) {
-    const int v = (16 << 10) >> stage;
+// feature maps at a stage (stage = res_log2 - 1): fmap_base = 16 << 10 in config-f, 8 << 10 in config-e (GANCE_FLAG_FMAP_BASE_8K)
+int fmap_base_of_flags(int flags) { return (flags & GANCE_FLAG_FMAP_BASE_8K) ? (8 << 10) : (16 << 10); }
+int nf(int stage, int fmap_base) {
+    const int v = fmap_base >> stage;
     return std::min(std::max(v, 1), 512);
 }
+int round_up32(int n) { return (n + 31) & ~31; }  // style / demod columns are dealt out in blocks of 32 (styles_kernel, demod_kernel)
 
 struct RgbLayerHost {
     int res_log2, cin, row;
 };
 
-void build_spec(int res_log2, std::vector<ConvLayerHost>* convs, std::vector<RgbLayerHost>* rgbs) {
-    convs->push_back({0, 2, nf(1), nf(1), false});
-    rgbs->push_back({2, nf(1), 1});
+void build_spec(int res_log2, int fmap_base, std::vector<ConvLayerHost>* convs, std::vector<RgbLayerHost>* rgbs) {
+    const auto fm = [fmap_base](int stage) { return nf(stage, fmap_base); };
+    convs->push_back({0, 2, fm(1), fm(1), false});
+    rgbs->push_back({2, fm(1), 1});
     for (int res = 3; res <= res_log2; ++res) {
-        convs->push_back({res * 2 - 5, res, nf(res - 2), nf(res - 1), true});
-        convs->push_back({res * 2 - 4, res, nf(res - 1), nf(res - 1), false});
-        rgbs->push_back({res, nf(res - 1), res * 2 - 3});
+        convs->push_back({res * 2 - 5, res, fm(res - 2), fm(res - 1), true});
+        convs->push_back({res * 2 - 4, res, fm(res - 1), fm(res - 1), false});
+        rgbs->push_back({res, fm(res - 1), res * 2 - 3});
     }
 }
 
-uint64_t blob_floats(int res_log2) {
+uint64_t blob_floats(int res_log2, int fmap_base) {
     std::vector<ConvLayerHost> convs;
     std::vector<RgbLayerHost> rgbs;
-    build_spec(res_log2, &convs, &rgbs);
+    build_spec(res_log2, fmap_base, &convs, &rgbs);
+    const auto nf = [fmap_base](int stage) { return ::nf(stage, fmap_base); };
     uint64_t n = 0;
     n += (uint64_t)kMappingLayers * (kDlatent * kDlatent + kDlatent);
     n += kDlatent;
@@ -170,6 +175,7 @@ struct GraphEntry {
 struct gance_engine {
     gance_engine_config cfg{};
     int res_log2 = 0;
+    int fmap_base = 16 << 10;  // the channel table: nf(stage, fmap_base)
     int num_rows = 0;  // W
     std::vector<ConvLayerHost> convs;
     std::vector<RgbLayerHost> rgbs;
@@ -687,13 +693,13 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
     return GANCE_OK;
 }
 
-// the workspaces alive in this process, by (device, resolution, max_batch)
+// the workspaces alive in this process, by (device, resolution, max_batch, channel table: its buffers are sized by the layers' channels)
 std::mutex g_workspace_mutex;
-std::map<std::tuple<int, int, int>, std::weak_ptr<gance_workspace>> g_workspaces;
+std::map<std::tuple<int, int, int, int>, std::weak_ptr<gance_workspace>> g_workspaces;
 
 int acquire_workspace(gance_engine* e) {
     const bool shared = !(e->cfg.flags & GANCE_FLAG_PRIVATE_WORKSPACE);
-    const auto key = std::make_tuple((int)e->cfg.device, (int)e->cfg.resolution, (int)e->cfg.max_batch);
+    const auto key = std::make_tuple((int)e->cfg.device, (int)e->cfg.resolution, (int)e->cfg.max_batch, (int)(e->cfg.flags & GANCE_FLAG_FMAP_BASE_8K));
     std::lock_guard<std::mutex> lock(g_workspace_mutex);
     if (shared) {
         auto it = g_workspaces.find(key);
@@ -795,11 +801,12 @@ extern "C" {
 const char* gance_last_error(void) { return g_last_error.c_str(); }
 int gance_abi_version(void) { return GANCE_ABI_VERSION; }
 
-uint64_t gance_weight_blob_floats(int32_t resolution) {
+uint64_t gance_weight_blob_floats_flags(int32_t resolution, int32_t flags) {
     const int l = ilog2_exact(resolution);
     if (l < 3 || l > 10) return 0;
-    return blob_floats(l);
+    return blob_floats(l, fmap_base_of_flags(flags));
 }
+uint64_t gance_weight_blob_floats(int32_t resolution) { return gance_weight_blob_floats_flags(resolution, 0); }
 
 int gance_engine_create(const gance_engine_config* config, const float* host_weights,
                         uint64_t num_floats, gance_engine** out_engine) {
@@ -811,10 +818,11 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         return fail(GANCE_ERR_INVALID_ARGUMENT, "resolution must be a power of two in [8, 1024]");
     if (config->max_batch < 1 || config->max_batch > 64)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "max_batch must be in [1, 64]");
-    if (num_floats != blob_floats(res_log2))
+    const int fmap_base = fmap_base_of_flags(config->flags);
+    if (num_floats != blob_floats(res_log2, fmap_base))
         return fail(GANCE_ERR_BAD_WEIGHTS,
                     "weight blob has " + std::to_string(num_floats) + " floats, expected " +
-                        std::to_string(blob_floats(res_log2)));
+                        std::to_string(blob_floats(res_log2, fmap_base)) + (fmap_base == (8 << 10) ? " (config-e)" : ""));
     int device_count = 0;
     const hipError_t count_err = hipGetDeviceCount(&device_count);
     if (count_err != hipSuccess || device_count < 1)
@@ -834,8 +842,10 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     e->cfg = *config;
     e->num_cus = num_cus > 0 ? num_cus : 256;
     e->res_log2 = res_log2;
+    e->fmap_base = fmap_base;
+    const auto nf = [fmap_base](int stage) { return ::nf(stage, fmap_base); };
     e->num_rows = res_log2 * 2 - 2;
-    build_spec(res_log2, &e->convs, &e->rgbs);
+    build_spec(res_log2, fmap_base, &e->convs, &e->rgbs);
     const int nconv = (int)e->convs.size();
     const int nrgb = (int)e->rgbs.size();
 
@@ -845,14 +855,15 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     e->rgb_s_off.resize(nrgb);
     int ctot = 0, dtot = 0;
     for (int i = 0; i < nconv; ++i) {
+        // (every layer's columns start a block of 32: a 16-channel layer -- config-e at 1024^2 -- leaves half a block unused)
         e->conv_s_off[i] = ctot;
-        ctot += e->convs[i].cin;
+        ctot += round_up32(e->convs[i].cin);
         e->conv_d_off[i] = dtot;
-        dtot += e->convs[i].cout;
+        dtot += round_up32(e->convs[i].cout);
     }
     for (int i = 0; i < nrgb; ++i) {
         e->rgb_s_off[i] = ctot;
-        ctot += e->rgbs[i].cin;
+        ctot += round_up32(e->rgbs[i].cin);
     }
     e->ctot = ctot;
     e->dtot = dtot;
@@ -890,7 +901,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     e->bias1_off = reserve(ctot);
     size_t w2_total = 0;
     for (const auto& c : e->convs) w2_total += (size_t)c.cin * c.cout;
-    e->w2_off = reserve(w2_total);
+    e->w2_off = reserve(w2_total + 32);  // (demod_kernel reads whole blocks of 32 columns: 16 past a 16-channel layer's)
     const float mod_coef = (float)(1.0 / std::sqrt((double)kDlatent));
     std::vector<gance::DemodLayer> demod_layers(nconv);
     // every form's weight image beyond the direct one, in the pool's order (enum WeightImage): its size and how it is arranged
@@ -1015,10 +1026,10 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     // dlatent row of every 32-column style block
     std::vector<int> blk_row(ctot / 32);
     for (int i = 0; i < nconv; ++i)
-        for (int cb = e->conv_s_off[i] / 32; cb < (e->conv_s_off[i] + e->convs[i].cin) / 32; ++cb)
+        for (int cb = e->conv_s_off[i] / 32; cb < (e->conv_s_off[i] + round_up32(e->convs[i].cin)) / 32; ++cb)
             blk_row[cb] = e->convs[i].layer_idx;
     for (int i = 0; i < nrgb; ++i)
-        for (int cb = e->rgb_s_off[i] / 32; cb < (e->rgb_s_off[i] + e->rgbs[i].cin) / 32; ++cb)
+        for (int cb = e->rgb_s_off[i] / 32; cb < (e->rgb_s_off[i] + round_up32(e->rgbs[i].cin)) / 32; ++cb)
             blk_row[cb] = e->rgbs[i].row;
 
     // ---- workspace sizes ----
@@ -1339,7 +1350,7 @@ int gance_engine_describe_plan(const gance_engine_config* config, int32_t num_cu
         return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_describe_plan: resolution, max_batch, batch or num_cus out of range");
     std::vector<ConvLayerHost> convs;
     std::vector<RgbLayerHost> rgbs;
-    build_spec(res_log2, &convs, &rgbs);
+    build_spec(res_log2, fmap_base_of_flags(config->flags), &convs, &rgbs);
     const Tuning tune = engine_tuning();
     std::vector<LayerCaps> caps;
     for (int i = 0; i < (int)convs.size(); ++i) caps.push_back(layer_caps(convs, i, config->flags, tune));

@@ -32,7 +32,7 @@ struct LayerPlan {
 
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-int layer_bm(int cout) { return cout == 32 ? 32 : (cout == 64 ? 64 : 128); }
+int layer_bm(int cout) { return cout == 16 ? 16 : (cout == 32 ? 32 : (cout == 64 ? 64 : 128)); }  // (16: conv16_mfma.hip, config-e at 1024^2)
 
 // Every GANCE_TUNE_* / GANCE_DEBUG_* value engine.hip reads (the kernel files read their own launch-geometry knobs). read_tuning() is
 // the only place that looks at the environment. All fields are read ONCE PER PROCESS (several size the workspace, which engines
@@ -130,12 +130,14 @@ Tuning engine_tuning() {  // the process's values, with the per-engine ones as t
     return t;
 }
 
-// K chunk (input channels per LDS stage) of the direct form's tiles: 8 in the narrow transposed convs (Cout 32 / 64), 4 everywhere else
-int layer_kc(int cout, bool up) { return up && layer_bm(cout) != 128 ? 8 : 4; }
+// K chunk (input channels per LDS stage) of the direct form's tiles: 16 in the 16-channel tiles, 8 in the narrow transposed convs
+// (Cout 32 / 64), 4 everywhere else
+int layer_kc(int cout, bool up) { return layer_bm(cout) == 16 ? 16 : (up && layer_bm(cout) != 128 ? 8 : 4); }
 
 // The direct form's tile (gance::kConvTiles) of a layer
 int choose_tile(int cout, bool up, int OH, int OW, int B) {
-    if (cout == 32) return up ? 6 : 4;  // 512 -> 1024 / the 1024^2 layers
+    if (cout == 16) return up ? 10 : 9;  // config-e: 512 -> 1024 / the 1024^2 layers (conv16_mfma.hip)
+    if (cout == 32) return up ? 6 : 4;  // config-f: 512 -> 1024 / the 1024^2 layers; config-e: the same at half the side
     if (cout == 64) return up ? 7 : 5;  // 256 -> 512 / the 512^2 layers
     if (up) return 8;                   // every up layer with Cout >= 128: runtime geometry
     // the stride-1 layers with Cout >= 128 (4^2 ... 256^2): the tile that covers the grid and the samples in the fewest blocks
@@ -177,7 +179,7 @@ LayerPlan plan_layer(const ConvLayerHost& c, int B, const Tuning& tune) {
     p.m_tiles = c.cout / t.BM;
     p.total_chunks = c.cin / t.KC;
     const int base = p.m_tiles * (p.tiles_x * p.tiles_y + p.row_tiles + p.col_tiles) * p.tiles_b;
-    p.nsplit = choose_nsplit(base, p.total_chunks);
+    p.nsplit = layer_bm(c.cout) == 16 ? 1 : choose_nsplit(base, p.total_chunks);  // (the 16-channel tiles have no split-K; their layers are 1024 wide)
     if (c.up) p.nsplit = std::min(p.nsplit, 8);  // the FIR pass re-reads every slab
     while (p.total_chunks % p.nsplit) --p.nsplit;
     p.chunks_per_split = p.total_chunks / p.nsplit;
@@ -232,9 +234,11 @@ LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, 
     } else {
         k.has[kUpfir16] = gance::upfir16_supported(c.cin, c.cout, H, H);
         k.has[kUpGemm] = tune.upgemm_min_columns > 0 && gance::upgemm_supported(c.cin, c.cout, H, H);
-        k.has[kUpfirSplit] = tune.engine.upfir_split != 0 &&
+        // (the split-operand and pair forms keep to the channel tables they were measured on: a 16-channel layer -- config-e,
+        // 512 -> 1024 -- has the fp32 form, 16 channels per block, as its one fused form)
+        k.has[kUpfirSplit] = tune.engine.upfir_split != 0 && c.cout >= 32 &&
                              (gance::upfirs_supported(c.cin, c.cout, H, H) || (tune.engine.upfir_split_narrow != 0 && gance::upfirs_narrow_supported(c.cin, c.cout, H, H)));
-        k.has[kUpfir16x] = tune.upfir16x != 0 && gance::upfir16x_supported(c.cin, c.cout, H, H);
+        k.has[kUpfir16x] = tune.upfir16x != 0 && c.cout >= 32 && gance::upfir16x_supported(c.cin, c.cout, H, H);
         // (... 9 Cout to be a multiple of 256: the 128-channel layer keeps the fp32 GEMM)
         k.gemm_split = (9 * c.cout) % 256 == 0 ? tune.engine.gemm_bf16 : 0;
     }
@@ -288,12 +292,13 @@ ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool 
     const int res = 1 << c.res_log2, B = ctx.B;
     ConvForm form{};
     // the network's last conv absorbs its ToRGB when one block holds all channels of a pixel
-    // (BM = Cout = 32, i.e. the 1024^2 generator): neither its activation nor the fp32 image is
+    // (BM = Cout = 32, i.e. the 1024^2 generator of config-f and the 512^2 one of config-e, or BM = Cout = 16, config-e at
+    // 1024^2): neither its activation nor the fp32 image is
     // written, only the uint8 frame (Tuning::fuse_rgb turns this off) -- so not where a debug tap reads that activation:
     // gance_engine_debug_read_activation would return whatever an earlier call left in the buffer
     const auto& tile = gance::kConvTiles[p.tile_id];
     form.fused_rgb = tune.fuse_rgb && c.res_log2 == ctx.convs.back().res_log2 && ctx.limit() == ctx.num_convs() && p.nsplit == 1 &&
-                     p.m_tiles == 1 && tile.TB == 1 && tile.BM == 32 && have_y_then && ctx.stop_after <= 0;
+                     p.m_tiles == 1 && tile.TB == 1 && (tile.BM == 32 || tile.BM == 16) && have_y_then && ctx.stop_after <= 0;
     // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry with the ToRGB product
     // in its epilogue (Tuning::last_wino64; measured: see DESIGN.md §3)
     const long long last_tiles = (long long)(res / 16) * (res / 32) * B;

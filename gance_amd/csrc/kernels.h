@@ -140,10 +140,13 @@ struct ConvArgs {
 struct ConvTileInfo {
     int BM, TB, TH, TW, KC, up;
 };
-constexpr int kNumConvTiles = 9;
+constexpr int kNumConvTiles = 11;
 extern const ConvTileInfo kConvTiles[kNumConvTiles];
 
 hipError_t launch_modconv(int tile_id, const ConvArgs& args, int total_blocks, hipStream_t stream);
+// The tiles with BM = 16 (conv16_mfma.hip, on v_mfma_f32_16x16x4_f32: the 16-channel layers of a config-e generator at 1024^2);
+// launch_modconv hands them on. Same arguments and weight image; one channel tile, no split-K, kEpilogueRgb on the stride-1 tile.
+hipError_t launch_modconv16(int tile_id, const ConvArgs& args, int total_blocks, hipStream_t stream);
 
 // Winograd F(2x2, 3x3) form of the stride-1 conv (winograd_conv.hip): 32 output channels x 8x64 pixels
 // per block; args.w points at the layer's transformed weights [m_tile][chunk][16][4][32].

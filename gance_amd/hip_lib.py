@@ -32,6 +32,7 @@ GANCE_FLAG_SPLIT_UPFIR = 8
 GANCE_FLAG_FORCE_FUSED_UPFIR = 16
 GANCE_FLAG_PRIVATE_WORKSPACE = 32
 GANCE_FLAG_WINOGRAD43 = 64
+GANCE_FLAG_FMAP_BASE_8K = 128  # the network is config-e (fmap_base = 8 << 10)
 
 STATUS_NAMES = {
     1: "GANCE_ERR_INVALID_ARGUMENT",
@@ -99,6 +100,7 @@ SIGNATURES = {
     "gance_engine_resolution": (ctypes.c_int32, [ctypes.c_void_p]),
     "gance_engine_max_batch": (ctypes.c_int32, [ctypes.c_void_p]),
     "gance_weight_blob_floats": (ctypes.c_uint64, [ctypes.c_int32]),
+    "gance_weight_blob_floats_flags": (ctypes.c_uint64, [ctypes.c_int32, ctypes.c_int32]),
     "gance_synthesize_w": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
@@ -370,7 +372,9 @@ class Engine:
         """
         self._lib = load_library()
         self._handle = ctypes.c_void_p()
-        spec = sg2_spec.make_spec(resolution)
+        # (the config is read off the variables: a config-e network, fmap_base = 8 << 10, carries GANCE_FLAG_FMAP_BASE_8K)
+        self.fmap_base = sg2_spec.fmap_base_of(variables, resolution)
+        spec = sg2_spec.make_spec(resolution, self.fmap_base)
         blob = sg2_spec.pack_variables(variables, spec)
         form_flags = {
             "auto": 0, "direct": GANCE_FLAG_DIRECT_CONV, "winograd": GANCE_FLAG_FORCE_WINOGRAD,
@@ -379,6 +383,8 @@ class Engine:
         form_flags |= {"auto": 0, "split": GANCE_FLAG_SPLIT_UPFIR, "fused": GANCE_FLAG_FORCE_FUSED_UPFIR}[up_form]
         if private_workspace:
             form_flags |= GANCE_FLAG_PRIVATE_WORKSPACE
+        if self.fmap_base == sg2_spec.FMAP_BASE_CONFIG_E:
+            form_flags |= GANCE_FLAG_FMAP_BASE_8K
         config = EngineConfig(resolution, max_batch, device, (GANCE_FLAG_PROFILE_STEPS if profile else 0) | form_flags)
         _check(
             self._lib,
@@ -528,7 +534,7 @@ class Engine:
     def debug_noise(self, conv_layer: int, sample: int = 0) -> np.ndarray:
         """The noise plane sample `sample` of conv layer `conv_layer` currently reads, [res, res] float32 (synchronises)."""
         self._require_open()
-        side = 2 ** sg2_spec.make_spec(self.resolution).convs[conv_layer].res_log2
+        side = 2 ** sg2_spec.make_spec(self.resolution, self.fmap_base).convs[conv_layer].res_log2
         out = np.empty((side, side), dtype=np.float32)
         _check(
             self._lib,
@@ -581,7 +587,7 @@ class Engine:
             capacity = batch * 512 * self.resolution * self.resolution
             channels = ctypes.c_int32()
             side = ctypes.c_int32()
-            spec = sg2_spec.make_spec(self.resolution)
+            spec = sg2_spec.make_spec(self.resolution, self.fmap_base)
             conv = spec.convs[num_conv_layers - 1]
             count = batch * conv.cout * (2 ** conv.res_log2) ** 2
             out = np.empty(count, dtype=np.float32)
@@ -605,7 +611,7 @@ class Engine:
         self._require_open()
         dl = _f32(dlatents)
         batch = dl.shape[0]
-        convs = sg2_spec.make_spec(self.resolution).convs
+        convs = sg2_spec.make_spec(self.resolution, self.fmap_base).convs
         if not 1 <= num_conv_layers <= len(convs):
             raise ValueError(f"num_conv_layers must be in [1, {len(convs)}], got {num_conv_layers}")
         _check(self._lib, self._lib.gance_engine_debug_stop_after(self._handle, num_conv_layers))

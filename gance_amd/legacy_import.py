@@ -15,8 +15,8 @@ unpickler that maps the class to an inert holder is enough to pull the weights o
 
 PARITY UNPINNED: no legacy pickle exists in the reference tree (test/assets/__init__.py:13-14 are
 git-ignored), so this is verified structurally only (names, shapes, a synthetic pickle written
-through the same state layout in tests/test_legacy_import.py). Only the config-f `skip`
-generator (the architecture this engine implements) is accepted; anything else raises.
+through the same state layout in tests/test_legacy_import.py). Only the `skip` generator of
+config-f and config-e (the architecture this engine implements) is accepted; anything else raises.
 """
 
 import io
@@ -121,7 +121,7 @@ def load_legacy_network(network_path: Path):
     Read (G, D, Gs)[2] out of a TF1 StyleGAN2 pickle.
     :return: (resolution, {name: float32 array}) holding exactly the variables of
     `gance_amd.stylegan2.spec.variable_shapes`.
-    :raises ValueError: the pickle is not a config-f skip-architecture StyleGAN2 generator.
+    :raises ValueError: the pickle is not a config-f / config-e skip-architecture StyleGAN2 generator.
     """
     return legacy_network_from_content(restricted_load(network_path))
 
@@ -132,13 +132,19 @@ def legacy_network_from_content(content: Any):
         raise ValueError("expected a pickled (G, D, Gs) tuple of dnnlib Networks")
     raw = extract_generator_variables(content[2])
     resolution = _resolution_of(name[len("G_synthesis/"):] for name in raw if name.startswith("G_synthesis/"))
-    spec = sg2_spec.make_spec(resolution)
+    # the config comes from the top ToRGB (spec.fmap_base_of); a pickle that matches neither is held to the config-f table
+    try:
+        fmap_base = sg2_spec.fmap_base_of(raw, resolution)
+    except ValueError:
+        fmap_base = sg2_spec.FMAP_BASE
+    config = "config-e" if fmap_base == sg2_spec.FMAP_BASE_CONFIG_E else "config-f"
+    spec = sg2_spec.make_spec(resolution, fmap_base)
     variables: Dict[str, np.ndarray] = {}
     for name, shape in sg2_spec.variable_shapes(spec).items():
         if name not in raw:
-            raise ValueError(f"legacy network has no variable {name!r}: not the config-f skip generator")
+            raise ValueError(f"legacy network has no variable {name!r}: not the {config} skip generator")
         value = np.asarray(raw[name], dtype=np.float32)
         if tuple(value.shape) != tuple(shape):
-            raise ValueError(f"legacy variable {name!r} has shape {value.shape}, config-f expects {shape}")
+            raise ValueError(f"legacy variable {name!r} has shape {value.shape}, {config} expects {shape}")
         variables[name] = np.array(value, dtype=np.float32, order="C").reshape(shape)
     return resolution, variables

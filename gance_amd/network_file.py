@@ -25,11 +25,12 @@ class NetworkFile(NamedTuple):
 
     resolution: int
     variables: Dict[str, np.ndarray]
+    fmap_base: int = sg2_spec.FMAP_BASE  # inferred from the variables (spec.fmap_base_of): 16 << 10 config-f, 8 << 10 config-e
 
 
 def save_network(path: Path, resolution: int, variables: Dict[str, np.ndarray]) -> None:
     """Write a generator (raw, un-scaled TF-named variables)."""
-    spec = sg2_spec.make_spec(resolution)
+    spec = sg2_spec.make_spec(resolution, sg2_spec.fmap_base_of(variables, resolution))
     sg2_spec.pack_variables(variables, spec)  # validates names and shapes
     with open(str(path), "wb") as file:
         pickle.dump({"format": FORMAT, "resolution": int(resolution), "variables": dict(variables)}, file, protocol=4)
@@ -48,16 +49,17 @@ def load_network(path: Path) -> NetworkFile:
     try:
         content = legacy_import.restricted_load(path)
         if isinstance(content, dict) and content.get("format") == FORMAT:
-            return NetworkFile(int(content["resolution"]), content["variables"])
+            resolution = int(content["resolution"])
+            return NetworkFile(resolution, content["variables"], sg2_spec.fmap_base_of(content["variables"], resolution))
         resolution, variables = legacy_import.legacy_network_from_content(content)
     except Exception as error:  # pylint: disable=broad-except
         raise RuntimeError(
             f"{path} is neither a gance_amd network file (format tag {FORMAT!r}) nor an importable "
             f"TF1 StyleGAN2 (G, D, Gs) pickle: {error}"
         ) from error
-    return NetworkFile(resolution, variables)
+    return NetworkFile(resolution, variables, sg2_spec.fmap_base_of(variables, resolution))
 
 
-def write_random_network(path: Path, resolution: int, seed: int = 0) -> None:
-    """Random-init generator as a network file."""
-    save_network(path, resolution, sg2_spec.make_random_variables(resolution, seed=seed))
+def write_random_network(path: Path, resolution: int, seed: int = 0, fmap_base: int = sg2_spec.FMAP_BASE) -> None:
+    """Random-init generator as a network file; `fmap_base=8 << 10` writes a config-e one."""
+    save_network(path, resolution, sg2_spec.make_random_variables(resolution, seed=seed, fmap_base=fmap_base))

@@ -1,5 +1,5 @@
 """
-StyleGAN2 config-f generator: static description (layer table, variable names, shapes), the
+StyleGAN2 config-f / config-e generator: static description (layer table, variable names, shapes), the
 random-init weight generator used by the benchmark, and the flat weight-blob packing that the
 C-ABI `gance_engine_create` consumes (`include/gance_hip.h`).
 
@@ -19,7 +19,9 @@ LATENT_SIZE = 512
 MAPPING_LAYERS = 8
 MAPPING_LRMUL = 0.01
 NUM_CHANNELS = 3
-FMAP_BASE = 16 << 10
+FMAP_BASE = 16 << 10  # config-f
+FMAP_BASE_CONFIG_E = 8 << 10  # config-e: the same skip generator with half the feature maps above 32x32
+FMAP_BASES = (FMAP_BASE, FMAP_BASE_CONFIG_E)
 FMAP_MAX = 512
 
 Variables = Dict[str, np.ndarray]
@@ -58,33 +60,67 @@ class SynthesisSpec(NamedTuple):
     num_layers: int  # dlatent rows W: 18 for 1024, 14 for 256
     convs: Tuple[ConvLayer, ...]
     torgbs: Tuple[ToRGBLayer, ...]
+    fmap_base: int = FMAP_BASE  # 16 << 10: config-f, 8 << 10: config-e
 
 
-def make_spec(resolution: int) -> SynthesisSpec:
+def check_fmap_base(fmap_base: int) -> int:
+    """The two published configs of the skip generator this engine runs: config-f (16 << 10) and config-e (8 << 10)."""
+    if fmap_base not in FMAP_BASES:
+        raise ValueError(f"fmap_base must be {FMAP_BASE} (config-f) or {FMAP_BASE_CONFIG_E} (config-e), got {fmap_base}")
+    return int(fmap_base)
+
+
+def make_spec(resolution: int, fmap_base: int = FMAP_BASE) -> SynthesisSpec:
     """
     Layer table of G_synthesis_stylegan2 (skip architecture) for a power-of-two resolution.
     dlatent rows: 4x4 conv -> 0, ToRGB(r) -> 2r-3, Conv0_up(r) -> 2r-5, Conv1(r) -> 2r-4.
     """
+    fmap_base = check_fmap_base(fmap_base)
     res_log2 = int(np.log2(resolution))
     if resolution != 2 ** res_log2 or resolution < 8:
         raise ValueError(f"resolution must be a power of two >= 8, got {resolution}")
-    convs: List[ConvLayer] = [ConvLayer(0, "4x4/Conv", 2, nf(1), nf(1), False)]
-    torgbs: List[ToRGBLayer] = [ToRGBLayer("4x4/ToRGB", 2, nf(1), 1)]
+
+    def fmaps(stage: int) -> int:
+        return nf(stage, fmap_base)
+
+    convs: List[ConvLayer] = [ConvLayer(0, "4x4/Conv", 2, fmaps(1), fmaps(1), False)]
+    torgbs: List[ToRGBLayer] = [ToRGBLayer("4x4/ToRGB", 2, fmaps(1), 1)]
     for res in range(3, res_log2 + 1):
         side = 2 ** res
         convs.append(
-            ConvLayer(res * 2 - 5, f"{side}x{side}/Conv0_up", res, nf(res - 2), nf(res - 1), True)
+            ConvLayer(res * 2 - 5, f"{side}x{side}/Conv0_up", res, fmaps(res - 2), fmaps(res - 1), True)
         )
         convs.append(
-            ConvLayer(res * 2 - 4, f"{side}x{side}/Conv1", res, nf(res - 1), nf(res - 1), False)
+            ConvLayer(res * 2 - 4, f"{side}x{side}/Conv1", res, fmaps(res - 1), fmaps(res - 1), False)
         )
-        torgbs.append(ToRGBLayer(f"{side}x{side}/ToRGB", res, nf(res - 1), res * 2 - 3))
+        torgbs.append(ToRGBLayer(f"{side}x{side}/ToRGB", res, fmaps(res - 1), res * 2 - 3))
     return SynthesisSpec(
         resolution=resolution,
         res_log2=res_log2,
         num_layers=res_log2 * 2 - 2,
         convs=tuple(convs),
         torgbs=tuple(torgbs),
+        fmap_base=fmap_base,
+    )
+
+
+def fmap_base_of(variables: Variables, resolution: int) -> int:
+    """
+    The config a set of variables belongs to, from the shape of the top ToRGB weight (its cin is nf(res_log2 - 1)).
+    Up to 32x32 both configs have the same channel table: that is reported as config-f.
+    :raises ValueError: the shape matches neither config.
+    """
+    res_log2 = int(np.log2(resolution))
+    name = f"G_synthesis/{resolution}x{resolution}/ToRGB/weight"
+    if name not in variables:
+        raise ValueError(f"no variable {name!r}: cannot tell the generator's fmap_base")
+    shape = tuple(np.shape(variables[name]))
+    expected = {base: (1, 1, nf(res_log2 - 1, base), NUM_CHANNELS) for base in FMAP_BASES}
+    for base in FMAP_BASES:  # (config-f first: where both agree it is the answer)
+        if shape == expected[base]:
+            return base
+    raise ValueError(
+        f"variable {name!r} has shape {shape}: config-f expects {expected[FMAP_BASE]}, config-e expects {expected[FMAP_BASE_CONFIG_E]}"
     )
 
 
@@ -95,7 +131,7 @@ def variable_shapes(spec: SynthesisSpec) -> Dict[str, Tuple[int, ...]]:
         shapes[f"G_mapping/Dense{i}/weight"] = (LATENT_SIZE if i == 0 else DLATENT_SIZE, DLATENT_SIZE)
         shapes[f"G_mapping/Dense{i}/bias"] = (DLATENT_SIZE,)
     shapes["dlatent_avg"] = (DLATENT_SIZE,)
-    shapes["G_synthesis/4x4/Const/const"] = (1, nf(1), 4, 4)
+    shapes["G_synthesis/4x4/Const/const"] = (1, nf(1, spec.fmap_base), 4, 4)
     for conv in spec.convs:
         scope = f"G_synthesis/{conv.scope}"
         shapes[f"{scope}/weight"] = (3, 3, conv.cin, conv.cout)
@@ -115,7 +151,7 @@ def variable_shapes(spec: SynthesisSpec) -> Dict[str, Tuple[int, ...]]:
     return shapes
 
 
-def make_random_variables(resolution: int, seed: int = 0, perturb: bool = False) -> Variables:
+def make_random_variables(resolution: int, seed: int = 0, perturb: bool = False, fmap_base: int = FMAP_BASE) -> Variables:
     """
     Random-init generator, the way the published TF code initialises it (equalised learning
     rate): conv / dense / mod weights N(0,1) (mapping weights N(0, 1/lrmul)), const N(0,1), noise
@@ -125,7 +161,7 @@ def make_random_variables(resolution: int, seed: int = 0, perturb: bool = False)
     small random values so that every term of every kernel is exercised (with the plain random
     init the noise and bias terms are identically zero).
     """
-    spec = make_spec(resolution)
+    spec = make_spec(resolution, fmap_base)
     rng = np.random.RandomState(seed)
     variables: Variables = {}
     for name, shape in variable_shapes(spec).items():
@@ -145,7 +181,7 @@ def make_random_variables(resolution: int, seed: int = 0, perturb: bool = False)
     return variables
 
 
-def make_stress_variables(resolution: int, seed: int = 0) -> Variables:
+def make_stress_variables(resolution: int, seed: int = 0, fmap_base: int = FMAP_BASE) -> Variables:
     """
     A generator with the STATISTICS of a trained network, for parity tests only (no trained pickle exists in the
     reference tree; the legacy importer loads real ones): what a random init never shows a kernel. Conv / ToRGB weights
@@ -155,7 +191,7 @@ def make_stress_variables(resolution: int, seed: int = 0) -> Variables:
     Winograd forms amplify rounding by the norms of their transforms (F(4x4,3x3), points 0, +-1, +-2: ~10 x 20 per
     layer), which is why the kernels' accuracy is stated on this network beside the random-init one.
     """
-    spec = make_spec(resolution)
+    spec = make_spec(resolution, fmap_base)
     rng = np.random.RandomState(seed)
     variables: Variables = {}
 

@@ -34,13 +34,15 @@ const char* gance_last_error(void);
 int gance_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------ */
-/* Latent -> frame: StyleGAN2 config-f generator engine                                        */
+/* Latent -> frame: StyleGAN2 generator engine (the skip generator of config-f and config-e)  */
 /* ------------------------------------------------------------------------------------------ */
 
 typedef struct gance_engine gance_engine; /* opaque; owns weights + workspace in HBM */
 
+/* The channel table is nf(stage) = clip(fmap_base >> stage, 1, 512): fmap_base = 16 << 10 (config-f) unless `flags` carries
+ * GANCE_FLAG_FMAP_BASE_8K (config-e: half the channels from 64x64 up, 16 at 1024x1024). Up to 32x32 both are one network. */
 typedef struct gance_engine_config {
-    int32_t resolution; /* output side, power of two in [8, 1024]; 1024 = FFHQ config-f        */
+    int32_t resolution; /* output side, power of two in [8, 1024]; 1024 = FFHQ config-f / config-e */
     int32_t max_batch;  /* workspace is sized for this many frames per call (>= 1)             */
     int32_t device;     /* HIP device ordinal                                                  */
     int32_t flags;      /* GANCE_FLAG_*                                                        */
@@ -65,6 +67,10 @@ typedef struct gance_engine_config {
  * Calls that share it are ordered by an event, on whatever streams they run. PRIVATE_WORKSPACE gives an engine
  * its own (calls of different engines may then overlap on different streams). */
 #define GANCE_FLAG_PRIVATE_WORKSPACE 32
+/* The network is config-e (fmap_base = 8 << 10): gance_engine_create expects the blob of that channel table
+ * (gance_weight_blob_floats_flags) and gance_engine_describe_plan plans its layers. Engines with and without it never share
+ * a workspace. */
+#define GANCE_FLAG_FMAP_BASE_8K 128
 #define GANCE_FLAG_WINOGRAD43 64 /* with FORCE_WINOGRAD: Conv1 layers from 32x32 up in Winograd F(4x4,3x3) form wherever the kernel supports the layer */
 
 /*
@@ -91,6 +97,8 @@ int32_t gance_engine_resolution(const gance_engine* engine);
 int32_t gance_engine_max_batch(const gance_engine* engine);
 /* Number of floats gance_engine_create expects for `resolution` (0 if unsupported). */
 uint64_t gance_weight_blob_floats(int32_t resolution);
+/* ... for an engine created with `flags`: only GANCE_FLAG_FMAP_BASE_8K changes the count (without it: the function above). */
+uint64_t gance_weight_blob_floats_flags(int32_t resolution, int32_t flags);
 
 /*
  * Matrix path. Replaces create_image_matrix (network_functions.py:160-169):

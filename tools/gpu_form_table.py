@@ -11,6 +11,7 @@ uint8; convT two-pass up layer (+ fir pass), convTF / convTFp one fused up kerne
 runs; the table printed is that of the last combination. --trace FILE also writes, per combination and batch size, every step
 name of the call and a sha256 of the returned uint8 frames (weights from make_random_variables(perturb=True), so that noise
 and bias terms are live): two libraries (GANCE_HIP_LIBRARY) that plan and compute the same give identical files.
+--fmap-base 8192 traces a config-e generator (profiles/launch_plan_config_e_256cus.txt, held by tests/test_config_e_plan.py).
 --compact TRACE... needs no GPU: it prints the traces' names from `styles` on (a gance_synthesize_w call; the nine launches
 of the mapping network in front are the same in every call) in the run-length form of profiles/launch_plan_256cus.txt, which
 tests/test_engine_plan.py holds gance_engine_describe_plan to.
@@ -31,6 +32,7 @@ parser.add_argument("max_batch", nargs="?", type=int, default=64)
 parser.add_argument("--conv-form", default="auto", help="auto, direct, winograd, winograd43; or a comma-separated list")
 parser.add_argument("--up-form", default="auto", help="auto, split, fused; or a comma-separated list")
 parser.add_argument("--batches", default=None, help="comma-separated frames per call (default: 1 ... max_batch)")
+parser.add_argument("--fmap-base", type=int, default=16 << 10, help="16384: a config-f generator (default); 8192: a config-e one")
 parser.add_argument("--trace", default=None, help="append step names and frame hashes of every call to this file")
 parser.add_argument("--compact", nargs="+", default=None, help="trace files to print in run-length form (no GPU)")
 options = parser.parse_args()
@@ -79,7 +81,7 @@ from gance_amd.stylegan2 import spec as sg2_spec  # noqa: E402
 
 resolution, max_batch = options.resolution, options.max_batch
 batches = [int(b) for b in options.batches.split(",")] if options.batches else list(range(1, max_batch + 1))
-variables = sg2_spec.make_random_variables(resolution, seed=0, perturb=options.trace is not None)
+variables = sg2_spec.make_random_variables(resolution, seed=0, perturb=options.trace is not None, fmap_base=options.fmap_base)
 knobs = ",".join(f"{k[len('GANCE_TUNE_'):]}={v}" for k, v in sorted(os.environ.items()) if k.startswith("GANCE_TUNE_")) or "-"
 for conv_form in options.conv_form.split(","):
     for up_form in options.up_form.split(","):
