@@ -14,7 +14,10 @@ variables, so it runs config-e unchanged).
     the plan runs the 32 -> 16 up layer as one fused launch (read from gance_engine_describe_plan for the device's CU count);
     conv_form "auto" / "direct", up_form "auto" / "split"; every-term and stress networks, and the every-term network with a noise
     plane per sample at strength 0.5 (the method of tests/test_isolated_noise_gpu.py, planes read back with debug_noise).
-    A tile seam or an image edge handled wrongly is an error of order 1 here.
+    A tile seam or an image edge handled wrongly is an error of order 1 here. And 17 frames, every-term and loud networks, conv
+    layers 14 and 15 only: the one batch at which the default plan on 256 CUs runs the 64 -> 32 up layer in the pair form of the
+    fused up kernel (convTFp13_512x512_64->32/16x, between convV12+rgb and convV14+rgb; at 16 and at 18 frames it is "/s3").
+    tests/test_isolated_coverage.py holds these batches against the planner (LARGE_CASES of tests/isolated_config_e_cases.py).
   * The frame-emitting launch (conv16+torgb_1024x1024_16->16: conv, ToRGB 16 -> 3, + upsampled 512^2 image + bias, uint8) by the
     method of tests/test_isolated_image_gpu.py: layer 17's activation (tap: the unfused launch) and debug_image_after of the 512^2
     stage through ONE fp64 torgb_layer against the float image of a whole untapped call; ceilings 2e-5 / 1e-4 (stress) and
@@ -28,7 +31,8 @@ Measured on an MI355X (256 CUs), every configuration below; the inputs are seede
 up as convTF15/16 and as convT15 + fir15, 16 -> 16 as conv16) 2.5e-7 ... 1.1e-6; 64 -> 32 up at 512^2 (convT13, /s3) 2.7e-7 ... 5.9e-7;
 32 -> 32 at 512^2 direct 5.4e-7 ... 1.6e-6, F(4x4,3x3) 8.9e-7 ... 4.0e-6; sensitivity to another sample's plane 0.28 ... 0.65.
 The frame-emitting launch: 1.6e-7 ... 2.1e-7, 0.64 ... 1.32 times the float32 oracle step's error; bytes exact; 38.6 % ... 66.5 % of
-them unsaturated. On 256 CUs the 32 -> 16 up layer is one fused launch from 2 frames per call.
+them unsaturated. On 256 CUs the 32 -> 16 up layer is one fused launch from 2 frames per call. The 17-frame rows: convTFp13/16x
+2.6e-7 ... 3.8e-7, convV14+rgb behind it 1.1e-6 ... 4.7e-6, sensitivity 0.27 ... 0.38.
 
 Bars are the project's: 2e-5 per layer in isolation, 1e-4 on the stress network, 1e-4 on the whole-chain float image, bytes within
 1 LSB on fewer than 1e-3 of them (tests/test_synthesis_gpu.py).
@@ -65,6 +69,13 @@ BATCHES = (1, 3, 16)
 ORACLE_ROWS = [0, 1, 2, 15]
 FIRST_LAYER = 14  # conv layers 14 ... 17 (1-based): Conv0_up / Conv1 of 512^2 and 1024^2
 UP_16 = "convTF15_1024x1024_32->16/16"
+# 17 frames: the one batch at which the default plan on 256 CUs runs the 64 -> 32 up layer in the pair form of the fused up kernel
+# (layers 9, 11 and 13 leave "/s3" for "/16x" at exactly 17 frames: tests/isolated_config_e_cases.py). Only conv layers 14 and 15
+# (1-based) are checked there: the 1024^2 layers keep their one form from 2 frames up, and their 17-frame activations are over a
+# gigabyte each to read back.
+PAIR_FORM_BATCH = 17
+PAIR_FORM_LAST_LAYER = 15
+UP_32_PAIR_FORM = "convTFp13_512x512_64->32/16x"
 LAST = "conv16+torgb_1024x1024_16->16"
 
 # dlatents = RandomState(seed).randn(batch, 18, 512) of the frame-emitting checks on the every-term 1024^2 network: batch -> the
@@ -214,6 +225,8 @@ ISOLATED = [
     ("stress", "direct", "split", 3),
     ("loud", "auto", "auto", 0),
     ("loud", "direct", "split", 3),
+    ("every_term", "auto", "auto", PAIR_FORM_BATCH),
+    ("loud", "auto", "auto", PAIR_FORM_BATCH),
 ]
 
 
@@ -221,6 +234,7 @@ ISOLATED = [
 def test_layers_512_and_1024_in_isolation(library, network: str, conv_form: str, up_form: str, batch: int) -> None:
     num_cus = torch.cuda.get_device_properties(0).multi_processor_count
     fused_batch = _fused_up_batch(library, num_cus)
+    last_layer = PAIR_FORM_LAST_LAYER if batch == PAIR_FORM_BATCH else 17
     batch = batch or fused_batch
     spec = sg2_spec.make_spec(LARGE, fmap_base=CONFIG_E)
     variables = _variables(network, LARGE)
@@ -235,7 +249,8 @@ def test_layers_512_and_1024_in_isolation(library, network: str, conv_form: str,
         if per_sample_noise:
             engine.randomize_noise(seed=NOISE_SEED, count=batch)
         x = engine.debug_activation_after(dlatents, FIRST_LAYER - 1)[samples].copy()
-        for n in range(FIRST_LAYER, len(spec.convs) + 1):
+        assert len(spec.convs) == 17
+        for n in range(FIRST_LAYER, last_layer + 1):
             conv = spec.convs[n - 1]
             got = engine.debug_activation_after(dlatents, n)[samples].copy()
             tapped[n] = _conv_launches(engine)[conv.layer_idx]
@@ -270,9 +285,10 @@ def test_layers_512_and_1024_in_isolation(library, network: str, conv_form: str,
         assert err < ceiling, f"conv layer {n} ({spec.convs[n - 1].scope}, {tapped[n]}), sample {s}: isolated error {err:.2e}"
         assert sens is None or sens > SENSITIVITY, f"conv layer {n}, sample {s}: another plane moves the oracle layer by only {sens:.3f}"
     # the forms the checks were meant to reach
-    for n in range(FIRST_LAYER, len(spec.convs)):  # (the tap on the last layer runs it unfused: below)
+    for n in range(FIRST_LAYER, min(last_layer, 16) + 1):  # (the tap on the last layer runs it unfused: below)
         assert tapped[n] == launches[spec.convs[n - 1].layer_idx], f"layer {n}: {tapped[n]} stopped, {launches[spec.convs[n - 1].layer_idx]} in the whole call"
-    assert tapped[17] == "conv16_1024x1024_16->16" and launches[16] == LAST and whole_call[-1] == LAST, (tapped[17], whole_call[-3:])
+    assert last_layer < 17 or tapped[17] == "conv16_1024x1024_16->16", tapped[17]
+    assert launches[16] == LAST and whole_call[-1] == LAST, whole_call[-3:]
     fused = up_form == "auto" and batch >= fused_batch
     assert launches[15] == (UP_16 if fused else "convT15_1024x1024_32->16"), launches[15]
     assert ("fir15_1024x1024" in whole_call) == (not fused)
@@ -280,6 +296,8 @@ def test_layers_512_and_1024_in_isolation(library, network: str, conv_form: str,
         assert launches[14] == "conv14_512x512_32->32", launches[14]
     if up_form == "split":
         assert launches[13] == "convT13_512x512_64->32", launches[13]
+    if batch == PAIR_FORM_BATCH and up_form == "auto" and num_cus == 256:
+        assert launches[13] == UP_32_PAIR_FORM and "fir13_512x512" not in whole_call, launches[13]
 
 
 # ---- the frame-emitting launch ----
