@@ -231,6 +231,15 @@ SIGNATURES = {
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
     ),
     "gance_jpeg_parse_header": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "gance_png_encode_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_png_encode_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_jpeg_decode_bounds": (
         ctypes.c_int,
         [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
@@ -291,7 +300,7 @@ ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
     "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8", "gance_jpeg_parse_header",
     "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8", "gance_debug_draw_text_u8", "gance_debug_font_columns",
-    "gance_engine_debug_read_skip_image",
+    "gance_engine_debug_read_skip_image", "gance_png_encode_bounds", "gance_png_encode_u8",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -877,6 +886,37 @@ def jpeg_encode_rect_device(  # pylint: disable=too-many-arguments
         lib.gance_jpeg_encode_rect_u8(
             d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
         ),
+    )
+
+
+# filtered bytes per independently deflated segment of a PNG (kSegmentBytes of csrc/png.hip): one IDAT chunk each
+PNG_SEGMENT_BYTES = 32768
+
+
+def png_encode_bounds(batch: int, width: int, height: int) -> Tuple[int, int]:
+    """(workspace bytes, output capacity) of one `png_encode_device` call of `batch` frames [height][width][3]. The capacity
+    is the size of the batch with every segment stored: batch * (63 + 17 * segments + height * (3 * width + 1)).
+    :raises ValueError: width or height outside [1, 8192], or batch < 1."""
+    lib = load_library()
+    workspace, capacity = ctypes.c_uint64(), ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_png_encode_bounds(batch, width, height, ctypes.byref(workspace), ctypes.byref(capacity)))
+    return int(workspace.value), int(capacity.value)
+
+
+def png_encode_device(  # pylint: disable=too-many-arguments
+    d_frames: int, batch: int, width: int, height: int, d_workspace: int, workspace_bytes: int, d_out: int, out_capacity: int,
+    d_offsets: int, stream: int = 0,
+) -> None:
+    """
+    PNG (8-bit RGB, libpng's minimum-sum filter choice per row, Huffman-only deflate in segments of PNG_SEGMENT_BYTES) of
+    uint8 frames [batch][height][width][3] in HBM: frame b's file lands at d_out[offsets[b]:offsets[b + 1]], offsets int64
+    [batch + 1] on the device. Asynchronous on `stream`.
+    :raises ValueError: bad width or height, workspace or capacity below `png_encode_bounds`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_png_encode_u8(d_frames, batch, width, height, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None),
     )
 
 

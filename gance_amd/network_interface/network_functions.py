@@ -112,6 +112,32 @@ class LoadedNetwork:
             out.append(self.engine.synthesize_z(data[start : start + self.max_batch], truncation_psi=TRUNCATION_PSI))
         return np.concatenate(out) if len(out) > 1 else out[0]
 
+    def create_images_vector_device(self, data: np.ndarray, randomize_noise: bool = True, noise_seed: Optional[int] = None) -> torch.Tensor:
+        """
+        Stills: z (B, L) -> uint8 [B, H, W, 3] left in HBM on the engine's device, for consumers that go on there (the PNG
+        encoder of synthesize_images). Frame b is exactly the image `create_image_vector(data[b])` gives: the engine picks
+        each layer's kernel form by the batch of the call, and the forms round differently, so every frame goes through a
+        call of its own (queued back to back, no host synchronisation between them). Fresh noise per frame as in the
+        reference; with `noise_seed` every frame reads the planes `create_image_vector(z, noise_seed=noise_seed)` reads.
+        """
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if data.ndim != 2 or len(data) < 1:
+            raise ValueError(f"data must be (B, L) with B >= 1, got {data.shape}")
+        cuda = torch.device("cuda", self.engine.device)
+        with torch.cuda.device(cuda):
+            current = torch.cuda.current_stream(cuda)
+            stream = current.cuda_stream
+            z = torch.from_numpy(data).to(cuda)
+            frames = torch.empty((len(data), self.resolution, self.resolution, 3), dtype=torch.uint8, device=cuda)
+            if not randomize_noise:
+                self.engine.restore_noise(stream=stream)
+            for index in range(len(data)):
+                if randomize_noise and (index == 0 or noise_seed is None):
+                    self.engine.randomize_noise(noise_seed, count=1, stream=stream)
+                self.engine.synthesize_z_device(z[index].data_ptr(), 1, TRUNCATION_PSI, frames[index].data_ptr(), 0, stream)
+            z.record_stream(current)
+        return frames
+
     def create_images_matrix(self, data: np.ndarray) -> np.ndarray:
         """dlatents (B, W, L) -> uint8 (B, H, W, 3): synthesis only, stored noise (network_functions.py:160-169: randomize_noise=False)."""
         self.engine.restore_noise()
@@ -119,9 +145,10 @@ class LoadedNetwork:
         out = [self.engine.synthesize_w(data[start : start + self.max_batch]) for start in range(0, len(data), self.max_batch)]
         return np.concatenate(out) if len(out) > 1 else out[0]
 
-    def create_image_vector(self, data: SingleVector) -> RGBInt8ImageType:
-        """One z vector -> one image; the callee adds the batch axis (network_functions.py:127-134)."""
-        return RGBInt8ImageType(self.create_images_vector(np.reshape(data, (1, *np.shape(data))))[0])
+    def create_image_vector(self, data: SingleVector, noise_seed: Optional[int] = None) -> RGBInt8ImageType:
+        """One z vector -> one image; the callee adds the batch axis (network_functions.py:127-134). `noise_seed` (not in the
+        reference) makes the fresh noise repeatable, as in `create_images_vector`."""
+        return RGBInt8ImageType(self.create_images_vector(np.reshape(data, (1, *np.shape(data))), noise_seed=noise_seed)[0])
 
     def create_image_matrix(self, data: SingleMatrix) -> RGBInt8ImageType:
         """One (W, L) latent matrix -> one image."""
@@ -262,9 +289,12 @@ class MultiNetwork:
         return self._loaded[self._network_paths[index]]
 
     @_raise_exception_if_unloaded
-    def indexed_create_image_vector(self: "MultiNetwork", index: int, data: SingleVector) -> RGBInt8ImageType:
-        """Image of network `index` for a z vector (network_functions.py:565-576)."""
-        return self._network_at(index).create_image_vector(data)
+    def indexed_create_image_vector(self: "MultiNetwork", index: int, data: SingleVector, noise_seed: Optional[int] = None) -> RGBInt8ImageType:
+        """Image of network `index` for a z vector (network_functions.py:565-576); `noise_seed` (not in the reference) makes
+        its fresh noise repeatable."""
+        if noise_seed is None:
+            return self._network_at(index).create_image_vector(data)
+        return self._network_at(index).create_image_vector(data, noise_seed=noise_seed)
 
     @_raise_exception_if_unloaded
     def indexed_create_image_matrix(self: "MultiNetwork", index: int, data: SingleMatrix) -> RGBInt8ImageType:
@@ -283,6 +313,11 @@ class MultiNetwork:
         """Batched form: (B, L) z vectors or (B, W, L) latent matrices -> (B, H, W, 3) uint8."""
         network = self._network_at(index)
         return network.create_images_vector(data) if np.ndim(data) == 2 else network.create_images_matrix(data)
+
+    @_raise_exception_if_unloaded
+    def indexed_create_images_vector_device(self: "MultiNetwork", index: int, data: np.ndarray, noise_seed: Optional[int] = None) -> torch.Tensor:
+        """`indexed_create_image_vector` of each of (B, L) z vectors, exactly, the frames uint8 [B, H, W, 3] left in HBM."""
+        return self._network_at(index).create_images_vector_device(data, noise_seed=noise_seed)
 
     @property
     def network_indices(self: "MultiNetwork") -> List[int]:

@@ -9,6 +9,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.blend(audio, latent_row0, blend)       [samples] f32, [F, L] f32 -> ([N, depth, L] f32, [N] i32)
     torch.ops.gance.jpeg_encode_rect(frames, quality)      [B, H, W, 3] u8  -> the same for frames that are not square
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
+    torch.ops.gance.png_encode(frames)                     [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
     torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
@@ -283,6 +284,38 @@ def jpeg_encode_rect(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, 
 def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
     batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     _, capacity = hip_lib.jpeg_encode_rect_bounds(batch, width, height)
+    return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+@torch.library.custom_op("gance::png_encode", mutates_args=(), device_types="cuda")
+def png_encode(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    Lossless PNG of each frame (write_image, still_image_common.py:19-28): `data` [capacity] u8 holds the files back to
+    back, frame b at data[offsets[b]:offsets[b + 1]]; `capacity` is the worst case of the shape (hip_lib.png_encode_bounds),
+    only offsets[-1] bytes are written. H and W are any sizes in [1, 8192]; B == 0 gives empty data and offsets [0].
+    """
+    _require_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [B, H, W, 3], got {tuple(frames.shape)}")
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if batch == 0:
+        return frames.new_empty((0,), dtype=torch.uint8), frames.new_zeros((1,), dtype=torch.int64)
+    workspace_bytes, capacity = hip_lib.png_encode_bounds(batch, width, height)
+    frames = frames.contiguous()
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
+    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
+    hip_lib.png_encode_device(
+        frames.data_ptr(), batch, width, height, workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity, offsets.data_ptr(),
+        _stream(frames),
+    )
+    return data, offsets
+
+
+@png_encode.register_fake
+def _(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    capacity = hip_lib.png_encode_bounds(batch, width, height)[1] if batch else 0
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
 
 

@@ -396,6 +396,26 @@ int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t wi
                               void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                               int64_t* d_offsets, void* stream);
 
+/* ---- PNG still encoder -------------------------------------------------------------------------
+ * Replaces PIL's Image.save(format="PNG") of write_image (gance/image_sources/still_image_common.py:19-28) and of
+ * synthesize_images.py:188-191: frames are encoded in HBM as standard PNG files (signature, IHDR with 8-bit depth,
+ * colour type 2, no interlace, IDAT chunks, IEND). Each row takes the filter (None, Sub, Up, Average, Paeth) with the
+ * smallest sum of |int8(filtered byte)|, ties to the lowest number; the filtered stream is deflated in independent
+ * segments of 32768 bytes, each one dynamic-Huffman block over literals and end-of-block (no match search) closed by
+ * an empty stored block, or one stored block whenever that is not larger; one IDAT chunk per segment and one for the
+ * Adler-32. A frame of one flat colour therefore costs about 1 bit per byte.
+ * gance_png_encode_bounds: host only; the workspace and output capacity one call needs. The capacity is exact for
+ * the worst case (every segment stored): batch * (63 + 17 * segments + height * (3 * width + 1)).
+ * batch >= 1, width and height in [1, 8192].
+ * gance_png_encode_u8: d_frames [batch][height][width][3] uint8 RGB (device); d_workspace (device, 16-byte aligned)
+ * of workspace_bytes; d_out (device) receives the files back to back, frame b at [d_offsets[b], d_offsets[b + 1]);
+ * d_offsets [batch + 1] int64 (device). Asynchronous on `stream`; a frame's bytes are the same whatever the batch it
+ * is encoded in. Returns GANCE_ERR_INVALID_ARGUMENT before touching a device for a NULL pointer, a size out of range,
+ * or a workspace or capacity below the bounds. */
+int gance_png_encode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes, uint64_t* out_capacity);
+int gance_png_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, void* d_workspace,
+                        uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream);
+
 /* ---- Motion-JPEG frame decoder -----------------------------------------------------------------
  * The other half of the encoder above, and what frames_in_video (gance/image_sources/video_common.py:229-298) gets from
  * cv2.VideoCapture: baseline sequential JFIF files (SOF0, 8 bit, three components sampled 2x1 / 1x1 / 1x1, one
