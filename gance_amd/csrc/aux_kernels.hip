@@ -9,7 +9,6 @@
 
 #include <cmath>
 
-#include <cstdlib>
 
 #include "kernels.h"
 
@@ -310,13 +309,10 @@ __global__ __launch_bounds__(256) void fir_epilogue_kernel(const FirArgs p) {
 
 hipError_t launch_fir_epilogue(const FirArgs& args, hipStream_t stream) {
     // 2 position rows per thread (measured best: +7 % over 1, same as 4) when the grid still fills the chip
-    static const int forced = [] { const char* v = std::getenv("GANCE_TUNE_FIR_RQ"); return v ? std::atoi(v) : 0; }();
-    int rq = (args.H % 2 == 0 && (size_t)args.B * args.C * (args.H / 2) * (args.W / 4) >= 256 * 256 * 4) ? 2 : 1;
-    if (forced == 1 || forced == 2 || forced == 4) rq = (args.H % forced == 0) ? forced : 1;
+    const int rq = (args.H % 2 == 0 && (size_t)args.B * args.C * (args.H / 2) * (args.W / 4) >= 256 * 256 * 4) ? 2 : 1;
     const size_t total = (size_t)args.B * args.C * (args.H / rq) * (args.W / 4);
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (rq == 4) hipLaunchKernelGGL(fir_epilogue_kernel<4>, grid, dim3(256), 0, stream, args);
-    else if (rq == 2) hipLaunchKernelGGL(fir_epilogue_kernel<2>, grid, dim3(256), 0, stream, args);
+    if (rq == 2) hipLaunchKernelGGL(fir_epilogue_kernel<2>, grid, dim3(256), 0, stream, args);
     else hipLaunchKernelGGL(fir_epilogue_kernel<1>, grid, dim3(256), 0, stream, args);
     return hipGetLastError();
 }

@@ -451,7 +451,6 @@ gance::WinoGemmArgs winogemm_args(const gance_engine* e, int li, const float* x,
     g.s_stride = e->ctot;
     g.d_stride = e->dtot;
     g.n_tiles = gance::winogemm_n_tiles(B, res, res);
-    g.bf16_split = e->caps[li].gemm_split;  // (as the weights were arranged)
     return g;
 }
 
@@ -477,7 +476,6 @@ gance::UpGemmArgs upgemm_args(const gance_engine* e, int li, const float* x, lon
     g.s_stride = e->ctot;
     g.d_stride = e->dtot;
     g.n_tiles = gance::upgemm_n_tiles(B, H, H);
-    g.bf16_split = e->caps[li].gemm_split;
     return g;
 }
 
@@ -905,35 +903,21 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     const float mod_coef = (float)(1.0 / std::sqrt((double)kDlatent));
     std::vector<gance::DemodLayer> demod_layers(nconv);
     // every form's weight image beyond the direct one, in the pool's order (enum WeightImage): its size and how it is arranged
-    // from the scaled HWIO weights (split: LayerCaps::gemm_split, three bf16 parts per value = 1.5 x the floats)
+    // from the scaled HWIO weights
     struct WeightImageKind {
-        size_t (*floats)(int cin, int cout, int split);
-        void (*arrange)(const float* scaled, int cin, int cout, int split, float* out);
+        size_t (*floats)(int cin, int cout);
+        void (*arrange)(const float* scaled, int cin, int cout, float* out);
     };
     static const WeightImageKind kinds[kNumWeightImages] = {
         // U = G w G^T of the scaled weights, in the Winograd kernel's LDS image [m tile][chunk][16][4][32]
-        {[](int ci, int co, int) { return gance::winograd_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::winograd_transform_weights(w, ci, co, out); }},
-        {[](int ci, int co, int) { return gance::winograd64_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::winograd64_transform_weights(w, ci, co, out); }},
-        {[](int ci, int co, int) { return gance::winograd43_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::winograd43_transform_weights(w, ci, co, out); }},
-        {[](int ci, int co, int) { return gance::upfir16_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::upfir16_arrange_weights(w, ci, co, kUpTapWeight, out); }},
-        {[](int ci, int co, int split) { return gance::winogemm_weight_floats(ci, co) * (split ? 3 : 2) / 2; },
-         [](const float* w, int ci, int co, int split, float* out) {
-             if (split) gance::winogemm_arrange_weights_split(w, ci, co, out);
-             else gance::winogemm_arrange_weights(w, ci, co, out);
-         }},
-        {[](int ci, int co, int split) { return gance::upgemm_weight_floats(ci, co) * (split ? 3 : 2) / 2; },
-         [](const float* w, int ci, int co, int split, float* out) {
-             if (split) gance::upgemm_arrange_weights_split(w, ci, co, kUpTapWeight, out);
-             else gance::upgemm_arrange_weights(w, ci, co, kUpTapWeight, out);
-         }},
-        {[](int ci, int co, int) { return gance::upfirs_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::upfirs_arrange_weights(w, ci, co, kUpTapWeight, out); }},
-        {[](int ci, int co, int) { return gance::upfir16x_weight_floats(ci, co); },
-         [](const float* w, int ci, int co, int, float* out) { gance::upfir16x_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {gance::winograd_weight_floats, gance::winograd_transform_weights},
+        {gance::winograd64_weight_floats, gance::winograd64_transform_weights},
+        {gance::winograd43_weight_floats, gance::winograd43_transform_weights},
+        {gance::upfir16_weight_floats, [](const float* w, int ci, int co, float* out) { gance::upfir16_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {gance::winogemm_weight_floats, gance::winogemm_arrange_weights},
+        {gance::upgemm_weight_floats, [](const float* w, int ci, int co, float* out) { gance::upgemm_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {gance::upfirs_weight_floats, [](const float* w, int ci, int co, float* out) { gance::upfirs_arrange_weights(w, ci, co, kUpTapWeight, out); }},
+        {gance::upfir16x_weight_floats, [](const float* w, int ci, int co, float* out) { gance::upfir16x_arrange_weights(w, ci, co, kUpTapWeight, out); }},
     };
     e->caps.resize(nconv);
     e->conv_bias.resize(nconv);
@@ -971,8 +955,8 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         }
         for (int f = 0; f < kNumWeightImages; ++f) {
             if (!caps.has[f]) continue;
-            caps.w[f] = reserve(kinds[f].floats(c.cin, c.cout, caps.gemm_split));
-            kinds[f].arrange(scaled.data(), c.cin, c.cout, caps.gemm_split, &pool[caps.w[f]]);
+            caps.w[f] = reserve(kinds[f].floats(c.cin, c.cout));
+            kinds[f].arrange(scaled.data(), c.cin, c.cout, &pool[caps.w[f]]);
         }
         src += wn;
         demod_layers[i] = {(long long)w2_cursor, e->conv_s_off[i], e->conv_d_off[i], c.cin, c.cout};
@@ -1051,15 +1035,14 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         const ConvLayerHost& c = e->convs[i];
         const int H = (1 << c.res_log2) / 2;
         if (c.up && gance::upgemm_supported(c.cin, c.cout, H, H)) {
-            // (x 3/2: room for the three bf16 parts of the experiment's operand images, whatever this engine's knobs say)
             const int samples = std::max(1, std::min(Bmax, gance::upgemm_max_columns(c.cout, e->tune.upgemm_buffer_columns) / (H * H)));
-            e->up_packed_floats = std::max(e->up_packed_floats, gance::upgemm_packed_floats(samples, c.cin, H, H) * 3 / 2);
+            e->up_packed_floats = std::max(e->up_packed_floats, gance::upgemm_packed_floats(samples, c.cin, H, H));
             e->up_prod_floats = std::max(e->up_prod_floats, gance::upgemm_prod_floats(samples, c.cout, H, H));
         }
         if (!c.up && i > 0 && gance::winogemm_supported(c.cin, c.cout, 2 * H, 2 * H)) {
             const int tiles = (H / 2) * (H / 2);  // 4x4 output tiles per sample
             const int samples = std::max(1, std::min(Bmax, gance::kWinoGemmMaxColumns / tiles));
-            e->up_packed_floats = std::max(e->up_packed_floats, gance::winogemm_packed_floats(samples, c.cin, 2 * H, 2 * H) * 3 / 2);
+            e->up_packed_floats = std::max(e->up_packed_floats, gance::winogemm_packed_floats(samples, c.cin, 2 * H, 2 * H));
             e->up_prod_floats = std::max(e->up_prod_floats, gance::winogemm_prod_floats(samples, c.cout, 2 * H, 2 * H));
         }
     }

@@ -84,7 +84,6 @@ struct Tuning {
     int debug_conv = 0;      // GANCE_DEBUG_CONV: ConvArgs::debug_flags; bit 16 dumps per-block phase stamps of the direct-form launches
     std::string debug_dump;  // GANCE_DEBUG_DUMP: ... and every block's stamps of the launches whose name contains this
     struct PerEngine {
-        int gemm_bf16 = 0;  // experiment GANCE_TUNE_GEMM_BF16X6: 1 = the GEMM forms on the bf16 matrix cores from split operands, bf16 x 3 (six terms); any non-zero value selects it (a stale 2, the removed fp16 x 2 mode, too)
         int upfir_split = 1;  // GANCE_TUNE_UPFIR_SPLIT: 0 never, 1 (default) where a launch fills the chip without row segments, 2 wherever supported
         int upfir_split_narrow = 1;  // GANCE_TUNE_UPFIR_SPLIT_NARROW: the split form's narrow geometries (inputs 32 and 16 wide) in mode 1 and 2 by the fill rule; 0 never
         int upfir_split_max_res = 1024;  // GANCE_TUNE_UPFIR_SPLIT_MAXRES: the largest OUTPUT side that takes the split form in mode 1 (measured: DESIGN.md section 3; 512 until the staging went to 16-byte loads)
@@ -114,7 +113,6 @@ Tuning read_tuning() {
     t.graph = number("GANCE_TUNE_GRAPH", 1) != 0;
     t.debug_conv = number("GANCE_DEBUG_CONV", 0);
     if (const char* v = std::getenv("GANCE_DEBUG_DUMP")) t.debug_dump = v;
-    t.engine.gemm_bf16 = number("GANCE_TUNE_GEMM_BF16X6", 0) != 0 ? 1 : 0;
     t.engine.upfir_split = std::max(0, std::min(2, number("GANCE_TUNE_UPFIR_SPLIT", 1)));
     t.engine.upfir_split_max_res = number("GANCE_TUNE_UPFIR_SPLIT_MAXRES", 1024);
     t.engine.upfir_split_narrow = number("GANCE_TUNE_UPFIR_SPLIT_NARROW", 1) == 0 ? 0 : 1;
@@ -216,7 +214,6 @@ struct LayerCaps {
     bool has[kNumWeightImages] = {};  // this engine may run the layer in that form ...
     size_t w[kNumWeightImages] = {};  // ... from the image at this pool offset
     size_t direct_w = 0;              // the direct form's image
-    int gemm_split = 0;  // the layer's GEMM form runs on the bf16 matrix cores from split operands (Tuning::PerEngine::gemm_bf16, where 256-row block tiles fit)
 };
 
 LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, const Tuning& tune) {
@@ -229,8 +226,6 @@ LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, 
         k.has[kWino64] = gance::winograd64_supported(c.cin, c.cout, res, res);
         k.has[kWino43] = after_up && res >= 32 && res <= wino43_max_res(flags, tune) && gance::winograd43_supported(c.cin, c.cout, res, res);
         k.has[kWinoGemm] = i > 0 && tune.winogemm_min_columns > 0 && wino43_max_res(flags, tune) >= 16 && gance::winogemm_supported(c.cin, c.cout, res, res);
-        // (the experiment's 256-row block tiles need Cout to be a multiple of 256: a 128-channel layer of a reduced network keeps the fp32 GEMM)
-        k.gemm_split = c.cout % 256 == 0 ? tune.engine.gemm_bf16 : 0;
     } else {
         k.has[kUpfir16] = gance::upfir16_supported(c.cin, c.cout, H, H);
         k.has[kUpGemm] = tune.upgemm_min_columns > 0 && gance::upgemm_supported(c.cin, c.cout, H, H);
@@ -239,8 +234,6 @@ LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, 
         k.has[kUpfirSplit] = tune.engine.upfir_split != 0 && c.cout >= 32 &&
                              (gance::upfirs_supported(c.cin, c.cout, H, H) || (tune.engine.upfir_split_narrow != 0 && gance::upfirs_narrow_supported(c.cin, c.cout, H, H)));
         k.has[kUpfir16x] = tune.upfir16x != 0 && c.cout >= 32 && gance::upfir16x_supported(c.cin, c.cout, H, H);
-        // (... 9 Cout to be a multiple of 256: the 128-channel layer keeps the fp32 GEMM)
-        k.gemm_split = (9 * c.cout) % 256 == 0 ? tune.engine.gemm_bf16 : 0;
     }
     return k;
 }

@@ -49,7 +49,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -86,16 +85,9 @@ constexpr int kRing = 3;
 constexpr int kHaloCols = 4;        // input columns X0 - 2, X0 - 1, X0 + 63, X0 + 64
 constexpr int kHaloUnits = kRows * kHaloCols * kPlanes;
 constexpr int kHaloTasks = kRows * kHaloCols * 4;  // (row, column, k-group): 144
-#ifndef GANCE_UPFIRS_WEAVE
-#define GANCE_UPFIRS_WEAVE 2  // other instructions dealt out per MFMA in a row's scheduling region (measured: 1 and 3 are within 1 % of 2)
-#endif
-#ifndef GANCE_UPFIRS_MIN_SEG_ROWS
-#define GANCE_UPFIRS_MIN_SEG_ROWS 16  // shortest row segment of a block (upfirs_plan)
-#endif
-#ifndef GANCE_UPFIRS_DEPTH
-#define GANCE_UPFIRS_DEPTH 6
-#endif
-constexpr int kDepth = GANCE_UPFIRS_DEPTH;  // patch rows in flight between their global loads and their LDS writes (3 or 6: 8 registers each)
+constexpr int kWeave = 2;           // other instructions dealt out per MFMA in a row's scheduling region
+constexpr int kMinSegRows = 16;     // shortest row segment of a block (upfirs_plan)
+constexpr int kDepth = 6;           // patch rows in flight between their global loads and their LDS writes (8 registers each)
 constexpr int kCarryRows = 3;
 constexpr int kPassCh = 4;          // channels of a channel tile per epilogue pass
 constexpr int kPassRows = 8;        // T rows per pass: four position rows
@@ -509,7 +501,7 @@ __device__ __forceinline__ void upfirs_body(const UpFirArgs& p) {
                     for (int i = 0; i < 54; ++i) {
                         if (i >= (j == 0 ? 18 : 54)) break;                 // (row 0 only has the dy = -1 taps)
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x092, GANCE_UPFIRS_WEAVE, 0);  // two of: vector ALU, vector memory, LDS
+                        __builtin_amdgcn_sched_group_barrier(0x092, kWeave, 0);  // two of: vector ALU, vector memory, LDS
                     }
                 } else {
                     // The chunk's last row, tap by tap (the dy = -1 taps first: the next chunk's first row needs them first): the row's
@@ -769,13 +761,12 @@ void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* a) {
     a->m_tiles = cout / kBM;
     a->strips = W / kSW;
     // Row segments only where whole images leave CUs idle: each costs a priming step of 8 rows, so segments of at least
-    // GANCE_UPFIRS_MIN_SEG_ROWS rows, powers of two, until every CU has a block (GANCE_TUNE_UPFIR_SPLIT_SEGS=0: never)
-    static const bool segments = [] { const char* v = std::getenv("GANCE_TUNE_UPFIR_SPLIT_SEGS"); return !(v && std::atoi(v) == 0); }();
+    // kMinSegRows rows, powers of two, until every CU has a block
     // ... the number that minimises (rounds of blocks over the CUs) x (rows a block sweeps, its priming step included)
     int segs = 1;
     const int base = B * a->m_tiles * a->strips;
     long long best = (long long)((base + num_cus - 1) / num_cus) * H;
-    for (int n = 2; segments && H / n >= GANCE_UPFIRS_MIN_SEG_ROWS && (H / n) % kTH == 0 && base * (n / 2) < num_cus; n *= 2) {
+    for (int n = 2; H / n >= kMinSegRows && (H / n) % kTH == 0 && base * (n / 2) < num_cus; n *= 2) {
         const long long cost = (long long)((base * n + num_cus - 1) / num_cus) * (H / n + kTH);
         if (cost < best) best = cost, segs = n;
     }

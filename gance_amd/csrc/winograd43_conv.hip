@@ -45,9 +45,6 @@
 
 #include "kernels.h"
 
-#ifndef GANCE_W43_WINDOW
-#define GANCE_W43_WINDOW 0
-#endif
 #ifndef GANCE_W43_ABLATE
 #define GANCE_W43_ABLATE 0  // timing ablations (wrong results; Makefile w43ab%): 1 no DMA inside the stream, 2 no input transform,
                             // 4 no weight reads, 8 no window reads (nor transform), 16 no barrier per k-step
@@ -62,18 +59,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kKC = 4;                         // input channels per chunk = one k-step of the 16x16x4 MFMA
-// LDS banks of the window reads (experiment of round 5, OFF: GANCE_W43_ODD_SHIFT = 2 and GANCE_W43_WINDOW = 3, Makefile target
-// ../libgance_hip_w43banks.so). A lane group of an 8-byte read is 32 lanes = the sixteen tiles of TWO input-channel planes; bank =
-// (address / 4) mod 64. Tiles are 4 floats apart, planes and rows multiples of 4: every lane of both planes reads the same two residues
-// mod 4, two lanes per bank; the dword reads of columns 3 / 8 (32 banks) put four lanes on a bank. With the odd planes two floats to
-// the right (their DMA pieces from 8 bytes further left) and columns 3 / 8 read as halves of 8-byte pairs every window read is
-// conflict-free by that model. Measured: SQ_LDS_BANK_CONFLICT 5.0e8 -> 4.0e8 per launch (the rest is not in the window reads), run
-// time +2 ... 3 % (3.57 / 3.62 / 3.91 / 4.53 / 5.45 -> 3.68 / 3.73 / 4.01 / 4.63 / 5.47 ms per 64 frames; either half alone: +1 ... 2 %):
-// the LDS array is 31 % busy in this kernel; its conflicts are not what the waves wait for.
-#ifndef GANCE_W43_ODD_SHIFT
-#define GANCE_W43_ODD_SHIFT 0
-#endif
-constexpr int kOddShift = GANCE_W43_ODD_SHIFT;
 constexpr int kBM = 32;                        // output channels per block (2 channel tiles of 16)
 constexpr int kUnit = 16 * 36;                 // a (channel tile, ci) unit of weights: [co % 16][36]: a lane's 36 weights are nine aligned float4
 constexpr int kWPieces = 18;                   // 8 units = 4608 floats = 18 pieces of 256 floats
@@ -95,10 +80,7 @@ struct Geo43 {
     static constexpr int kSlot = kPieces * 256;                   // 39 / 40 KB
     static constexpr int kNoiseRowsPerPiece = 256 / kTW;          // noise rows one 1 KB piece covers: 4 / 8
 };
-#ifndef GANCE_W43_NBUF
-#define GANCE_W43_NBUF 3  // (Makefile target ../libgance_hip_w43nbuf<N>.so builds the ring-depth variants)
-#endif
-constexpr int kNBUF = GANCE_W43_NBUF;          // ring slots: chunk G + 2 is issued during k-step G (a fourth slot measured no faster)
+constexpr int kNBUF = 3;                       // ring slots: chunk G + 2 is issued during k-step G
 // constants of a tile, fetched by LDS-DMA with its first chunk (a global load in the epilogue costs its whole latency once
 // per tile, and the wait behind it would drain the ring): demod | bias | next layer's style (32 each, padded to 64) |
 // noise [16][64] | (RGB) A operands of the ToRGB product [2 channel tiles][4 steps][64 lanes]
@@ -249,12 +231,10 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
                 const int q4 = f % (kPW / 4);
                 const int row = (f / (kPW / 4)) % kPH;
                 const int c = f / (kPW / 4 * kPH);
-                // (odd planes sit TWO FLOATS to the right in LDS -- kOddShift: their 16-byte pieces come from 8 bytes further left; the two
-                // floats in front of a row's first piece are the row above's last ones: never read)
-                piece_voff[r] = ((c * Hp + row) * Wp + 4 * q4 - kOddShift * (c & 1)) * 4;
+                piece_voff[r] = ((c * Hp + row) * Wp + 4 * q4) * 4;
             }
         }
-        win_off = kWFloats + g * kPlane + 4 * (pg * kTR + n16 / kTC) * kPW + 4 * (n16 % kTC) + kOddShift * (g & 1);
+        win_off = kWFloats + g * kPlane + 4 * (pg * kTR + n16 / kTC) * kPW + 4 * (n16 % kTC);
         a_off = (cot * 4 + g) * kUnit + n16 * 36;
     };
     lane_setup();
@@ -357,26 +337,10 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
         f32x2 c45[6], c67[6], c38[6];
 #pragma unroll
         for (int y = 0; y < 6; ++y) {
-#if GANCE_W43_WINDOW == 1
-            // (variant: three aligned 16-byte reads per window row, columns 4 n .. 4 n + 11: bank-conflict free, twice the bytes)
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(P + y * kPW);
-            const f32x4 q1 = *reinterpret_cast<const f32x4*>(P + y * kPW + 4);
-            const f32x4 q2 = *reinterpret_cast<const f32x4*>(P + y * kPW + 8);
-            c45[y] = f32x2{q1[0], q1[1]};
-            c67[y] = f32x2{q1[2], q1[3]};
-            c38[y] = f32x2{q0[3], q2[0]};
-#else
             c45[y] = *reinterpret_cast<const f32x2*>(P + y * kPW + 4);
             c67[y] = *reinterpret_cast<const f32x2*>(P + y * kPW + 6);
-#if GANCE_W43_WINDOW == 3
-            // (experiment: columns 3 and 8 as the halves of two 8-byte reads -- see kOddShift)
-            c38[y][0] = (*reinterpret_cast<const f32x2*>(P + y * kPW + 2))[1];
-            c38[y][1] = (*reinterpret_cast<const f32x2*>(P + y * kPW + 8))[0];
-#else
             c38[y][0] = P[y * kPW + 3];
             c38[y][1] = P[y * kPW + 8];
-#endif
-#endif
         }
 #if GANCE_W43_ABLATE & 4
 #pragma unroll
@@ -742,7 +706,7 @@ hipError_t launch_winograd43_conv(const ConvArgs& args, hipStream_t stream) {
     const int tw = narrow ? 32 : 64, th = 1024 / tw;
     const size_t lds_bytes = sizeof(float) * ((size_t)kNBUF * (narrow ? Geo43<32>::kSlot : Geo43<64>::kSlot) + 2 * kConstFloats + (rgb ? 2 * kRgbXchgFloats : 0));
     // (154.5 KB / 157.5 KB with both ToRGB buffers, + 16 bytes of tickets, of the CU's 160 KB)
-    static_assert(sizeof(float) * (kNBUF * std::max(Geo43<32>::kSlot, Geo43<64>::kSlot) + 2 * kConstFloats + 2 * kRgbXchgFloats) + 64 <= 160 * 1024 || kNBUF != 3,
+    static_assert(sizeof(float) * (kNBUF * std::max(Geo43<32>::kSlot, Geo43<64>::kSlot) + 2 * kConstFloats + 2 * kRgbXchgFloats) + 64 <= 160 * 1024,
                   "ring + tile constants + ToRGB buffers must fit the LDS of a CU");
     static PerDeviceInt resident[4];  // per device: the dynamic-LDS opt-in and the launch size = one block per CU, a multiple of 8 (XCDs)
     int resident_blocks = 0;

@@ -39,17 +39,11 @@ constexpr int kWBM = 32;             // output channels per block
 // 16 x 32 (8 x 16 tiles, wave = two tile rows); both have a 720-float patch per channel (10x72 / 18x40)
 constexpr int kWTH = 8, kWTW = 64;
 constexpr int kWTHn = 16, kWTWn = 32;
-#ifndef GANCE_WINO_KC
-#define GANCE_WINO_KC 8
-#endif
-#ifndef GANCE_WINO_NBUF
-#define GANCE_WINO_NBUF 3
-#endif
-constexpr int kWKC = GANCE_WINO_KC;  // input channels per chunk
+constexpr int kWKC = 8;  // input channels per chunk
 constexpr int kWPH = kWTH + 2, kWPW = kWTW + 8;
 constexpr int kWPHn = kWTHn + 2, kWPWn = kWTWn + 8;
 static_assert(kWPH * kWPW == kWPHn * kWPWn, "both geometries share the ring-slot layout");
-constexpr int kWNBUF = GANCE_WINO_NBUF;  // ring depth: NBUF-1 chunks in flight ahead of the one being multiplied
+constexpr int kWNBUF = 3;  // ring depth: NBUF-1 chunks in flight ahead of the one being multiplied
 constexpr int kWWlFloats = 16 * kWKC * kWBM;              // 1 KiB DMA pieces
 constexpr int kWPlFloats = kWKC * kWPH * kWPW;            // 2880
 constexpr int kWPlF4 = kWPlFloats / 4;                    // 720
@@ -484,15 +478,12 @@ __global__ __launch_bounds__(256, 1) void winograd_conv_kernel(const ConvArgs p)
     };
     // weave: 16 x (1 MFMA, 4 VALU, 2 LDS reads [, 1 LDS-DMA issue])
     auto weave = [&](bool with_dma) {
-#ifndef GANCE_WINO_WEAVE
-#define GANCE_WINO_WEAVE 1
-#endif
 #pragma unroll
-        for (int q = 0; q < 16 / GANCE_WINO_WEAVE; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, GANCE_WINO_WEAVE, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 4 * GANCE_WINO_WEAVE, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * GANCE_WINO_WEAVE, 0);
-            if (with_dma) __builtin_amdgcn_sched_group_barrier(0x020, GANCE_WINO_WEAVE, 0);
+        for (int q = 0; q < 16; ++q) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            if (with_dma) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         }
     };
 
