@@ -292,6 +292,45 @@ SIGNATURES = {
             ctypes.c_void_p,
         ],
     ),
+    "gance_modconv3x3_workspace_bytes": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_modconv3x3_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "gance_modconv3x3_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "gance_noise_bias_lrelu_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_noise_bias_lrelu_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_torgb_skip_workspace_bytes": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_torgb_skip_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_torgb_skip_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
 }
 
 # entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
@@ -300,7 +339,9 @@ ADDED_WITHIN_ABI = {
     "gance_engine_describe_plan", "gance_jpeg_encode_rect_bounds", "gance_jpeg_encode_rect_u8", "gance_debug_place_panels_u8",
     "gance_debug_draw_panels_u8", "gance_debug_scatter3d_u8", "gance_debug_draw_scatter3d_u8", "gance_jpeg_parse_header",
     "gance_jpeg_decode_bounds", "gance_jpeg_decode_u8", "gance_debug_draw_text_u8", "gance_debug_font_columns",
-    "gance_engine_debug_read_skip_image", "gance_png_encode_bounds", "gance_png_encode_u8",
+    "gance_engine_debug_read_skip_image", "gance_png_encode_bounds", "gance_png_encode_u8", "gance_modconv3x3_workspace_bytes",
+    "gance_modconv3x3_forward", "gance_modconv3x3_backward", "gance_noise_bias_lrelu_forward", "gance_noise_bias_lrelu_backward",
+    "gance_torgb_skip_workspace_bytes", "gance_torgb_skip_forward", "gance_torgb_skip_backward",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -917,6 +958,97 @@ def png_encode_device(  # pylint: disable=too-many-arguments
     _value_error_on_invalid_argument(
         lib,
         lib.gance_png_encode_u8(d_frames, batch, width, height, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None),
+    )
+
+
+# ---- differentiable synthesis (csrc/synthesis_grad.hip): raw device pointers, asynchronous on `stream` ----
+
+
+def modconv3x3_workspace_bytes(batch: int, cin: int, cout: int, side: int, up: bool) -> int:
+    """Workspace of one `modconv3x3_forward_device` / `modconv3x3_backward_device` call (`side` is the input's).
+    :raises ValueError: a shape the kernels refuse (include/gance_hip.h)."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_modconv3x3_workspace_bytes(batch, cin, cout, side, int(up), ctypes.byref(size)))
+    return int(size.value)
+
+
+def modconv3x3_forward_device(  # pylint: disable=too-many-arguments
+    d_x: int, d_style: int, d_demod: int, d_weight: int, batch: int, cin: int, cout: int, height: int, width: int, up: bool, d_y: int,
+    d_workspace: int, workspace_bytes: int, stream: int = 0,
+) -> None:
+    """y = demod * conv3x3(style * x, weight), with `up` the transposed conv + FIR to twice the side (gance_modconv3x3_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_modconv3x3_forward(d_x, d_style, d_demod, d_weight, batch, cin, cout, height, width, int(up), d_y, d_workspace, workspace_bytes,
+                                     stream or None),
+    )
+
+
+def modconv3x3_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_y: int, d_x: int, d_y: int, d_style: int, d_demod: int, d_weight: int, batch: int, cin: int, cout: int, height: int, width: int,
+    up: bool, d_grad_x: int, d_grad_style: int, d_grad_demod: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+) -> None:
+    """grad_x, grad_style and grad_demod of `modconv3x3_forward_device` (gance_modconv3x3_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_modconv3x3_backward(d_grad_y, d_x, d_y, d_style, d_demod, d_weight, batch, cin, cout, height, width, int(up), d_grad_x,
+                                      d_grad_style, d_grad_demod, d_workspace, workspace_bytes, stream or None),
+    )
+
+
+def noise_bias_lrelu_forward_device(  # pylint: disable=too-many-arguments
+    d_x: int, d_noise: int, noise_batch: int, d_strength: int, d_bias: int, batch: int, channels: int, height: int, width: int, d_out: int,
+    stream: int = 0,
+) -> None:
+    """out = lrelu_0.2(x + noise * strength + bias) * sqrt(2) (gance_noise_bias_lrelu_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_noise_bias_lrelu_forward(d_x, d_noise, noise_batch, d_strength, d_bias, batch, channels, height, width, d_out, stream or None),
+    )
+
+
+def noise_bias_lrelu_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_out: int, d_out: int, batch: int, channels: int, height: int, width: int, d_grad_x: int, stream: int = 0
+) -> None:
+    """grad_x of `noise_bias_lrelu_forward_device` from the saved output (gance_noise_bias_lrelu_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_noise_bias_lrelu_backward(d_grad_out, d_out, batch, channels, height, width, d_grad_x, None, None, None, stream or None)
+    )
+
+
+def torgb_skip_workspace_bytes(batch: int, cin: int, side: int) -> int:
+    """Workspace of one `torgb_skip_backward_device` call."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_torgb_skip_workspace_bytes(batch, cin, side, ctypes.byref(size)))
+    return int(size.value)
+
+
+def torgb_skip_forward_device(  # pylint: disable=too-many-arguments
+    d_x: int, d_style: int, d_weight: int, d_bias: int, d_y_prev: int, batch: int, cin: int, height: int, width: int, d_y: int, stream: int = 0
+) -> None:
+    """y = upsample_2d(y_prev) + ToRGB(x) + bias; `d_y_prev` 0: no skip image (gance_torgb_skip_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_torgb_skip_forward(d_x, d_style, d_weight, d_bias, d_y_prev or None, batch, cin, height, width, d_y, stream or None)
+    )
+
+
+def torgb_skip_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_y: int, d_x: int, d_style: int, d_weight: int, batch: int, cin: int, height: int, width: int, d_grad_x: int, d_grad_style: int,
+    d_grad_y_prev: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+) -> None:
+    """grad_x, grad_style and (unless `d_grad_y_prev` is 0) grad_y_prev of `torgb_skip_forward_device` (gance_torgb_skip_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_torgb_skip_backward(d_grad_y, d_x, d_style, d_weight, batch, cin, height, width, d_grad_x, d_grad_style, d_grad_y_prev or None,
+                                      d_workspace, workspace_bytes, stream or None),
     )
 
 

@@ -34,6 +34,9 @@ from gance_amd.gance_types import RGBInt8ImageType
 from gance_amd.logger_common import LOGGER
 from gance_amd.vector_sources.vector_types import SingleMatrix, SingleVector, is_vector
 
+if typing.TYPE_CHECKING:
+    from gance_amd.stylegan2.differentiable import DifferentiableSynthesis
+
 NETWORK_SUFFIX = ".pkl"  # network_functions.py:38
 TRUNCATION_PSI = 1.2  # network_functions.py:124,155
 # frames per engine call of the batched entry points: the batch the kernels are tuned for (64: 1350 frames/s class at 1024^2; 16: -12 %),
@@ -170,6 +173,16 @@ class LoadedNetwork:
             create_image_matrix=self.create_image_matrix,
             create_image_generic=self.create_image_generic,
         )
+
+    def differentiable(self) -> "DifferentiableSynthesis":
+        """
+        The same network as a differentiable function of the dlatents (gance_amd/stylegan2/differentiable.py), on the engine's
+        device: a second copy of the synthesis weights, built from the network file's variables; the engine is not touched.
+        """
+        from gance_amd.stylegan2.differentiable import DifferentiableSynthesis  # pylint: disable=import-outside-toplevel
+
+        loaded = network_file.load_network(self.network_path)
+        return DifferentiableSynthesis(loaded.variables, loaded.resolution, fmap_base=loaded.fmap_base, device=self.engine.device)
 
     def stop(self) -> None:
         """Free the network's HBM. Safe to call twice."""

@@ -11,6 +11,10 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
     torch.ops.gance.png_encode(frames)                     [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
     torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
+    torch.ops.gance.modconv3x3(x, style, demod, weight, up)        [B, Cin, S, S] f32 -> [B, Cout, S or 2S, ...] f32   differentiable
+    torch.ops.gance.noise_bias_lrelu(x, noise, strength, bias)     [B, C, S, S] f32 -> the same                          differentiable
+    torch.ops.gance.torgb_skip(x, style, weight, bias, y_prev)     [B, Cin, S, S] f32 -> [B, 3, S, S] f32                differentiable
+    (each with a `_backward` op; gradients reach x, style, demod and y_prev: gance_amd/stylegan2/differentiable.py is the user)
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
 without synchronising, so the ops compose with torch code and with `torch.distributed` collectives in stream
@@ -24,7 +28,7 @@ ctypes binding (gance_amd/hip_lib.py). There is no CPU implementation: on a CPU 
 
 import ctypes
 import weakref
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -387,3 +391,218 @@ def _(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     context = torch.library.get_ctx()
     height, width = context.new_dynamic_size(), context.new_dynamic_size()
     return data.new_empty((offsets.shape[0] - 1, height, width, 3))
+
+
+# ---- differentiable synthesis (csrc/synthesis_grad.hip): forward and backward ops of the generator's three layer operations ----
+
+
+def _f32_cuda(tensor: torch.Tensor, shape: Tuple[int, ...], name: str) -> torch.Tensor:
+    _require_cuda(tensor, torch.float32, name)
+    if tuple(tensor.shape) != tuple(shape):
+        raise ValueError(f"`{name}` must be {list(shape)}, got {list(tensor.shape)}")
+    return tensor.contiguous()
+
+
+def _activation_shape(x: torch.Tensor) -> Tuple[int, int, int, int]:
+    if x.dim() != 4:
+        raise ValueError(f"`x` must be [B, C, S, S], got {list(x.shape)}")
+    return int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3])
+
+
+def _modconv_weight_shape(weight: torch.Tensor) -> Tuple[int, int]:
+    if weight.dim() != 4 or weight.shape[0] != 3 or weight.shape[1] != 3:
+        raise ValueError(f"`weight` must be [3, 3, Cin, Cout], got {list(weight.shape)}")
+    return int(weight.shape[2]), int(weight.shape[3])
+
+
+@torch.library.custom_op("gance::modconv3x3", mutates_args=(), device_types="cuda")
+def modconv3x3(x: torch.Tensor, style: torch.Tensor, demod: torch.Tensor, weight: torch.Tensor, up: bool) -> torch.Tensor:
+    """
+    The modulated 3x3 conv of the published generator with its style [B, Cin] and demodulation [B, Cout] as inputs:
+    demod * conv(style * x, weight), weight [3, 3, Cin, Cout] runtime-scaled; `up`: the stride-2 transposed conv + FIR.
+    """
+    batch, cin, height, width = _activation_shape(x)
+    cout = _modconv_weight_shape(weight)[1]
+    x = _f32_cuda(x, (batch, cin, height, width), "x")
+    style, demod = _f32_cuda(style, (batch, cin), "style"), _f32_cuda(demod, (batch, cout), "demod")
+    weight = _f32_cuda(weight, (3, 3, cin, cout), "weight")
+    workspace_bytes = hip_lib.modconv3x3_workspace_bytes(batch, cin, cout, height, up)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=x.device)
+    factor = 2 if up else 1
+    y = torch.empty((batch, cout, height * factor, width * factor), dtype=torch.float32, device=x.device)
+    hip_lib.modconv3x3_forward_device(
+        x.data_ptr(), style.data_ptr(), demod.data_ptr(), weight.data_ptr(), batch, cin, cout, height, width, up, y.data_ptr(),
+        workspace.data_ptr(), workspace_bytes, _stream(x),
+    )
+    return y
+
+
+@modconv3x3.register_fake
+def _(x: torch.Tensor, style: torch.Tensor, demod: torch.Tensor, weight: torch.Tensor, up: bool) -> torch.Tensor:
+    factor = 2 if up else 1
+    return x.new_empty((x.shape[0], weight.shape[3], x.shape[2] * factor, x.shape[3] * factor))
+
+
+@torch.library.custom_op("gance::modconv3x3_backward", mutates_args=(), device_types="cuda")
+def modconv3x3_backward(  # pylint: disable=too-many-arguments
+    grad_y: torch.Tensor, x: torch.Tensor, y: torch.Tensor, style: torch.Tensor, demod: torch.Tensor, weight: torch.Tensor, up: bool
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_x, grad_style, grad_demod) of `modconv3x3` from its inputs and its output `y`; no weight gradient."""
+    batch, cin, height, width = _activation_shape(x)
+    cout = _modconv_weight_shape(weight)[1]
+    factor = 2 if up else 1
+    x = _f32_cuda(x, (batch, cin, height, width), "x")
+    y = _f32_cuda(y, (batch, cout, height * factor, width * factor), "y")
+    grad_y = _f32_cuda(grad_y, tuple(y.shape), "grad_y")
+    style, demod = _f32_cuda(style, (batch, cin), "style"), _f32_cuda(demod, (batch, cout), "demod")
+    weight = _f32_cuda(weight, (3, 3, cin, cout), "weight")
+    workspace_bytes = hip_lib.modconv3x3_workspace_bytes(batch, cin, cout, height, up)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=x.device)
+    grad_x, grad_style, grad_demod = torch.empty_like(x), torch.empty_like(style), torch.empty_like(demod)
+    hip_lib.modconv3x3_backward_device(
+        grad_y.data_ptr(), x.data_ptr(), y.data_ptr(), style.data_ptr(), demod.data_ptr(), weight.data_ptr(), batch, cin, cout, height, width,
+        up, grad_x.data_ptr(), grad_style.data_ptr(), grad_demod.data_ptr(), workspace.data_ptr(), workspace_bytes, _stream(x),
+    )
+    return grad_x, grad_style, grad_demod
+
+
+@modconv3x3_backward.register_fake
+def _(  # pylint: disable=too-many-arguments
+    grad_y: torch.Tensor, x: torch.Tensor, y: torch.Tensor, style: torch.Tensor, demod: torch.Tensor, weight: torch.Tensor, up: bool
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return x.new_empty(x.shape), style.new_empty(style.shape), demod.new_empty(demod.shape)
+
+
+def _modconv3x3_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    x, style, demod, weight, up = inputs
+    ctx.save_for_backward(x, output, style, demod, weight)
+    ctx.up = up
+
+
+def _modconv3x3_grad(ctx, grad_y: torch.Tensor):  # type: ignore[no-untyped-def]
+    x, y, style, demod, weight = ctx.saved_tensors
+    grad_x, grad_style, grad_demod = modconv3x3_backward(grad_y, x, y, style, demod, weight, ctx.up)
+    return grad_x, grad_style, grad_demod, None, None
+
+
+torch.library.register_autograd("gance::modconv3x3", _modconv3x3_grad, setup_context=_modconv3x3_setup)
+
+
+@torch.library.custom_op("gance::noise_bias_lrelu", mutates_args=(), device_types="cuda")
+def noise_bias_lrelu(x: torch.Tensor, noise: torch.Tensor, strength: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """lrelu_0.2(x + noise * strength + bias[c]) * sqrt(2): noise [1 or B, 1, S, S], strength one value, bias [C]."""
+    batch, channels, height, width = _activation_shape(x)
+    x = _f32_cuda(x, (batch, channels, height, width), "x")
+    if noise.dim() != 4 or noise.shape[0] not in (1, batch):
+        raise ValueError(f"`noise` must be [1 or {batch}, 1, {height}, {width}], got {list(noise.shape)}")
+    noise = _f32_cuda(noise, (int(noise.shape[0]), 1, height, width), "noise")
+    if strength.numel() != 1:
+        raise ValueError(f"`strength` must hold one value, got {list(strength.shape)}")
+    strength = _f32_cuda(strength, tuple(strength.shape), "strength")
+    bias = _f32_cuda(bias, (channels,), "bias")
+    out = torch.empty_like(x)
+    hip_lib.noise_bias_lrelu_forward_device(
+        x.data_ptr(), noise.data_ptr(), int(noise.shape[0]), strength.data_ptr(), bias.data_ptr(), batch, channels, height, width,
+        out.data_ptr(), _stream(x),
+    )
+    return out
+
+
+@noise_bias_lrelu.register_fake
+def _(x: torch.Tensor, noise: torch.Tensor, strength: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op("gance::noise_bias_lrelu_backward", mutates_args=(), device_types="cuda")
+def noise_bias_lrelu_backward(grad_out: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """grad_x of `noise_bias_lrelu`: the slope of every position is read off the sign of the saved output."""
+    batch, channels, height, width = _activation_shape(out)
+    out = _f32_cuda(out, (batch, channels, height, width), "out")
+    grad_out = _f32_cuda(grad_out, tuple(out.shape), "grad_out")
+    grad_x = torch.empty_like(out)
+    hip_lib.noise_bias_lrelu_backward_device(grad_out.data_ptr(), out.data_ptr(), batch, channels, height, width, grad_x.data_ptr(), _stream(out))
+    return grad_x
+
+
+@noise_bias_lrelu_backward.register_fake
+def _(grad_out: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    return out.new_empty(out.shape)
+
+
+def _noise_bias_lrelu_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(output)
+
+
+def _noise_bias_lrelu_grad(ctx, grad_out: torch.Tensor):  # type: ignore[no-untyped-def]
+    (out,) = ctx.saved_tensors
+    return noise_bias_lrelu_backward(grad_out, out), None, None, None  # (noise, strength and bias have no gradient yet)
+
+
+torch.library.register_autograd("gance::noise_bias_lrelu", _noise_bias_lrelu_grad, setup_context=_noise_bias_lrelu_setup)
+
+
+@torch.library.custom_op("gance::torgb_skip", mutates_args=(), device_types="cuda")
+def torgb_skip(x: torch.Tensor, style: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, y_prev: Optional[torch.Tensor]) -> torch.Tensor:
+    """
+    The image step of the skip generator: upsample_2d(y_prev) + sum_i weight[i, c] * style[b, i] * x[b, i] + bias[c], no
+    demodulation; weight [Cin, 3] runtime-scaled, y_prev [B, 3, S / 2, S / 2] or None (the 4x4 layer).
+    """
+    batch, cin, height, width = _activation_shape(x)
+    x = _f32_cuda(x, (batch, cin, height, width), "x")
+    style, weight, bias = _f32_cuda(style, (batch, cin), "style"), _f32_cuda(weight, (cin, 3), "weight"), _f32_cuda(bias, (3,), "bias")
+    if y_prev is not None:
+        y_prev = _f32_cuda(y_prev, (batch, 3, height // 2, width // 2), "y_prev")
+    y = torch.empty((batch, 3, height, width), dtype=torch.float32, device=x.device)
+    hip_lib.torgb_skip_forward_device(
+        x.data_ptr(), style.data_ptr(), weight.data_ptr(), bias.data_ptr(), 0 if y_prev is None else y_prev.data_ptr(), batch, cin, height,
+        width, y.data_ptr(), _stream(x),
+    )
+    return y
+
+
+@torgb_skip.register_fake
+def _(x: torch.Tensor, style: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, y_prev: Optional[torch.Tensor]) -> torch.Tensor:
+    return x.new_empty((x.shape[0], 3, x.shape[2], x.shape[3]))
+
+
+@torch.library.custom_op("gance::torgb_skip_backward", mutates_args=(), device_types="cuda")
+def torgb_skip_backward(
+    grad_y: torch.Tensor, x: torch.Tensor, style: torch.Tensor, weight: torch.Tensor, has_y_prev: bool
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_x, grad_style, grad_y_prev) of `torgb_skip`; grad_y_prev is empty ([0]) without a skip image."""
+    batch, cin, height, width = _activation_shape(x)
+    x = _f32_cuda(x, (batch, cin, height, width), "x")
+    grad_y = _f32_cuda(grad_y, (batch, 3, height, width), "grad_y")
+    style, weight = _f32_cuda(style, (batch, cin), "style"), _f32_cuda(weight, (cin, 3), "weight")
+    workspace_bytes = hip_lib.torgb_skip_workspace_bytes(batch, cin, height)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=x.device)
+    grad_x, grad_style = torch.empty_like(x), torch.empty_like(style)
+    grad_y_prev = torch.empty((batch, 3, height // 2, width // 2) if has_y_prev else (0,), dtype=torch.float32, device=x.device)
+    hip_lib.torgb_skip_backward_device(
+        grad_y.data_ptr(), x.data_ptr(), style.data_ptr(), weight.data_ptr(), batch, cin, height, width, grad_x.data_ptr(),
+        grad_style.data_ptr(), grad_y_prev.data_ptr() if has_y_prev else 0, workspace.data_ptr(), workspace_bytes, _stream(x),
+    )
+    return grad_x, grad_style, grad_y_prev
+
+
+@torgb_skip_backward.register_fake
+def _(
+    grad_y: torch.Tensor, x: torch.Tensor, style: torch.Tensor, weight: torch.Tensor, has_y_prev: bool
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    prev_shape = (x.shape[0], 3, x.shape[2] // 2, x.shape[3] // 2) if has_y_prev else (0,)
+    return x.new_empty(x.shape), style.new_empty(style.shape), x.new_empty(prev_shape)
+
+
+def _torgb_skip_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    x, style, weight, _, y_prev = inputs
+    ctx.save_for_backward(x, style, weight)
+    ctx.has_y_prev = y_prev is not None
+
+
+def _torgb_skip_grad(ctx, grad_y: torch.Tensor):  # type: ignore[no-untyped-def]
+    x, style, weight = ctx.saved_tensors
+    grad_x, grad_style, grad_y_prev = torgb_skip_backward(grad_y, x, style, weight, ctx.has_y_prev)
+    return grad_x, grad_style, None, None, grad_y_prev if ctx.has_y_prev else None
+
+
+torch.library.register_autograd("gance::torgb_skip", _torgb_skip_grad, setup_context=_torgb_skip_setup)

@@ -554,6 +554,57 @@ int gance_debug_draw_text_u8(const uint8_t* d_text, int32_t text_stride, int32_t
 /* the font's table: 95 glyphs x 5 column bytes, bit 0 = top row (host only, no GPU needed); count must be 475 */
 int gance_debug_font_columns(uint8_t* h_out, uint64_t count);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Differentiable synthesis: forward and backward of the generator's three layer operations   */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * The plain-form path behind torch.ops.gance.modconv3x3 / noise_bias_lrelu / torgb_skip and
+ * gance_amd/stylegan2/differentiable.py: the image's gradient with respect to the dlatents,
+ * which the engine's forward-only kernel forms cannot give. Every tensor is float32, C-contiguous, NCHW, on the device;
+ * every call is asynchronous on `stream` without host synchronisation, uses no floating-point atomics and sums in one
+ * fixed order: the bits are a pure function of the arguments. Refused with GANCE_ERR_INVALID_ARGUMENT before a device is
+ * touched: a NULL pointer (except where noted), a pointer that is not 4-byte aligned, a channel count that is not a multiple
+ * of 16 in [16, 512], height != width, a side outside [4, 1024] (an up layer's input side outside [4, 512]), a batch
+ * outside [1, 65535] or so large that batch * channels * (2 side + 1)^2 passes 2^31 - 1, a workspace below the bound.
+ *
+ * Modulated 3x3 conv (modulated_conv2d_layer of the published network with the style and the demodulation as inputs):
+ *   y[b,o] = demod[b,o] * sum_{i,tap} weight[tap,i,o] * style[b,i] * x[b,i]     zero padding 1; weight [3][3][cin][cout] runtime-scaled
+ * with up != 0 the stride-2 transposed conv and the [1,3,3,1] FIR of upsample_conv_2d: x [batch][cin][side][side] ->
+ * y [batch][cout][2 side][2 side]. The backward gives grad_x (shape of x), grad_style [batch][cin] and grad_demod
+ * [batch][cout] (demod > 0); there is no weight gradient. d_y is the forward's output. Both contractions run on
+ * v_mfma_f32_16x16x4_f32. The workspace (16-byte multiples, any 4-byte aligned address) serves either direction.
+ */
+int gance_modconv3x3_workspace_bytes(int32_t batch, int32_t cin, int32_t cout, int32_t side, int32_t up, uint64_t* workspace_bytes);
+int gance_modconv3x3_forward(const float* d_x, const float* d_style, const float* d_demod, const float* d_weight, int32_t batch, int32_t cin,
+                             int32_t cout, int32_t height, int32_t width, int32_t up, float* d_y, void* d_workspace, uint64_t workspace_bytes,
+                             void* stream);
+int gance_modconv3x3_backward(const float* d_grad_y, const float* d_x, const float* d_y, const float* d_style, const float* d_demod,
+                              const float* d_weight, int32_t batch, int32_t cin, int32_t cout, int32_t height, int32_t width, int32_t up,
+                              float* d_grad_x, float* d_grad_style, float* d_grad_demod, void* d_workspace, uint64_t workspace_bytes,
+                              void* stream);
+/*
+ * out = lrelu_0.2(x + noise * strength + bias[c]) * sqrt(2): x, out [batch][channels][side][side], d_noise
+ * [noise_batch = 1 or batch][1][side][side], d_strength one float on the device, d_bias [channels]. The backward reads the
+ * slope off the sign of the saved output (leaky ReLU keeps the sign) and gives grad_x; d_grad_noise, d_grad_strength and
+ * d_grad_bias are reserved for gradients that are not implemented and must be NULL.
+ */
+int gance_noise_bias_lrelu_forward(const float* d_x, const float* d_noise, int32_t noise_batch, const float* d_strength, const float* d_bias,
+                                   int32_t batch, int32_t channels, int32_t height, int32_t width, float* d_out, void* stream);
+int gance_noise_bias_lrelu_backward(const float* d_grad_out, const float* d_out, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                                    float* d_grad_x, float* d_grad_noise, float* d_grad_strength, float* d_grad_bias, void* stream);
+/*
+ * ToRGB of the skip architecture: y = upsample_2d(y_prev) + sum_i weight[i,c] * style[b,i] * x[b,i] + bias[c], no
+ * demodulation: x [batch][cin][side][side], weight [cin][3], y [batch][3][side][side], d_y_prev [batch][3][side / 2][side / 2]
+ * or NULL (the 4x4 layer; with it the side must be even). The backward gives grad_x, grad_style [batch][cin] and, unless
+ * d_grad_y_prev is NULL, the transpose of the zero-insert + FIR upsample applied to grad_y.
+ */
+int gance_torgb_skip_workspace_bytes(int32_t batch, int32_t cin, int32_t side, uint64_t* workspace_bytes);
+int gance_torgb_skip_forward(const float* d_x, const float* d_style, const float* d_weight, const float* d_bias, const float* d_y_prev,
+                             int32_t batch, int32_t cin, int32_t height, int32_t width, float* d_y, void* stream);
+int gance_torgb_skip_backward(const float* d_grad_y, const float* d_x, const float* d_style, const float* d_weight, int32_t batch, int32_t cin,
+                              int32_t height, int32_t width, float* d_grad_x, float* d_grad_style, float* d_grad_y_prev, void* d_workspace,
+                              uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
