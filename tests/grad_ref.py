@@ -13,7 +13,7 @@ The yardstick of a gradient bar is the oracle itself in float32 on the CPU, judg
 """
 
 import functools
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -89,6 +89,29 @@ class Case(NamedTuple):
 # (resolution, fmap_base): 16^2 ... 64^2 config-f and 64^2 config-e, each on the stress network and the perturbed random init
 CASE_SHAPES = ((16, sg2_spec.FMAP_BASE), (32, sg2_spec.FMAP_BASE), (64, sg2_spec.FMAP_BASE), (64, sg2_spec.FMAP_BASE_CONFIG_E))
 CASE_NAMES = tuple(f"{kind}-{resolution}-{'e' if base == sg2_spec.FMAP_BASE_CONFIG_E else 'f'}" for resolution, base in CASE_SHAPES for kind in ("stress", "perturb"))
+# Beyond 64^2, config-e only: every position sum of a real layer sequence in 4 (128^2) and 16 (256^2) segments. Apart from
+# CASE_NAMES, so that nothing parametrized over that changes. perturb-256-e is left out: the float32 oracle alone flips 11 of its
+# cap of 23 signs there.
+LARGE_CASE_NAMES = ("perturb-128-e", "stress-128-e", "stress-256-e")
+# MAX_SIGN_FLIPS was set for at most this many activations per sample (64^2 config-f): 512 * (16 + 2 * 64 + 2 * 256 + 2 * 1024 + 2 * 4096)
+SIGN_FLIP_ACTIVATIONS = 5_578_752
+
+
+def activations_per_sample(resolution: int, fmap_base: int) -> int:
+    return sum(conv.cout * (1 << conv.res_log2) ** 2 for conv in sg2_spec.make_spec(resolution, fmap_base).convs)
+
+
+def sign_flip_cap(name: str) -> int:
+    """
+    MAX_SIGN_FLIPS for the cases it was set for; for the larger ones the same density of flips per activation (the number of
+    pre-activations within rounding distance of zero grows with the activation count), rounded down: 11 at 128^2 config-e
+    (7 675 904 activations), 23 at 256^2 config-e (16 064 512).
+    """
+    if name in CASE_NAMES:
+        return MAX_SIGN_FLIPS
+    _, resolution_text, config = name.split("-")
+    count = activations_per_sample(int(resolution_text), sg2_spec.FMAP_BASE_CONFIG_E if config == "e" else sg2_spec.FMAP_BASE)
+    return max(MAX_SIGN_FLIPS, MAX_SIGN_FLIPS * count // SIGN_FLIP_ACTIVATIONS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,11 +143,12 @@ def gradient64(this: Case, signs: Sequence[torch.Tensor]) -> torch.Tensor:
     return gradient
 
 
-def check_signs(this: Case, activations: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+def check_signs(this: Case, activations: Sequence[torch.Tensor], who: str = "the run") -> List[torch.Tensor]:
     """
-    The slope masks of a run (activation > 0 per conv layer) after the conditions on them: at most MAX_SIGN_FLIPS activations
-    differ in sign from the float64 oracle's, each smaller than SIGN_FLIP_MAGNITUDE of its layer's largest activation, in the
-    run and in the oracle. A real sign or mask mistake flips ordinary-sized values and fails this.
+    The slope masks of a run (activation > 0 per conv layer) after the conditions on them: at most sign_flip_cap (MAX_SIGN_FLIPS
+    for every case up to 64^2) activations differ in sign from the float64 oracle's, each smaller than SIGN_FLIP_MAGNITUDE of
+    its layer's largest activation, in the run and in the oracle. A real sign or mask mistake flips ordinary-sized values and
+    fails this.
     """
     signs, flips = [], 0
     assert len(activations) == len(this.activations64)
@@ -139,7 +163,9 @@ def check_signs(this: Case, activations: Sequence[torch.Tensor]) -> List[torch.T
             assert largest < limit, f"{this.name} layer {index}: an activation of magnitude {largest:.3e} (limit {limit:.3e}) changed sign"
         flips += count
         signs.append(sign)
-    assert flips <= MAX_SIGN_FLIPS, f"{this.name}: {flips} activations differ in sign from the float64 oracle"
+    cap = sign_flip_cap(this.name)
+    print(f"{this.name}: {flips} activations of {who} differ in sign from the float64 oracle (at most {cap})")
+    assert flips <= cap, f"{this.name}: {flips} activations differ in sign from the float64 oracle (at most {cap})"
     return signs
 
 
@@ -154,7 +180,7 @@ def yardstick(name: str) -> float:
     activations: List[torch.Tensor] = []
     image = g_synthesis_with_signs(dlatents, this.variables, this.resolution, this.fmap_base, collect=activations)
     (gradient,) = torch.autograd.grad(image, dlatents, torch.from_numpy(this.cotangent))
-    return row_error(gradient, gradient64(this, check_signs(this, activations)))
+    return row_error(gradient, gradient64(this, check_signs(this, activations, "the float32 oracle")))
 
 
 # ---- the three operations in isolation: float64 (or float32) autograd of the oracle's layer functions with style and demod as leaves ----
@@ -219,8 +245,9 @@ def torgb_inputs(batch: int, cin: int, side: int, with_prev: bool, seed: int) ->
 def torgb_oracle(inputs: Dict[str, np.ndarray], dtype: torch.dtype) -> Tuple[torch.Tensor, ...]:
     """(y, grad_x, grad_style[, grad_y_prev]) of ref.torgb_layer in `dtype`, the style a leaf as in modconv_oracle."""
     batch, cin, side = inputs["x"].shape[:3]
+    # res_log2 only names the scope and the dlatent row that ref.torgb_layer reads: any even side goes under its power of two below
     res_log2 = int(np.log2(side))
-    scope = f"G_synthesis/{side}x{side}/ToRGB"
+    scope = f"G_synthesis/{2 ** res_log2}x{2 ** res_log2}/ToRGB"
     variables = {
         f"{scope}/weight": inputs["weight"],
         f"{scope}/mod_weight": np.eye(cin) * np.sqrt(float(cin)),
@@ -239,3 +266,91 @@ def torgb_oracle(inputs: Dict[str, np.ndarray], dtype: torch.dtype) -> Tuple[tor
     y = ref.torgb_layer(x, y_prev, dlatents, variables, res_log2)
     grads = torch.autograd.grad(y, leaves, torch.from_numpy(inputs["grad_y"]).to(dtype))
     return (y.detach(), *grads)
+
+
+def lrelu_inputs(batch: int, channels: int, side: int, noise_batch: int, seed: int) -> Dict[str, np.ndarray]:
+    """Inputs whose pre-activation stays at least 1e-3 away from the kink (values nearer than 2e-3 are moved to +-2e-3 through x)."""
+    rng = np.random.RandomState(seed)
+    x = rng.randn(batch, channels, side, side).astype(np.float32)
+    noise = rng.randn(noise_batch, 1, side, side).astype(np.float32)
+    strength, bias = np.float32(0.37), rng.randn(channels).astype(np.float32)
+    rest = noise.astype(np.float64) * float(strength) + bias.astype(np.float64)[None, :, None, None]
+    pre = x.astype(np.float64) + rest
+    near = np.abs(pre) < 2e-3
+    x = np.where(near, np.where(pre >= 0, 2e-3, -2e-3) - rest, x).astype(np.float32)
+    assert np.abs(x.astype(np.float64) + rest).min() >= 1e-3
+    return {"x": x, "noise": noise, "strength": np.reshape(strength, (1,)), "bias": bias, "grad": rng.randn(batch, channels, side, side).astype(np.float32)}
+
+
+def lrelu_oracle(inputs: Dict[str, np.ndarray], dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+    x = torch.from_numpy(inputs["x"]).to(dtype).requires_grad_(True)
+    pre = x + torch.from_numpy(inputs["noise"]).to(dtype) * torch.from_numpy(inputs["strength"]).to(dtype)
+    out = ref.apply_bias_act(pre, torch.from_numpy(inputs["bias"]).to(dtype), "lrelu")
+    (grad,) = torch.autograd.grad(out, x, torch.from_numpy(inputs["grad"]).to(dtype))
+    return out.detach(), grad
+
+
+# ---- what the GPU test modules share ----
+
+
+def cuda(array: np.ndarray, requires_grad: bool = False) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(array, dtype=np.float32)).cuda().requires_grad_(requires_grad)
+
+
+def judge(label: str, names: Sequence[str], got: Sequence[torch.Tensor], want64: Sequence[torch.Tensor], want32: Sequence[torch.Tensor]) -> None:
+    """tensor 0 is the forward output (bar LAYER_BAR), the others gradients (bar 8 x the float32 oracle's own error)."""
+    failures = []
+    for index, name in enumerate(names):
+        error = relative_error(got[index], want64[index])
+        own = relative_error(want32[index], want64[index])
+        bar = LAYER_BAR if index == 0 else GRADIENT_BAR_FACTOR * own
+        print(f"{label} {name}: error {error:.3e}, float32 oracle {own:.3e}, ratio {error / own if own else float('inf'):.2f}, bar {bar:.3e}")
+        if not (np.isfinite(error) and error <= bar):
+            failures.append(f"{name}: {error:.3e} > {bar:.3e}")
+    assert not failures, f"{label}: " + "; ".join(failures)
+
+
+def run_chain(synthesis: Any, this: Case) -> Tuple[torch.Tensor, List[torch.Tensor], torch.Tensor]:
+    """(image, activations, dlatent gradient) of a DifferentiableSynthesis on a case's dlatents and cotangent."""
+    dlatents = cuda(this.dlatents, True)
+    activations: List[torch.Tensor] = []
+    image = synthesis(dlatents, collect=activations)
+    (gradient,) = torch.autograd.grad(image, dlatents, cuda(this.cotangent))
+    return image.detach(), [activation.detach() for activation in activations], gradient
+
+
+def check_whole_chain(name: str) -> None:
+    """
+    A whole-chain case on the GPU: the image against the float64 oracle and against the engine, every activation against
+    LAYER_BAR, the sign conditions, and the dlatent gradient's worst row against GRADIENT_BAR_FACTOR x `yardstick`.
+    """
+    from gance_amd import hip_lib  # pylint: disable=import-outside-toplevel
+    from gance_amd.stylegan2.differentiable import DifferentiableSynthesis  # pylint: disable=import-outside-toplevel
+
+    this = case(name)
+    synthesis = DifferentiableSynthesis(this.variables, this.resolution, fmap_base=this.fmap_base, device=0)
+    image, activations, gradient = run_chain(synthesis, this)
+    assert image.shape == (2, 3, this.resolution, this.resolution) and image.dtype == torch.float32
+    failures = []
+
+    def bar(what: str, error: float, limit: float) -> None:
+        print(f"{name} {what}: {error:.3e} (bar {limit:.3e})")
+        if not (np.isfinite(error) and error <= limit):
+            failures.append(f"{what}: {error:.3e} > {limit:.3e}")
+
+    bar("image against the float64 oracle", relative_error(image, this.image64), IMAGE_BAR)
+    engine = hip_lib.Engine(this.variables, this.resolution, max_batch=2, device=0)
+    try:
+        _, engine_image = engine.synthesize_w(this.dlatents, want_float=True)
+    finally:
+        engine.close()
+    bar("image against the engine", relative_error(image, torch.from_numpy(engine_image)), IMAGE_BAR)
+    assert len(activations) == len(this.activations64)
+    for index, (got, want) in enumerate(zip(activations, this.activations64)):
+        bar(f"activation {index}", relative_error(got, want), LAYER_BAR)
+    signs = check_signs(this, activations)
+    own = yardstick(name)
+    error = row_error(gradient, gradient64(this, signs))
+    print(f"{name} dlatent gradient: ratio to the float32 oracle {error / own:.2f}")
+    bar("dlatent gradient, worst row", error, GRADIENT_BAR_FACTOR * own)
+    assert not failures, f"{name}: " + "; ".join(failures)

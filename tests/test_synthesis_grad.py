@@ -198,3 +198,21 @@ def test_oracle_functions_take_the_style_as_a_leaf() -> None:
     want = torch.nn.functional.conv2d(x, weight, padding=1) * torch.from_numpy(inputs["demod"]).double()[:, :, None, None]
     assert grad_ref.relative_error(y, want) < 1e-6  # (the float32 rounding of the scaled weight)
     assert ref.upsample_2d(torch.ones(1, 1, 2, 2, dtype=torch.float64)).shape == (1, 1, 4, 4)
+
+
+def test_torgb_oracle_takes_any_even_side() -> None:
+    """Side 66 is no power of two: the scope the helper builds is the one ref.torgb_layer reads, and the result is the ToRGB step."""
+    inputs = grad_ref.torgb_inputs(2, 16, 66, True, seed=0)
+    y, grad_x, grad_style, grad_y_prev = grad_ref.torgb_oracle(inputs, torch.float64)
+    assert grad_x.shape == (2, 16, 66, 66) and grad_style.shape == (2, 16) and grad_y_prev.shape == (2, 3, 33, 33)
+    coefficients = torch.from_numpy(grad_ref.scaled_weight(inputs["weight"]).astype("float64")).reshape(16, 3)
+    rgb = torch.einsum("bi,ic,bihw->bchw", torch.from_numpy(inputs["style"]).double(), coefficients, torch.from_numpy(inputs["x"]).double())
+    want = ref.upsample_2d(torch.from_numpy(inputs["y_prev"]).double()) + rgb + torch.from_numpy(inputs["bias"]).double().reshape(1, 3, 1, 1)
+    assert grad_ref.relative_error(y, want) < 1e-6  # (the float32 rounding of the scaled weight)
+
+
+def test_sign_flip_cap_keeps_the_density_of_the_small_cases() -> None:
+    assert grad_ref.activations_per_sample(64, sg2_spec.FMAP_BASE) == grad_ref.SIGN_FLIP_ACTIVATIONS
+    assert all(grad_ref.sign_flip_cap(name) == grad_ref.MAX_SIGN_FLIPS == 8 for name in grad_ref.CASE_NAMES)
+    assert [grad_ref.sign_flip_cap(name) for name in grad_ref.LARGE_CASE_NAMES] == [11, 11, 23]
+    assert not set(grad_ref.LARGE_CASE_NAMES) & set(grad_ref.CASE_NAMES)
