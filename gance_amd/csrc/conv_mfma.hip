@@ -27,8 +27,8 @@
 // All LDS is one dynamic array; no ordinary global load sits inside the K loop. (A third buffer and
 // blocks that walk several tiles were built and measured slower: HISTORY.md.)
 //
-// The stride-1 layers at >= 32x32 normally run in Winograd form instead (winograd_conv.hip); this
-// kernel keeps the small layers, every transposed conv, and the last layer fused with its ToRGB.
+// The stride-1 layers at >= 32x32 normally run in Winograd form instead (winograd64_conv.hip,
+// winograd43_conv.hip); this kernel keeps the small layers, every transposed conv, and the last layer fused with its ToRGB.
 
 #include <hip/hip_runtime.h>
 

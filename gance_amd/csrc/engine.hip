@@ -301,6 +301,15 @@ struct ConvOut {
     long long b_stride, c_stride, slab_stride, cls_stride;
 };
 
+// the pool offset of the weight image a run_conv launch reads
+size_t conv_weights(const LayerCaps& caps, Form form) {
+    switch (form) {
+        case Form::Wino64: return caps.w[kWino64];
+        case Form::Wino43: return caps.w[kWino43];
+        default: return caps.direct_w;  // Direct, DirectSplitK, DirectTorgb, UpTwoPass
+    }
+}
+
 gance::ConvArgs conv_args(const gance_engine* e, int li, const LayerStep& step, const float* x, long long x_b_stride, int H, int W,
                           const ConvOut& o, int B, const FusedRgb* rgb, const float* s_next) {
     const ConvLayerHost& c = e->convs[li];
@@ -322,9 +331,7 @@ gance::ConvArgs conv_args(const gance_engine* e, int li, const LayerStep& step, 
     a.x = x;
     // (F(4x4,3x3) and the 16x16x4 kernel's 32-channel geometry take the input multiplied by this layer's style: plan_call arranged
     // that with the producing layer)
-    a.w = e->pool + (step.form == Form::Wino43 ? caps.w[kWino43]
-                                               : (step.form == Form::Wino64 ? caps.w[kWino64]
-                                                                            : ((step.form == Form::Wino || step.form == Form::WinoTorgb) ? caps.w[kWino] : caps.direct_w)));
+    a.w = e->pool + conv_weights(caps, step.form);
     a.s = e->ws->styles + e->conv_s_off[li];
     a.d = e->ws->demod + e->conv_d_off[li];
     a.noise = layer_noise(e, li, &a.noise_b_stride);
@@ -393,10 +400,6 @@ int run_conv(gance_engine* e, int li, const LayerStep& step, const float* x, lon
     }
     if (step.form == Form::Wino64) {
         GANCE_HIP_CHECK(gance::launch_winograd64_conv(a, stream));
-        return GANCE_OK;
-    }
-    if (step.form == Form::Wino || step.form == Form::WinoTorgb) {  // the round-1 32-channel kernel
-        GANCE_HIP_CHECK(gance::launch_winograd_conv(a, stream));
         return GANCE_OK;
     }
     GANCE_HIP_CHECK(gance::launch_modconv(p.tile_id, a, p.total_blocks, stream));
@@ -592,8 +595,7 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                 GANCE_HIP_CHECK(gance::launch_winogemm(g, stream));
                 break;
             }
-            case Form::DirectTorgb:
-            case Form::WinoTorgb: {
+            case Form::DirectTorgb: {
                 FusedRgb rgb{e->pool + e->rgb_w[ri], e->ws->styles + e->rgb_s_off[ri], e->pool + e->rgb_bias[ri],
                              e->ws->ybuf[ycur], (d_f32 != nullptr || e->keep_skip_image) ? e->ws->ybuf[1 - ycur] : nullptr, d_u8};
                 ConvOut o = activation;
@@ -605,7 +607,6 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                 break;
             }
             case Form::Direct:
-            case Form::Wino:
             case Form::Wino64:
             case Form::Wino43: {
                 if (!step.rgb_sum) {
@@ -909,8 +910,6 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
         void (*arrange)(const float* scaled, int cin, int cout, float* out);
     };
     static const WeightImageKind kinds[kNumWeightImages] = {
-        // U = G w G^T of the scaled weights, in the Winograd kernel's LDS image [m tile][chunk][16][4][32]
-        {gance::winograd_weight_floats, gance::winograd_transform_weights},
         {gance::winograd64_weight_floats, gance::winograd64_transform_weights},
         {gance::winograd43_weight_floats, gance::winograd43_transform_weights},
         {gance::upfir16_weight_floats, [](const float* w, int ci, int co, float* out) { gance::upfir16_arrange_weights(w, ci, co, kUpTapWeight, out); }},

@@ -63,11 +63,7 @@ struct Tuning {
     // product in its epilogue (measured: see DESIGN.md §3)
     int last_wino64 = 1;
     int winograd = -1;  // GANCE_TUNE_WINOGRAD = 0 / 1 / 2: overrides the engine flags' Winograd mode (never / where it fills the chip / always)
-    // GANCE_TUNE_WINOGRAD_RGB = 1: the 32-channel Winograd kernel's own fused-ToRGB variant on the last layer (built, parity-green,
-    // register-starved in its epilogue and measured no faster than the direct-form fused last layer)
-    bool winograd_rgb = false;
-    bool wino64 = true;  // GANCE_TUNE_WINO64 = 0 keeps the round-1 32-channel Winograd kernel instead of the one on 16x16x4 MFMAs
-    int upfir = -1;      // GANCE_TUNE_UPFIR = 0 / 1 / 2: overrides the engine flags' fused-up mode (never / auto / always)
+    int upfir = -1;  // GANCE_TUNE_UPFIR = 0 / 1 / 2: overrides the engine flags' fused-up mode (never / auto / always)
     // GANCE_TUNE_PRESCALE_UP = 0: a Winograd launch never scales its stores by the next (fused up) layer's style; that kernel then
     // scales in its own K loop
     bool prescale_up = true;
@@ -102,8 +98,6 @@ Tuning read_tuning() {
     t.fuse_rgb = number("GANCE_TUNE_FUSE_RGB", 1) != 0;
     t.last_wino64 = number("GANCE_TUNE_LAST_WINO64", 1);
     t.winograd = number("GANCE_TUNE_WINOGRAD", -1);
-    t.winograd_rgb = number("GANCE_TUNE_WINOGRAD_RGB", 0) != 0;
-    t.wino64 = number("GANCE_TUNE_WINO64", 1) != 0;
     t.upfir = number("GANCE_TUNE_UPFIR", -1);
     t.prescale_up = number("GANCE_TUNE_PRESCALE_UP", 1) != 0;
     t.w64_rgb = number("GANCE_TUNE_W64_RGB", 1) != 0;
@@ -200,8 +194,7 @@ int wino43_max_res(int flags, const Tuning& tune) {
 // ---- what an engine may run a layer in: decided once, at creation, from (layer spec, engine flags, tuning) ----
 // The forms beyond the direct one (conv_mfma.hip, which every layer has); each reads a weight image of its own. In the pool's order.
 enum WeightImage {
-    kWino,        // Winograd F(2x2,3x3), the round-1 32-channel kernel (winograd_conv.hip)
-    kWino64,      // the same on 16x16x4 MFMAs (winograd64_conv.hip: layers with >= 64 output channels, and the 32-channel last layer)
+    kWino64,      // Winograd F(2x2,3x3) on 16x16x4 MFMAs (winograd64_conv.hip: layers with >= 64 output channels, and the 32-channel last layer)
     kWino43,      // Winograd F(4x4,3x3) (winograd43_conv.hip)
     kUpfir16,     // fused transposed conv + FIR on the fp32 matrix cores, 16 channels per block, two blocks per CU (upfir16_fused.hip)
     kWinoGemm,    // Winograd F(4x4,3x3) as 36 dense GEMMs, the stride-1 layers at 8x8 ... 128x128 (gemm_forms.hip)
@@ -222,7 +215,6 @@ LayerCaps layer_caps(const std::vector<ConvLayerHost>& convs, int i, int flags, 
     LayerCaps k;
     if (!c.up) {
         const bool after_up = i > 0 && convs[i - 1].up;
-        k.has[kWino] = gance::winograd_supported(c.cin, c.cout, res, res);
         k.has[kWino64] = gance::winograd64_supported(c.cin, c.cout, res, res);
         k.has[kWino43] = after_up && res >= 32 && res <= wino43_max_res(flags, tune) && gance::winograd43_supported(c.cin, c.cout, res, res);
         k.has[kWinoGemm] = i > 0 && tune.winogemm_min_columns > 0 && wino43_max_res(flags, tune) >= 16 && gance::winogemm_supported(c.cin, c.cout, res, res);
@@ -243,7 +235,7 @@ enum class Form {
     Direct,        // conv_mfma.hip, one launch
     DirectSplitK,  // ... split-K into slabs + the finish pass
     DirectTorgb,   // ... the last layer with its whole ToRGB (and the uint8 conversion) in the epilogue
-    Wino, WinoTorgb, Wino64, Wino43, WinoGemm,  // the stride-1 forms of WeightImage (WinoTorgb: kWino's own fused-ToRGB variant)
+    Wino64, Wino43, WinoGemm,  // the stride-1 forms of WeightImage
     UpTwoPass,     // conv_mfma.hip's transposed conv into parity planes + the FIR pass
     UpGemm,        // scatter-form GEMM + the FIR pass
     UpFused16, UpFused16x, UpSplit  // one fused launch: kUpfir16, kUpfir16x, kUpfirSplit
@@ -276,7 +268,7 @@ struct PlanContext {
 // Which form conv layer idx (a stride-1 conv, direct-form geometry p) runs in for this batch. The layer BEFORE a conv on the
 // 16x16x4 Winograd kernel has to know: that kernel takes its input multiplied by its own style (plan_call's second pass).
 struct ConvForm {
-    bool fused_rgb, winograd, winograd_last, wino64, wino43;
+    bool fused_rgb, winograd, wino64, wino43;
 };
 ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool have_y_then) {
     const ConvLayerHost& c = ctx.convs[idx];
@@ -292,25 +284,25 @@ ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool 
     const auto& tile = gance::kConvTiles[p.tile_id];
     form.fused_rgb = tune.fuse_rgb && c.res_log2 == ctx.convs.back().res_log2 && ctx.limit() == ctx.num_convs() && p.nsplit == 1 &&
                      p.m_tiles == 1 && tile.TB == 1 && (tile.BM == 32 || tile.BM == 16) && have_y_then && ctx.stop_after <= 0;
-    // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry with the ToRGB product
-    // in its epilogue (Tuning::last_wino64; measured: see DESIGN.md §3)
-    const long long last_tiles = (long long)(res / 16) * (res / 32) * B;
-    if (form.fused_rgb && tune.last_wino64 != 0 && c.cout == 32 && caps.has[kWino64] && !(ctx.flags & GANCE_FLAG_DIRECT_CONV) &&
-        !(ctx.flags & GANCE_FLAG_FORCE_WINOGRAD) && last_tiles >= ctx.num_cus)
-        form.fused_rgb = false;
-    // Winograd F(2x2,3x3) form where the layer supports it and the launch fills the chip
-    // (one block per CU). Engine flags choose: DIRECT_CONV = never, FORCE_WINOGRAD = whatever
-    // the block count; Tuning::winograd = 0 / 1 / 2 overrides them for tuning.
+    // Winograd form: engine flags choose (DIRECT_CONV = never, FORCE_WINOGRAD = whatever the block count);
+    // Tuning::winograd = 0 / 1 / 2 overrides them for tuning.
     const int wino_mode = tune.winograd >= 0 ? tune.winograd
                                              : ((ctx.flags & GANCE_FLAG_DIRECT_CONV) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_WINOGRAD) ? 2 : 1));
-    // (tiles of 8 x 64 pixels, or 16 x 32 on the 32-pixel-wide layer; the kernel has no split-K)
+    // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry (or in F(4x4,3x3) form) with the ToRGB
+    // channel sum in its epilogue (Tuning::last_wino64; measured: see DESIGN.md §3): where the launch fills the chip, or Winograd is forced
+    const long long last_tiles = (long long)(res / 16) * (res / 32) * B;
+    if (form.fused_rgb && tune.last_wino64 != 0 && c.cout == 32 && caps.has[kWino64] && !(ctx.flags & GANCE_FLAG_DIRECT_CONV) &&
+        (wino_mode == 2 || last_tiles >= ctx.num_cus))
+        form.fused_rgb = false;
+    // Winograd F(2x2,3x3) form where the layer supports it and the launch fills the chip (one block per CU).
+    // The fill rule counts the tiles of round 1's 32-channel kernel (HISTORY.md section D, item 20), which the plans were measured
+    // with: 8 x 64 pixels, or 16 x 32 on the 32-pixel-wide layer; no split-K. That kernel's support predicate was cin % 8 == 0,
+    // 24 <= cin <= 512, cout % 32 == 0, side a multiple of 32: on a square layer exactly winograd64_supported (cout % 64 == 0
+    // wants the side a multiple of 8 and of 32, cout % 32 == 0 of 16 and of 32), so kWino64 names the same set of layers.
     const long long wino_tiles = (long long)(c.cout / 32) * (res % 64 == 0 ? (res / 8) * (res / 64) : (res / 16) * (res / 32)) * B;
-    form.winograd = !c.up && wino_mode != 0 && caps.has[kWino] && (wino_mode == 2 || (p.nsplit == 1 && wino_tiles >= 256));
-    // the direct-form fused last layer stays unless Winograd is forced (Tuning::winograd_rgb says why, and selects the other)
-    form.winograd_last = form.winograd && (wino_mode == 2 || tune.winograd_rgb);
-    // the kernel on 16x16x4 MFMAs (unless Tuning::wino64 is off): every stride-1 conv it
-    // supports that follows an up layer (all of them do: Conv1 follows Conv0_up)
-    form.wino64 = !form.fused_rgb && form.winograd && tune.wino64 && caps.has[kWino64] && idx > 0 && ctx.convs[idx - 1].up;
+    form.winograd = !c.up && wino_mode != 0 && caps.has[kWino64] && (wino_mode == 2 || (p.nsplit == 1 && wino_tiles >= 256));
+    // the kernel on 16x16x4 MFMAs: every stride-1 conv it supports that follows an up layer (all of them do: Conv1 follows Conv0_up)
+    form.wino64 = !form.fused_rgb && form.winograd && idx > 0 && ctx.convs[idx - 1].up;
     // F(4x4, 3x3) where the layer has the weights for it (layer_caps: resolution limit, geometry, an up layer in
     // front) and the launch fills the chip; never the network's last layer while that one carries the fused ToRGB
     const long long w43_tiles = (long long)(c.cout / 32) * (res >= 64 ? (res / 16) * (res / 64) : 1) * B;  // (32 x 32 pixels per tile on the 32-wide layer)
@@ -368,7 +360,7 @@ void name_step(const ConvLayerHost& c, LayerStep* s) {
     const char* kind = "";
     switch (s->form) {
         case Form::Direct: case Form::DirectSplitK: case Form::DirectTorgb: break;
-        case Form::Wino: case Form::WinoTorgb: case Form::Wino64: kind = "W"; break;
+        case Form::Wino64: kind = "W"; break;
         case Form::Wino43: kind = "V"; break;
         case Form::WinoGemm: kind = "VG"; break;
         case Form::UpTwoPass: kind = "T"; break;
@@ -376,7 +368,7 @@ void name_step(const ConvLayerHost& c, LayerStep* s) {
         case Form::UpFused16: case Form::UpFused16x: case Form::UpSplit: kind = s->input_prescaled ? "TFp" : "TF"; break;
     }
     const char* suffix = s->form == Form::UpFused16 ? "/16" : (s->form == Form::UpFused16x ? "/16x" : (s->form == Form::UpSplit ? "/s3" : ""));
-    const bool absorbs_torgb = s->form == Form::DirectTorgb || s->form == Form::WinoTorgb;
+    const bool absorbs_torgb = s->form == Form::DirectTorgb;
     std::snprintf(s->name, sizeof(s->name), "conv%s%d%s_%dx%d_%d->%d%s", kind, c.layer_idx, absorbs_torgb ? "+torgb" : (s->rgb_sum ? "+rgb" : ""),
                   res, res, c.cin, c.cout, suffix);
     if (s->form == Form::DirectSplitK) std::snprintf(s->second, sizeof(s->second), "finish%d_%dx%d", c.layer_idx, res, res);
@@ -409,9 +401,9 @@ std::vector<LayerStep> plan_call(const std::vector<ConvLayerHost>& convs, const 
             if (caps[li].has[kWinoGemm] && gemm_columns >= tune.winogemm_min_columns && gemm_columns <= gance::kWinoGemmMaxColumns && !form.wino43) {
                 s.form = Form::WinoGemm;
             } else if (form.fused_rgb) {
-                s.form = form.winograd_last ? Form::WinoTorgb : Form::DirectTorgb;
-            } else if (s.p.nsplit == 1 || form.winograd) {
-                s.form = form.wino43 ? Form::Wino43 : (form.wino64 ? Form::Wino64 : (form.winograd ? Form::Wino : Form::Direct));
+                s.form = Form::DirectTorgb;
+            } else if (s.p.nsplit == 1 || form.wino64 || form.wino43) {
+                s.form = form.wino43 ? Form::Wino43 : (form.wino64 ? Form::Wino64 : Form::Direct);
                 // Where the 64-channel Winograd kernel holds every channel of a pixel in one block (Cout = 64 at 512^2,
                 // Cout = 32 at 1024^2) its epilogue also does the channel sum of the layer's ToRGB on the matrix pipe; the
                 // ToRGB pass then only adds bias and skip image (and converts). The LAST layer's activation has no

@@ -148,14 +148,7 @@ hipError_t launch_modconv(int tile_id, const ConvArgs& args, int total_blocks, h
 // launch_modconv hands them on. Same arguments and weight image; one channel tile, no split-K, kEpilogueRgb on the stride-1 tile.
 hipError_t launch_modconv16(int tile_id, const ConvArgs& args, int total_blocks, hipStream_t stream);
 
-// Winograd F(2x2, 3x3) form of the stride-1 conv (winograd_conv.hip): 32 output channels x 8x64 pixels
-// per block; args.w points at the layer's transformed weights [m_tile][chunk][16][4][32].
-bool winograd_supported(int cin, int cout, int H, int W);
-size_t winograd_weight_floats(int cin, int cout);
-void winograd_transform_weights(const float* w_in /*[9][cin][cout]*/, int cin, int cout, float* w_out);
-hipError_t launch_winograd_conv(const ConvArgs& args, hipStream_t stream);
-
-// The same Winograd form for layers with >= 64 output channels (winograd64_conv.hip): 64 channels x 8x32 pixels per
+// Winograd F(2x2, 3x3) form of the stride-1 conv for layers with >= 64 output channels (winograd64_conv.hip): 64 channels x 8x32 pixels per
 // block on v_mfma_f32_16x16x4_f32; args.w points at [m tile of 64][chunk of 8][16][8][16][4].
 bool winograd64_supported(int cin, int cout, int H, int W);
 size_t winograd64_weight_floats(int cin, int cout);

@@ -1,14 +1,13 @@
-// Winograd F(2x2, 3x3) form of the modulated 3x3 stride-1 convolution on v_mfma_f32_16x16x4_f32: the same arithmetic as
-// winograd_conv.hip (`modulated_conv2d_layer` -> tf.nn.conv2d), every Conv1 layer from 32^2 to 1024^2.
+// Winograd F(2x2, 3x3) form of the modulated 3x3 stride-1 convolution on v_mfma_f32_16x16x4_f32: Y = A^T [sum_ci U (.) V] A
+// (`modulated_conv2d_layer` -> tf.nn.conv2d), every Conv1 layer from 32^2 to 1024^2.
 //
-// Why a second kernel. In winograd_conv.hip a wave transforms a 4x4 input window per (tile, channel) -- 40 vector
-// instructions -- and feeds the 16 results to 16 MFMAs (one 32x32x2 tile of 32 output channels per Winograd
-// position): 2.5 vector instructions per MFMA, and on gfx950 the fp32 MFMA does not hide vector work of its own
-// wave, so that kernel executes at 0.58 of the matrix peak. Here the MFMA is v_mfma_f32_16x16x4_f32
-// (16 channels x 16 tiles x 4 input channels, 32 cycles) and a wave holds FOUR accumulator tiles per position:
-// 16 positions x 4 x 4 registers = 256 accumulators, the same register budget, but a transformed window now feeds
-// 64 MFMAs (2048 matrix-pipe cycles) instead of 16 (1024). The weight fragments of a position come out of LDS in ONE
-// read (the weight image is laid out [pos][ci][m % 16][m / 16]).
+// Why this MFMA. A wave transforms a 4x4 input window per (tile, channel) in 40 vector instructions, and on gfx950 the
+// fp32 MFMA does not hide vector work of its own wave: what counts is the matrix work a transformed window
+// feeds. The MFMA is v_mfma_f32_16x16x4_f32 (16 channels x 16 tiles x 4 input channels, 32 cycles) and a wave holds FOUR
+// accumulator tiles per position: 16 positions x 4 x 4 registers = 256 accumulators, so a transformed window feeds
+// 64 MFMAs (2048 matrix-pipe cycles). (Round 1's kernel fed 16 MFMAs on 32x32x2 tiles, 1024 cycles, from the same
+// register budget and ran at 0.58 of the matrix peak: HISTORY.md.) The weight fragments of a position come out of LDS
+// in ONE read (the weight image is laid out [pos][ci][m % 16][m / 16]).
 //
 // Geometries (template <MT channel tiles, TG tile rows per wave>): <4, 1> = 64 output channels x (8 x 32) pixels per
 // block; <2, 2> = 32 channels x (16 x 32) pixels (the 32-channel layer at 1024^2). Block = 4 waves; wave w owns tile
@@ -59,7 +58,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // Geometry of a variant: MT channel tiles of 16 per wave and position, TG tile rows per wave.
 //   <4, 1>: 64 output channels x  8 x 32 pixels per block (layers with >= 64 output channels)
 //   <2, 2>: 32 output channels x 16 x 32 pixels per block (the 32-channel layers: 1024^2); a wave then transforms TWO
-//           windows per k-step, i.e. the vector work per matrix cycle of winograd_conv.hip, but keeps this kernel's
+//           windows per k-step, i.e. twice the vector work per matrix cycle of <4, 1>, but keeps this kernel's
 //           ring, weave and one-instruction weight fragments
 // Either way 16 positions x TG x MT x 4 registers = 256 accumulators and 64 MFMAs per k-step.
 constexpr int kKC = 4;                  // input channels per chunk = one k-step of the 16x16x4 MFMA

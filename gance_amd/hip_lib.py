@@ -418,7 +418,9 @@ class Engine:
         :param conv_form: "auto" = every Conv1 from 32x32 up in Winograd F(4x4,3x3) form when its launch has a tile per
         CU, else F(2x2,3x3) when that launch has a block per CU, else the direct form; "direct" = never Winograd;
         "winograd" = the F(2x2,3x3) kernels on every layer that supports them, whatever the batch; "winograd43" = the
-        F(4x4,3x3) kernel on every Conv1 from 32x32 up (F(2x2,3x3) on what is left), whatever the batch.
+        F(4x4,3x3) kernel on every Conv1 from 32x32 up (F(2x2,3x3) on what is left), whatever the batch. With either of
+        the two a 32-channel last layer (config-f at 1024^2, config-e at 512^2) runs in that Winograd form with the ToRGB
+        channel sum in its epilogue (convW<N>+rgb / convV<N>+rgb, then torgb), as "auto" does once the launch fills the chip.
         """
         self._lib = load_library()
         self._handle = ctypes.c_void_p()

@@ -53,7 +53,9 @@ typedef struct gance_engine_config {
  * the multiply-adds) where the launch fills the chip with its 16 x 64 pixel tiles, else F(2x2,3x3) (4/9), else the direct
  * form; results differ between the forms by fp32 rounding only (~1e-6 of the activation range). DIRECT_CONV keeps every
  * layer in direct form; FORCE_WINOGRAD alone puts every layer that supports it on the F(2x2,3x3) kernels whatever the
- * batch, FORCE_WINOGRAD | WINOGRAD43 on the F(4x4,3x3) kernel where that supports the layer (parity tests of each form). */
+ * batch, FORCE_WINOGRAD | WINOGRAD43 on the F(4x4,3x3) kernel where that supports the layer (parity tests of each form). With
+ * either, a 32-channel last layer (1024^2, or 512^2 with FMAP_BASE_8K) runs in that form with the ToRGB channel sum in its
+ * epilogue, the launch the default selects there once it fills the chip, not the direct-form launch that absorbs the whole ToRGB. */
 #define GANCE_FLAG_DIRECT_CONV 2
 #define GANCE_FLAG_FORCE_WINOGRAD 4
 /* Conv0_up of the layers whose input is >= 64 wide runs as ONE kernel (transposed conv + FIR + noise + bias +

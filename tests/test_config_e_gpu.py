@@ -18,6 +18,8 @@ variables, so it runs config-e unchanged).
     layers 14 and 15 only: the one batch at which the default plan on 256 CUs runs the 64 -> 32 up layer in the pair form of the
     fused up kernel (convTFp13_512x512_64->32/16x, between convV12+rgb and convV14+rgb; at 16 and at 18 frames it is "/s3").
     tests/test_isolated_coverage.py holds these batches against the planner (LARGE_CASES of tests/isolated_config_e_cases.py).
+  * conv_form "winograd" / "winograd43" on the 512^2 network, 2 frames: the smallest network with a 32-channel last layer, which
+    those forms end in convW14+rgb / convV14+rgb and torgb_512x512 (measured: image error 7.8e-6 / 8.6e-6).
   * The frame-emitting launch (conv16+torgb_1024x1024_16->16: conv, ToRGB 16 -> 3, + upsampled 512^2 image + bias, uint8) by the
     method of tests/test_isolated_image_gpu.py: layer 17's activation (tap: the unfused launch) and debug_image_after of the 512^2
     stage through ONE fp64 torgb_layer against the float image of a whole untapped call; ceilings 2e-5 / 1e-4 (stress) and
@@ -195,6 +197,39 @@ def test_whole_chain_matches_oracle_on_the_z_entry(library, resolution: int, tmp
             _check_frames(frames[checked], image[checked], want[rows], False, f"{batch} frames")
     finally:
         network.stop()
+
+
+# ---- the 32-channel last layer with a Winograd form forced (the smallest network that has one: 512^2) ----
+
+FORCED_LAST = {"winograd": "convW14+rgb_512x512_32->32", "winograd43": "convV14+rgb_512x512_32->32"}
+_FORCED_ORACLE: list = []
+
+
+@pytest.mark.parametrize("conv_form", sorted(FORCED_LAST))
+def test_forced_winograd_forms_end_a_512_network_in_the_epilogue_channel_sum(library, conv_form: str) -> None:
+    """
+    conv_form "winograd" / "winograd43" on a network whose last layer has 32 channels: that layer runs on the 16x16x4 kernel's
+    32-channel geometry / in F(4x4,3x3) form with the ToRGB channel sum in its epilogue (no launch absorbs the whole ToRGB),
+    the two frames against the fp64 oracle at the whole-chain bars.
+    """
+    resolution, batch = 512, 2
+    spec = sg2_spec.make_spec(resolution, fmap_base=CONFIG_E)
+    variables = _variables("every_term", resolution)
+    dlatents = np.random.RandomState(7).randn(batch, spec.num_layers, 512).astype(np.float32)
+    if not _FORCED_ORACLE:  # (once, shared by the two forms)
+        _FORCED_ORACLE.append(ref.synthesize_w(dlatents, variables, resolution))
+    engine = hip_lib.Engine(variables, resolution, max_batch=batch, conv_form=conv_form, profile=True)
+    try:
+        assert engine.fmap_base == CONFIG_E
+        frames, image = engine.synthesize_w(dlatents, want_float=True)
+        whole_call = [step.name for step in engine.steps()]
+    finally:
+        engine.close()
+    print(f"\nconfig-e every_term network {resolution}^2, conv_form={conv_form}:")
+    conv_launches = [name for name in whole_call if name.startswith("conv")]
+    assert conv_launches[-1] == FORCED_LAST[conv_form] and whole_call[-1] == "torgb_512x512", whole_call[-3:]
+    assert not any("+torgb" in name for name in whole_call), whole_call
+    _check_frames(frames, image, _FORCED_ORACLE[0], False, f"{batch} frames")
 
 
 # ---- the 512^2 and 1024^2 layers in isolation ----

@@ -81,7 +81,7 @@ def library_path() -> Path:
 
 def test_fixture_covers_the_matrix() -> None:
     headers = [header for header, _ in SECTIONS]
-    assert len(headers) == len(set(headers)) == 36
+    assert len(headers) == len(set(headers)) == 35
     for header, plans in SECTIONS:
         resolution, max_batch, _, _, knob = header.split()
         if knob == "-":

@@ -149,16 +149,24 @@ def test_config_f_1024_frame_matches_oracle(library) -> None:
     )
 
 
-def test_config_f_1024_with_every_eligible_layer_in_winograd_form(library) -> None:
-    """The 64^2 ... 1024^2 stride-1 layers all in Winograd form, the last one fused with its ToRGB."""
+@pytest.mark.parametrize("up_form", ["auto", "split"])
+def test_config_f_1024_with_every_eligible_layer_in_winograd_form(library, up_form: str) -> None:
+    """
+    The 64^2 ... 1024^2 stride-1 layers all in Winograd form, the last one (the 16x16x4 kernel's 32-channel geometry) with the
+    channel sum of its ToRGB in the epilogue. up_form="split": the two-pass up layer's FIR pass then writes that geometry's
+    pre-scaled input.
+    """
     resolution = 1024
     variables = sg2_spec.make_random_variables(resolution, seed=0, perturb=True)
     z = np.random.RandomState(2).randn(2, 512).astype(np.float32)
-    engine = hip_lib.Engine(variables, resolution, max_batch=2, conv_form="winograd")
+    engine = hip_lib.Engine(variables, resolution, max_batch=2, conv_form="winograd", up_form=up_form, profile=True)
     try:
         frames, image = engine.synthesize_z(z, truncation_psi=1.2, want_float=True)
+        launches = [step.name for step in engine.steps()]
     finally:
         engine.close()
+    assert "convW16+rgb_1024x1024_32->32" in launches and not any("+torgb" in name for name in launches), launches
+    assert ("fir15_1024x1024" in launches) == (up_form == "split"), launches
     # (the same network and first z as test_config_f_1024_every_term_on_default_kernels: RandomState(2)'s first 512 draws)
     _check_frames(frames[:1], image[:1], _oracle_once("every_term_1024", lambda: ref.synthesize_z(z[:1], variables, resolution, truncation_psi=1.2)))
 
@@ -636,14 +644,14 @@ np.savez(sys.argv[2], frames=frames, image=image)
 @pytest.mark.parametrize(
     "variable,off_value,up_form",
     [
-        ("GANCE_TUNE_W64_RGB", "0", "auto"), ("GANCE_TUNE_W64_RGB", "0", "fused"), ("GANCE_TUNE_WINO64", "0", "auto"), ("GANCE_TUNE_PRESCALE_UP", "0", "fused"),
+        ("GANCE_TUNE_W64_RGB", "0", "auto"), ("GANCE_TUNE_W64_RGB", "0", "fused"), ("GANCE_TUNE_PRESCALE_UP", "0", "fused"),
         ("GANCE_TUNE_W43_ROUNDS", "1", "fused"),  # one persistent block per CU in the F(4x4,3x3) launches instead of four queued ones: same tiles, other blocks
     ],
 )
 def test_winograd_kernel_fallback_forms_agree_with_the_default(library, tmp_path, variable: str, off_value: str, up_form: str) -> None:
     """
     The tuning switches read once per process select kernels the default path no longer runs (the
-    Winograd kernel without the ToRGB product in its epilogue; the round-1 32-channel Winograd kernel; the
+    Winograd kernel without the ToRGB product in its epilogue; the
     fused up kernel with the style scale in its own K loop instead of on its producer's stores):
     each in its own process, same network and latents, against the default form. `up_form="fused"` forces the fused
     up kernel at this small batch: with it, a Winograd launch WITHOUT the ToRGB product must not scale its stores by the
