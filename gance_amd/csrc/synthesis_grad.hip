@@ -240,6 +240,41 @@ __global__ __launch_bounds__(kThreads) void noise_bias_lrelu_backward_kernel(con
     grad_x[at] = grad_out[at] * ((out[at] > 0.f ? 1.f : 0.2f) * 1.4142135623730951f);
 }
 
+// noise_bias_lrelu_backward_kernel with the noise gradient in the same pass: grad_noise[n][pos] = strength * sum_{b of plane n} sum_c grad_x[b][c][pos]
+// (a shared plane, noise_batch 1, sums over the batch too). A block is PX consecutive positions x G = kThreads / PX channel
+// groups: thread (px, g) adds the channels g, g + G, ... of each sample in rising order, thread (px, 0) adds the G partial sums
+// in rising order. PX is chosen by the shape alone (64, or 16 below 4096 positions, where 512 channels would otherwise sit
+// in 16 ... 256 threads), so the order is a function of the shape and two runs give the same bits.
+template <int PX>
+__global__ __launch_bounds__(kThreads) void noise_bias_lrelu_backward_noise_kernel(const float* __restrict__ grad_out, const float* __restrict__ out,
+                                                                                   const float* __restrict__ strength, int noise_batch, int batch,
+                                                                                   int channels, int positions, float* __restrict__ grad_x,
+                                                                                   float* __restrict__ grad_noise) {
+    constexpr int G = kThreads / PX;
+    __shared__ float part[kThreads];
+    const int px = threadIdx.x % PX, g = threadIdx.x / PX;
+    const int pos = blockIdx.x * PX + px;
+    const int plane = blockIdx.y;
+    const int b_first = noise_batch > 1 ? plane : 0, b_last = noise_batch > 1 ? plane + 1 : batch;
+    float sum = 0.f;
+    if (pos < positions)
+        for (int b = b_first; b < b_last; ++b)
+            for (int c = g; c < channels; c += G) {
+                const size_t at = ((size_t)b * channels + c) * positions + pos;
+                const float gx = grad_out[at] * ((out[at] > 0.f ? 1.f : 0.2f) * 1.4142135623730951f);
+                grad_x[at] = gx;
+                sum += gx;
+            }
+    part[g * PX + px] = sum;
+    __syncthreads();
+    if (g == 0 && pos < positions) {
+        float total = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k) total += part[k * PX + px];
+        grad_noise[(size_t)plane * positions + pos] = total * strength[0];
+    }
+}
+
 // y = upsample_2d(y_prev) + sum_i w[i][c] style[b][i] x[b][i] + bias[c]. upsample_2d per axis: output o reads the zero-inserted
 // image z (z[2 j] = y_prev[j]) at o + a - 2 with [1,3,3,1] / 4 (gain 2 per axis, pads 2 and 1)
 __global__ __launch_bounds__(kThreads) void torgb_skip_kernel(const float* __restrict__ x, const float* __restrict__ style, const float* __restrict__ w,
@@ -527,6 +562,28 @@ int gance_noise_bias_lrelu_backward(const float* d_grad_out, const float* d_out,
     if (guard.status() != hipSuccess) return hip_failure(kName, "hipSetDevice", guard.status());
     const size_t total = (size_t)batch * channels * height * width;
     noise_bias_lrelu_backward_kernel<<<blocks_for(total), kThreads, 0, (hipStream_t)stream_ptr>>>(d_grad_out, d_out, total, d_grad_x);
+    return launched(kName);
+}
+
+int gance_noise_bias_lrelu_backward_noise(const float* d_grad_out, const float* d_out, const float* d_strength, int32_t noise_batch, int32_t batch,
+                                          int32_t channels, int32_t height, int32_t width, float* d_grad_x, float* d_grad_noise, void* stream_ptr) {
+    using namespace gance_sgrad;
+    static const char* const kName = "gance_noise_bias_lrelu_backward_noise";
+    if (const int status = check_pointers(kName, {d_grad_out, d_out, d_strength, d_grad_x, d_grad_noise})) return status;
+    if (const int status = check_shape(kName, batch, {channels}, height, width)) return status;
+    if (noise_batch != 1 && noise_batch != batch)
+        return invalid(kName, "noise must hold 1 or " + std::to_string(batch) + " planes, got " + std::to_string(noise_batch));
+    if (const int status = no_device()) return status;
+    gance::DeviceGuard guard(gance::device_of_pointer(d_out));  // launch where the data lives
+    if (guard.status() != hipSuccess) return hip_failure(kName, "hipSetDevice", guard.status());
+    const int positions = height * width;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (positions >= 4096)
+        noise_bias_lrelu_backward_noise_kernel<64><<<dim3((positions + 63) / 64, noise_batch), kThreads, 0, stream>>>(
+            d_grad_out, d_out, d_strength, noise_batch, batch, channels, positions, d_grad_x, d_grad_noise);
+    else
+        noise_bias_lrelu_backward_noise_kernel<16><<<dim3((positions + 15) / 16, noise_batch), kThreads, 0, stream>>>(
+            d_grad_out, d_out, d_strength, noise_batch, batch, channels, positions, d_grad_x, d_grad_noise);
     return launched(kName);
 }
 

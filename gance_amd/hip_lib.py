@@ -331,6 +331,30 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
     ),
+    "gance_noise_bias_lrelu_backward_noise": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_noise_regularizer_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
+    "gance_noise_regularizer_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "gance_noise_regularizer_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "gance_pyramid_distance_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
+    "gance_pyramid_distance_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "gance_pyramid_distance_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
 }
 
 # entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
@@ -342,6 +366,9 @@ ADDED_WITHIN_ABI = {
     "gance_engine_debug_read_skip_image", "gance_png_encode_bounds", "gance_png_encode_u8", "gance_modconv3x3_workspace_bytes",
     "gance_modconv3x3_forward", "gance_modconv3x3_backward", "gance_noise_bias_lrelu_forward", "gance_noise_bias_lrelu_backward",
     "gance_torgb_skip_workspace_bytes", "gance_torgb_skip_forward", "gance_torgb_skip_backward",
+    "gance_noise_bias_lrelu_backward_noise", "gance_noise_regularizer_workspace_bytes", "gance_noise_regularizer_forward",
+    "gance_noise_regularizer_backward", "gance_pyramid_distance_workspace_bytes", "gance_pyramid_distance_forward",
+    "gance_pyramid_distance_backward",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1023,6 +1050,20 @@ def noise_bias_lrelu_backward_device(  # pylint: disable=too-many-arguments
     )
 
 
+def noise_bias_lrelu_backward_noise_device(  # pylint: disable=too-many-arguments
+    d_grad_out: int, d_out: int, d_strength: int, noise_batch: int, batch: int, channels: int, height: int, width: int, d_grad_x: int,
+    d_grad_noise: int, stream: int = 0,
+) -> None:
+    """grad_x and grad_noise [noise_batch, 1, S, S] of `noise_bias_lrelu_forward_device` in one pass (gance_noise_bias_lrelu_backward_noise)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_noise_bias_lrelu_backward_noise(d_grad_out, d_out, d_strength, noise_batch, batch, channels, height, width, d_grad_x,
+                                                  d_grad_noise, stream or None),
+    )
+
+
+
 def torgb_skip_workspace_bytes(batch: int, cin: int, side: int) -> int:
     """Workspace of one `torgb_skip_backward_device` call."""
     lib = load_library()
@@ -1051,6 +1092,73 @@ def torgb_skip_backward_device(  # pylint: disable=too-many-arguments
         lib,
         lib.gance_torgb_skip_backward(d_grad_y, d_x, d_style, d_weight, batch, cin, height, width, d_grad_x, d_grad_style, d_grad_y_prev or None,
                                       d_workspace, workspace_bytes, stream or None),
+    )
+
+
+# ---- projection's losses (csrc/projection.hip): raw device pointers, asynchronous on `stream` ----
+
+
+def noise_regularizer_levels(side: int) -> int:
+    """Pyramid levels of the noise regulariser: sides side, side / 2, ... 8 (one level for 4 and 8)."""
+    return max(1, int(side).bit_length() - 3)
+
+
+def noise_regularizer_workspace_bytes(batch: int, side: int) -> int:
+    """Workspace shared by `noise_regularizer_forward_device` and `noise_regularizer_backward_device`.
+    :raises ValueError: a side that is not a power of two in [4, 1024], a batch outside [1, 65535]."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_noise_regularizer_workspace_bytes(batch, side, ctypes.byref(size)))
+    return int(size.value)
+
+
+def noise_regularizer_forward_device(  # pylint: disable=too-many-arguments
+    d_noise: int, batch: int, side: int, d_reg: int, d_means: int, d_workspace: int, workspace_bytes: int, stream: int = 0
+) -> None:
+    """reg [batch] and means [batch, levels, 2] of planes [batch, 1, side, side] (gance_noise_regularizer_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_noise_regularizer_forward(d_noise, batch, side, d_reg, d_means, d_workspace, workspace_bytes, stream or None)
+    )
+
+
+def noise_regularizer_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_reg: int, d_noise: int, d_means: int, d_workspace: int, workspace_bytes: int, batch: int, side: int, d_grad_noise: int, stream: int = 0
+) -> None:
+    """grad_noise from grad_reg, the forward's means and its workspace (gance_noise_regularizer_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_noise_regularizer_backward(d_grad_reg, d_noise, d_means, d_workspace, workspace_bytes, batch, side, d_grad_noise, stream or None),
+    )
+
+
+def pyramid_distance_workspace_bytes(batch: int, resolution: int) -> int:
+    """Workspace shared by `pyramid_distance_forward_device` and `pyramid_distance_backward_device`.
+    :raises ValueError: a resolution that is not a power of two in [8, 1024], a batch outside [1, 65535]."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_pyramid_distance_workspace_bytes(batch, resolution, ctypes.byref(size)))
+    return int(size.value)
+
+
+def pyramid_distance_forward_device(  # pylint: disable=too-many-arguments
+    d_image: int, d_target: int, batch: int, resolution: int, d_dist: int, d_workspace: int, workspace_bytes: int, stream: int = 0
+) -> None:
+    """dist [batch] of image [batch, 3, R, R] in -1 ... 1 against target [batch, 3, min(R, 256), ...] in 0 ... 255 (gance_pyramid_distance_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_pyramid_distance_forward(d_image, d_target, batch, resolution, d_dist, d_workspace, workspace_bytes, stream or None)
+    )
+
+
+def pyramid_distance_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_dist: int, d_workspace: int, workspace_bytes: int, batch: int, resolution: int, d_grad_image: int, stream: int = 0
+) -> None:
+    """grad_image from grad_dist and the forward's workspace (gance_pyramid_distance_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_pyramid_distance_backward(d_grad_dist, d_workspace, workspace_bytes, batch, resolution, d_grad_image, stream or None)
     )
 
 

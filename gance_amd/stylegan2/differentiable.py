@@ -15,9 +15,10 @@ and the per-layer plumbing is plain torch on the device, because it is tiny:
     style = dlatents[:, row] @ mod_weight + mod_bias + 1        [B, Cin]
     demod = rsqrt(style^2 @ sum_tap(weight^2) + 1e-8)           [B, Cout]
 
-so autograd itself carries the ops' grad_style and grad_demod back to the dlatents. Gradients exist for the dlatents only
-(not for weights, noise or biases); the mapping network is not part of it: projection works in W. What it is for: optimising
-dlatents against any loss written in PyTorch (the reference's projection, gance/projection/projector.py, without its loss).
+so autograd itself carries the ops' grad_style and grad_demod back to the dlatents. Gradients exist for the dlatents and for
+noise planes passed as tensors that require grad (not for weights, noise strengths or biases); the mapping network is not
+part of it: projection works in W. What it is for: optimising dlatents against any loss written in PyTorch
+(gance_amd/stylegan2/projector.py is the reference's projection, gance/projection/projector.py, built on it).
 """
 
 from typing import Dict, List, Optional, Union
@@ -109,6 +110,7 @@ class DifferentiableSynthesis:
     def _noise(self, conv: _ConvWeights, noise: Optional[NoisePlanes], batch: int) -> torch.Tensor:
         if noise is None or conv.layer_idx not in noise:
             return conv.noise
+        # (a float32 tensor already on the device passes through both calls as itself: it may be a leaf that requires grad)
         planes = torch.as_tensor(noise[conv.layer_idx], dtype=torch.float32).to(self.device)
         side = conv.noise.shape[2]
         if planes.dim() != 4 or planes.shape[0] not in (1, batch) or tuple(planes.shape[1:]) != (1, side, side):

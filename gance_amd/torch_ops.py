@@ -14,7 +14,10 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.modconv3x3(x, style, demod, weight, up)        [B, Cin, S, S] f32 -> [B, Cout, S or 2S, ...] f32   differentiable
     torch.ops.gance.noise_bias_lrelu(x, noise, strength, bias)     [B, C, S, S] f32 -> the same                          differentiable
     torch.ops.gance.torgb_skip(x, style, weight, bias, y_prev)     [B, Cin, S, S] f32 -> [B, 3, S, S] f32                differentiable
-    (each with a `_backward` op; gradients reach x, style, demod and y_prev: gance_amd/stylegan2/differentiable.py is the user)
+    (each with a `_backward` op; gradients reach x, style, demod, y_prev and the noise planes: gance_amd/stylegan2/differentiable.py is the user)
+    torch.ops.gance.noise_regularizer(noise)                       [B, 1, S, S] f32 -> [B] f32                           differentiable
+    torch.ops.gance.pyramid_distance(image, target)                [B, 3, R, R], [B, 3, min(R, 256), ...] f32 -> [B]     differentiable
+    (projection's losses: gance_amd/stylegan2/projector.py is the user)
 
 Tensors are CUDA (HIP) tensors; every op launches on torch's CURRENT stream of the tensor's device and returns
 without synchronising, so the ops compose with torch code and with `torch.distributed` collectives in stream
@@ -529,13 +532,49 @@ def _(grad_out: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out.new_empty(out.shape)
 
 
+@torch.library.custom_op("gance::noise_bias_lrelu_backward_noise", mutates_args=(), device_types="cuda")
+def noise_bias_lrelu_backward_noise(
+    grad_out: torch.Tensor, out: torch.Tensor, strength: torch.Tensor, noise_batch: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    (grad_x, grad_noise) of `noise_bias_lrelu` in one pass over grad_out and out: grad_x is bit for bit what
+    `noise_bias_lrelu_backward` gives, grad_noise [noise_batch, 1, S, S] = strength * the sum of grad_x over the channels
+    (and, for a shared plane, over the batch), in a fixed order.
+    """
+    batch, channels, height, width = _activation_shape(out)
+    out = _f32_cuda(out, (batch, channels, height, width), "out")
+    grad_out = _f32_cuda(grad_out, tuple(out.shape), "grad_out")
+    if strength.numel() != 1:
+        raise ValueError(f"`strength` must hold one value, got {list(strength.shape)}")
+    strength = _f32_cuda(strength, tuple(strength.shape), "strength")
+    if noise_batch not in (1, batch):
+        raise ValueError(f"`noise_batch` must be 1 or {batch}, got {noise_batch}")
+    grad_x = torch.empty_like(out)
+    grad_noise = torch.empty((noise_batch, 1, height, width), dtype=torch.float32, device=out.device)
+    hip_lib.noise_bias_lrelu_backward_noise_device(
+        grad_out.data_ptr(), out.data_ptr(), strength.data_ptr(), noise_batch, batch, channels, height, width, grad_x.data_ptr(),
+        grad_noise.data_ptr(), _stream(out),
+    )
+    return grad_x, grad_noise
+
+
+@noise_bias_lrelu_backward_noise.register_fake
+def _(grad_out: torch.Tensor, out: torch.Tensor, strength: torch.Tensor, noise_batch: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return out.new_empty(out.shape), out.new_empty((noise_batch, 1, out.shape[2], out.shape[3]))
+
+
 def _noise_bias_lrelu_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
-    ctx.save_for_backward(output)
+    _, noise, strength, _ = inputs
+    ctx.save_for_backward(output, strength)
+    ctx.noise_batch = int(noise.shape[0])
 
 
 def _noise_bias_lrelu_grad(ctx, grad_out: torch.Tensor):  # type: ignore[no-untyped-def]
-    (out,) = ctx.saved_tensors
-    return noise_bias_lrelu_backward(grad_out, out), None, None, None  # (noise, strength and bias have no gradient yet)
+    out, strength = ctx.saved_tensors
+    if ctx.needs_input_grad[1]:
+        grad_x, grad_noise = noise_bias_lrelu_backward_noise(grad_out, out, strength, ctx.noise_batch)
+        return grad_x, grad_noise, None, None
+    return noise_bias_lrelu_backward(grad_out, out), None, None, None  # (strength and bias have no gradient)
 
 
 torch.library.register_autograd("gance::noise_bias_lrelu", _noise_bias_lrelu_grad, setup_context=_noise_bias_lrelu_setup)
@@ -606,3 +645,141 @@ def _torgb_skip_grad(ctx, grad_y: torch.Tensor):  # type: ignore[no-untyped-def]
 
 
 torch.library.register_autograd("gance::torgb_skip", _torgb_skip_grad, setup_context=_torgb_skip_setup)
+
+
+# ---- projection's losses (csrc/projection.hip) ----
+
+
+def _regularizer_planes(noise: torch.Tensor) -> Tuple[int, int]:
+    if noise.dim() != 4 or noise.shape[1] != 1 or noise.shape[2] != noise.shape[3]:
+        raise ValueError(f"`noise` must be [B, 1, S, S], got {list(noise.shape)}")
+    return int(noise.shape[0]), int(noise.shape[2])
+
+
+def _regularizer_forward(noise: torch.Tensor, batch: int, side: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(reg, means, workspace) of one forward call; the workspace holds the pyramid the backward reads."""
+    workspace_bytes = hip_lib.noise_regularizer_workspace_bytes(batch, side)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=noise.device)
+    reg = torch.empty((batch,), dtype=torch.float32, device=noise.device)
+    means = torch.empty((batch, hip_lib.noise_regularizer_levels(side), 2), dtype=torch.float32, device=noise.device)
+    hip_lib.noise_regularizer_forward_device(
+        noise.data_ptr(), batch, side, reg.data_ptr(), means.data_ptr(), workspace.data_ptr(), workspace_bytes, _stream(noise)
+    )
+    return reg, means, workspace
+
+
+@torch.library.custom_op("gance::noise_regularizer", mutates_args=(), device_types="cuda")
+def noise_regularizer(noise: torch.Tensor) -> torch.Tensor:
+    """
+    The noise regulariser of StyleGAN2's projector per sample: over the pyramid of 2x2 means of each plane [B, 1, S, S] (S a
+    power of two in [4, 1024], down to 8 x 8), the sum of mean(v * roll(v, 1, W))^2 + mean(v * roll(v, 1, H))^2 -> [B].
+    """
+    batch, side = _regularizer_planes(noise)
+    noise = _f32_cuda(noise, (batch, 1, side, side), "noise")
+    return _regularizer_forward(noise, batch, side)[0]
+
+
+@noise_regularizer.register_fake
+def _(noise: torch.Tensor) -> torch.Tensor:
+    return noise.new_empty((noise.shape[0],))
+
+
+@torch.library.custom_op("gance::noise_regularizer_backward", mutates_args=(), device_types="cuda")
+def noise_regularizer_backward(grad_reg: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    """
+    grad_noise of `noise_regularizer`. The pyramid and the means are rebuilt here (three small launches over 4/3 of the plane)
+    instead of being carried from the forward op: the op stays a function of its inputs alone.
+    """
+    batch, side = _regularizer_planes(noise)
+    noise = _f32_cuda(noise, (batch, 1, side, side), "noise")
+    grad_reg = _f32_cuda(grad_reg, (batch,), "grad_reg")
+    _, means, workspace = _regularizer_forward(noise, batch, side)
+    grad_noise = torch.empty_like(noise)
+    hip_lib.noise_regularizer_backward_device(
+        grad_reg.data_ptr(), noise.data_ptr(), means.data_ptr(), workspace.data_ptr(), workspace.numel(), batch, side, grad_noise.data_ptr(),
+        _stream(noise),
+    )
+    return grad_noise
+
+
+@noise_regularizer_backward.register_fake
+def _(grad_reg: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    return noise.new_empty(noise.shape)
+
+
+def _noise_regularizer_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(inputs[0])
+
+
+def _noise_regularizer_grad(ctx, grad_reg: torch.Tensor):  # type: ignore[no-untyped-def]
+    (noise,) = ctx.saved_tensors
+    return noise_regularizer_backward(grad_reg, noise)
+
+
+torch.library.register_autograd("gance::noise_regularizer", _noise_regularizer_grad, setup_context=_noise_regularizer_setup)
+
+
+def _distance_shapes(image: torch.Tensor, target: torch.Tensor) -> Tuple[int, int]:
+    if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] != image.shape[3]:
+        raise ValueError(f"`image` must be [B, 3, R, R], got {list(image.shape)}")
+    return int(image.shape[0]), int(image.shape[2])
+
+
+def _distance_forward(image: torch.Tensor, target: torch.Tensor, batch: int, resolution: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dist, workspace) of one forward call; the workspace holds the pyramid of differences the backward reads."""
+    workspace_bytes = hip_lib.pyramid_distance_workspace_bytes(batch, resolution)
+    side = min(resolution, 256)
+    image = _f32_cuda(image, (batch, 3, resolution, resolution), "image")
+    target = _f32_cuda(target, (batch, 3, side, side), "target")
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=image.device)
+    dist = torch.empty((batch,), dtype=torch.float32, device=image.device)
+    hip_lib.pyramid_distance_forward_device(
+        image.data_ptr(), target.data_ptr(), batch, resolution, dist.data_ptr(), workspace.data_ptr(), workspace_bytes, _stream(image)
+    )
+    return dist, workspace
+
+
+@torch.library.custom_op("gance::pyramid_distance", mutates_args=(), device_types="cuda")
+def pyramid_distance(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """
+    A weight-free multi-scale squared distance (not LPIPS): image [B, 3, R, R] in -1 ... 1 (R a power of two in [8, 1024]) is
+    area-averaged to T = min(R, 256) on the 0 ... 255 scale, d_0 = (that - target [B, 3, T, T]) / 255, d_l the 2x2 means down to
+    8 x 8; the sum over the levels of mean(d_l^2) -> [B].
+    """
+    batch, resolution = _distance_shapes(image, target)
+    return _distance_forward(image, target, batch, resolution)[0]
+
+
+@pyramid_distance.register_fake
+def _(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return image.new_empty((image.shape[0],))
+
+
+@torch.library.custom_op("gance::pyramid_distance_backward", mutates_args=(), device_types="cuda")
+def pyramid_distance_backward(grad_dist: torch.Tensor, image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """grad_image of `pyramid_distance`; the pyramid of differences is rebuilt here, as in `noise_regularizer_backward`."""
+    batch, resolution = _distance_shapes(image, target)
+    grad_dist = _f32_cuda(grad_dist, (batch,), "grad_dist")
+    _, workspace = _distance_forward(image, target, batch, resolution)
+    grad_image = torch.empty((batch, 3, resolution, resolution), dtype=torch.float32, device=image.device)
+    hip_lib.pyramid_distance_backward_device(
+        grad_dist.data_ptr(), workspace.data_ptr(), workspace.numel(), batch, resolution, grad_image.data_ptr(), _stream(image)
+    )
+    return grad_image
+
+
+@pyramid_distance_backward.register_fake
+def _(grad_dist: torch.Tensor, image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return image.new_empty(image.shape)
+
+
+def _pyramid_distance_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(*inputs)
+
+
+def _pyramid_distance_grad(ctx, grad_dist: torch.Tensor):  # type: ignore[no-untyped-def]
+    image, target = ctx.saved_tensors
+    return pyramid_distance_backward(grad_dist, image, target), None  # (the target has no gradient)
+
+
+torch.library.register_autograd("gance::pyramid_distance", _pyramid_distance_grad, setup_context=_pyramid_distance_setup)

@@ -588,12 +588,19 @@ int gance_modconv3x3_backward(const float* d_grad_y, const float* d_x, const flo
  * out = lrelu_0.2(x + noise * strength + bias[c]) * sqrt(2): x, out [batch][channels][side][side], d_noise
  * [noise_batch = 1 or batch][1][side][side], d_strength one float on the device, d_bias [channels]. The backward reads the
  * slope off the sign of the saved output (leaky ReLU keeps the sign) and gives grad_x; d_grad_noise, d_grad_strength and
- * d_grad_bias are reserved for gradients that are not implemented and must be NULL.
+ * d_grad_bias are reserved and must be NULL (the noise gradient has an entry point of its own, below).
  */
 int gance_noise_bias_lrelu_forward(const float* d_x, const float* d_noise, int32_t noise_batch, const float* d_strength, const float* d_bias,
                                    int32_t batch, int32_t channels, int32_t height, int32_t width, float* d_out, void* stream);
 int gance_noise_bias_lrelu_backward(const float* d_grad_out, const float* d_out, int32_t batch, int32_t channels, int32_t height, int32_t width,
                                     float* d_grad_x, float* d_grad_noise, float* d_grad_strength, float* d_grad_bias, void* stream);
+/*
+ * The same backward with the noise gradient, in one pass over grad_out and out: d_grad_x as above (the same bits), and
+ * d_grad_noise [noise_batch][1][side][side], grad_noise[n][p] = strength * sum_c grad_x[b][c][p] over the samples b that
+ * read plane n (noise_batch 1: every sample, in rising order). The order of the sum is a function of the shape alone.
+ */
+int gance_noise_bias_lrelu_backward_noise(const float* d_grad_out, const float* d_out, const float* d_strength, int32_t noise_batch, int32_t batch,
+                                          int32_t channels, int32_t height, int32_t width, float* d_grad_x, float* d_grad_noise, void* stream);
 /*
  * ToRGB of the skip architecture: y = upsample_2d(y_prev) + sum_i weight[i,c] * style[b,i] * x[b,i] + bias[c], no
  * demodulation: x [batch][cin][side][side], weight [cin][3], y [batch][3][side][side], d_y_prev [batch][3][side / 2][side / 2]
@@ -606,6 +613,38 @@ int gance_torgb_skip_forward(const float* d_x, const float* d_style, const float
 int gance_torgb_skip_backward(const float* d_grad_y, const float* d_x, const float* d_style, const float* d_weight, int32_t batch, int32_t cin,
                               int32_t height, int32_t width, float* d_grad_x, float* d_grad_style, float* d_grad_y_prev, void* d_workspace,
                               uint64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Projection: the losses of gance_amd/stylegan2/projector.py   */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Float32, C-contiguous, on the device, asynchronous on `stream`, no atomics and one fixed summation order, as above.
+ * Refused with GANCE_ERR_INVALID_ARGUMENT before a device is touched: a NULL or misaligned pointer, a batch outside
+ * [1, 65535], a side that is not a power of two in the stated range, a workspace below the bound.
+ *
+ * Noise regulariser of StyleGAN2's projector, per sample over planes d_noise [batch][1][side][side], side a power of two in
+ * [4, 1024]:  reg = 0;  repeat { reg += mean(v * roll(v, 1, W))^2 + mean(v * roll(v, 1, H))^2;  stop if side <= 8;
+ * v = 2x2 mean of v }  (the roll wraps). levels = max(1, log2(side) - 2). The forward writes d_reg [batch] and the two means
+ * of every level, d_means [batch][levels][2], and leaves the pyramid in the workspace; the backward takes d_means and the
+ * same workspace, unchanged since the forward, and gives d_grad_noise [batch][1][side][side] from d_grad_reg [batch].
+ */
+int gance_noise_regularizer_workspace_bytes(int32_t batch, int32_t side, uint64_t* workspace_bytes);
+int gance_noise_regularizer_forward(const float* d_noise, int32_t batch, int32_t side, float* d_reg, float* d_means, void* d_workspace,
+                                    uint64_t workspace_bytes, void* stream);
+int gance_noise_regularizer_backward(const float* d_grad_reg, const float* d_noise, const float* d_means, const void* d_workspace,
+                                     uint64_t workspace_bytes, int32_t batch, int32_t side, float* d_grad_noise, void* stream);
+/*
+ * Pyramid distance (weight-free; NOT the LPIPS of the published projector): d_image [batch][3][R][R] in -1 ... 1, R a power of
+ * two in [8, 1024]; d_target [batch][3][T][T] in 0 ... 255, T = min(R, 256), f = R / T.  p = f x f area mean of
+ * (image + 1) * 127.5;  d_0 = (p - target) / 255;  d_l = 2x2 mean of d_(l-1) while the side of d_(l-1) is above 8;
+ * dist[b] = sum_l mean over channels and pixels of d_l^2. The forward leaves the d_l in the workspace; the backward takes the
+ * same workspace, unchanged since, and gives d_grad_image [batch][3][R][R] from d_grad_dist [batch].
+ */
+int gance_pyramid_distance_workspace_bytes(int32_t batch, int32_t resolution, uint64_t* workspace_bytes);
+int gance_pyramid_distance_forward(const float* d_image, const float* d_target, int32_t batch, int32_t resolution, float* d_dist,
+                                   void* d_workspace, uint64_t workspace_bytes, void* stream);
+int gance_pyramid_distance_backward(const float* d_grad_dist, const void* d_workspace, uint64_t workspace_bytes, int32_t batch,
+                                    int32_t resolution, float* d_grad_image, void* stream);
 
 #ifdef __cplusplus
 }
