@@ -240,6 +240,15 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_png_encode_lz_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_png_encode_lz_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_jpeg_decode_bounds": (
         ctypes.c_int,
         [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
@@ -368,7 +377,7 @@ ADDED_WITHIN_ABI = {
     "gance_torgb_skip_workspace_bytes", "gance_torgb_skip_forward", "gance_torgb_skip_backward",
     "gance_noise_bias_lrelu_backward_noise", "gance_noise_regularizer_workspace_bytes", "gance_noise_regularizer_forward",
     "gance_noise_regularizer_backward", "gance_pyramid_distance_workspace_bytes", "gance_pyramid_distance_forward",
-    "gance_pyramid_distance_backward",
+    "gance_pyramid_distance_backward", "gance_png_encode_lz_bounds", "gance_png_encode_lz_u8",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -987,6 +996,33 @@ def png_encode_device(  # pylint: disable=too-many-arguments
     _value_error_on_invalid_argument(
         lib,
         lib.gance_png_encode_u8(d_frames, batch, width, height, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None),
+    )
+
+
+def png_encode_lz_bounds(batch: int, width: int, height: int) -> Tuple[int, int]:
+    """(workspace bytes, output capacity) of one `png_encode_lz_device` call. The capacity is `png_encode_bounds`'s (the
+    stored form stays the worst case); the workspace is larger by the match search's tokens, 4 * PNG_SEGMENT_BYTES per segment.
+    :raises ValueError: width or height outside [1, 8192], or batch < 1."""
+    lib = load_library()
+    workspace, capacity = ctypes.c_uint64(), ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_png_encode_lz_bounds(batch, width, height, ctypes.byref(workspace), ctypes.byref(capacity)))
+    return int(workspace.value), int(capacity.value)
+
+
+def png_encode_lz_device(  # pylint: disable=too-many-arguments
+    d_frames: int, batch: int, width: int, height: int, d_workspace: int, workspace_bytes: int, d_out: int, out_capacity: int,
+    d_offsets: int, stream: int = 0,
+) -> None:
+    """
+    `png_encode_device` with an LZ77 match search (csrc/png_lz.hip): the same filter, container and segments; each segment
+    takes the smallest of the stored block, the literal-only block and a block with length / distance pairs that never
+    reach before the segment, so no file is larger than `png_encode_device`'s. Asynchronous on `stream`.
+    :raises ValueError: bad width or height, workspace or capacity below `png_encode_lz_bounds`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_png_encode_lz_u8(d_frames, batch, width, height, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None),
     )
 
 

@@ -1,6 +1,6 @@
 """
 Still images (gance/image_sources/still_image_common.py): written as PNG by the HIP encoder in HBM
-(torch.ops.gance.png_encode), read back through PIL.
+(torch.ops.gance.png_encode, or torch.ops.gance.png_encode_lz with compression="matches"), read back through PIL.
 
 `write_image` / `read_image` keep the reference's signatures. `write_images_device` is the batched form the still
 products use: one encode call per batch, only the compressed bytes cross to the host.
@@ -19,18 +19,31 @@ from gance_amd.gance_types import RGBInt8ImageType
 
 PNG = "png"  # still_image_common.py:16
 
+# `compression`: "huffman" codes literals only (the default, right for network texture); "matches" adds the LZ77 match
+# search: never a larger file, several times smaller on flat or repeating content, a slower encode
+COMPRESSIONS = ("huffman", "matches")
 
-def write_images_device(frames: torch.Tensor, paths: Sequence[Path]) -> List[str]:
+
+def check_compression(compression: str) -> None:
+    """:raises ValueError: `compression` is none of COMPRESSIONS. Touches no device."""
+    if compression not in COMPRESSIONS:
+        raise ValueError(f"compression must be one of {COMPRESSIONS}, got {compression!r}")
+
+
+def write_images_device(frames: torch.Tensor, paths: Sequence[Path], compression: str = "huffman") -> List[str]:
     """
     Encode `frames` [B, H, W, 3] uint8 (CUDA) as PNG in one call, copy the files' bytes (not the worst-case buffer) to the
     host and write frame b to paths[b].
+    :param compression: one of COMPRESSIONS.
     :return: the md5 hex digest of each file, from the bytes in memory: what `hash_file` of the written file gives.
     """
+    check_compression(compression)
     if frames.dim() != 4 or frames.shape[0] != len(paths):
         raise ValueError(f"frames must be [B, H, W, 3] with one path per frame, got {tuple(frames.shape)} and {len(paths)} paths")
     if not paths:
         return []
-    data, offsets = torch.ops.gance.png_encode(frames)
+    encode = torch.ops.gance.png_encode_lz if compression == "matches" else torch.ops.gance.png_encode
+    data, offsets = encode(frames)
     host_offsets = offsets.cpu().numpy()  # synchronises with the encode
     host_data = data[: int(host_offsets[-1])].cpu().numpy()
     hashes = []
@@ -42,11 +55,12 @@ def write_images_device(frames: torch.Tensor, paths: Sequence[Path]) -> List[str
     return hashes
 
 
-def write_image(image: Union[RGBInt8ImageType, torch.Tensor], path: Path) -> None:
+def write_image(image: Union[RGBInt8ImageType, torch.Tensor], path: Path, compression: str = "huffman") -> None:
     """
     Write one image [H, W, 3] uint8 to `path` as PNG (still_image_common.py:19-28). A numpy image is uploaded to the
-    current GPU first; a CUDA tensor is encoded where it is. There is no CPU encoder.
+    current GPU first; a CUDA tensor is encoded where it is. There is no CPU encoder. `compression` is one of COMPRESSIONS.
     """
+    check_compression(compression)
     if isinstance(image, torch.Tensor):
         frames = image
     else:
@@ -56,7 +70,7 @@ def write_image(image: Union[RGBInt8ImageType, torch.Tensor], path: Path) -> Non
         frames = torch.from_numpy(array).cuda()
     if frames.dim() != 3 or frames.shape[2] != 3:
         raise ValueError(f"image must be [H, W, 3], got {tuple(frames.shape)}")
-    write_images_device(frames[None], [path])
+    write_images_device(frames[None], [path], compression=compression)
 
 
 def read_image(image_path: Path, mode: Optional[str] = None) -> RGBInt8ImageType:

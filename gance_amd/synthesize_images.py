@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from gance_amd.hash_file import hash_file
-from gance_amd.image_sources.still_image_common import PNG, write_images_device
+from gance_amd.image_sources.still_image_common import PNG, check_compression, write_images_device
 from gance_amd.logger_common import LOGGER
 from gance_amd.network_interface.network_functions import NETWORK_SUFFIX, MultiNetwork
 from gance_amd.synthesis_file import SYNTHESIS_FILE_SUFFIX, read_vector_in_file, write_synthesis_file
@@ -51,6 +51,7 @@ def synthesis_file_into_networks(  # pylint: disable=too-many-locals
     synthesis_file: Optional[List[str]],
     output_directory: str,
     noise_seed: Optional[int] = None,
+    png_compression: str = "huffman",
 ) -> None:
     """
     For each input synthesis file, read the vector; write each vector to each network
@@ -59,7 +60,11 @@ def synthesis_file_into_networks(  # pylint: disable=too-many-locals
     inside; the vectors of one network are synthesised and encoded in batches of up to `max_batch`.
     :param noise_seed: not in the reference, whose images draw fresh noise each (None): with a seed every image is
         `indexed_create_image_vector(index, vector, noise_seed=noise_seed)`, repeatable.
+    :param png_compression: not in the reference: still_image_common.COMPRESSIONS; "matches" writes smaller or equal files
+        of the same pixels, and the JSON's image_hash is that file's.
+    :raises ValueError: an unknown png_compression, before anything is read or written.
     """
+    check_compression(png_compression)
     network_paths = all_paths(dir_of_paths=networks_dir, given_paths=network, suffix=NETWORK_SUFFIX)
     synthesis_file_paths = all_paths(dir_of_paths=synthesis_files_dir, given_paths=synthesis_file, suffix=SYNTHESIS_FILE_SUFFIX)
     if not network_paths or not synthesis_file_paths:
@@ -89,7 +94,7 @@ def synthesis_file_into_networks(  # pylint: disable=too-many-locals
                 batch_paths = image_paths[start : start + multi_network.max_batch]
                 batch_vectors = vectors[start : start + multi_network.max_batch]
                 frames = multi_network.indexed_create_images_vector_device(index, np.stack(batch_vectors), noise_seed=noise_seed)
-                image_hashes = write_images_device(frames, batch_paths)
+                image_hashes = write_images_device(frames, batch_paths, compression=png_compression)
                 for image_path, image_hash, vector in zip(batch_paths, image_hashes, batch_vectors):
                     write_synthesis_file(
                         destination_path=image_path.with_suffix(SYNTHESIS_FILE_SUFFIX),
@@ -141,6 +146,7 @@ def _write_pass(  # pylint: disable=too-many-arguments,too-many-locals
     network_path: Path,
     network_hash: str,
     noise_seed: Optional[int],
+    png_compression: str,
 ) -> None:
     """
     One pass of one network (create_images + write_images, synthesize_images.py:215-295): candidates in stream order,
@@ -170,7 +176,7 @@ def _write_pass(  # pylint: disable=too-many-arguments,too-many-locals
             output_directory.joinpath(f"{network_name}_{network_hash}_{kind}_{written + offset}.{PNG}") for offset in range(len(accepted))
         ]
         picked = frames if len(accepted) == len(vectors) else frames[torch.tensor(accepted, device=frames.device)]
-        image_hashes = write_images_device(picked, image_paths)
+        image_hashes = write_images_device(picked, image_paths, compression=png_compression)
         for image_path, image_hash, position in zip(image_paths, image_hashes, accepted):
             write_synthesis_file(
                 destination_path=image_path.with_suffix(SYNTHESIS_FILE_SUFFIX),
@@ -194,6 +200,7 @@ def images_from_network(  # pylint: disable=too-many-arguments,too-many-locals
     num_images: int = 0,
     frames_per_call: int = DEFAULT_FRAMES_PER_CALL,
     noise_seed: Optional[int] = None,
+    png_compression: str = "huffman",
 ) -> None:
     """
     Load each network of a directory and synthesize stills with it (synthesize_images.py:327-394): per network a
@@ -207,8 +214,12 @@ def images_from_network(  # pylint: disable=too-many-arguments,too-many-locals
     :param frames_per_call: candidates synthesised per engine call (at most the engine's max_batch).
     :param noise_seed: not in the reference, whose images draw fresh noise each (None): with a seed every candidate is
         `indexed_create_image_vector(index, vector, noise_seed=noise_seed)`, so a run can be repeated.
+    :param png_compression: not in the reference: still_image_common.COMPRESSIONS; "matches" writes smaller or equal files
+        of the same pixels, and the JSON's image_hash is that file's.
     :raises NotImplementedError: num_faces or no_faces non-zero without a face_finder.
+    :raises ValueError: an unknown png_compression, before anything is read or written.
     """
+    check_compression(png_compression)
     if face_finder is None and (num_faces or no_faces):
         raise NotImplementedError("num_faces / no_faces need a face_finder (an object with face_locations(image)); num_images needs none")
     # sorted: the reference takes the directory's own order, and the vector stream runs on from network to network
@@ -249,5 +260,6 @@ def images_from_network(  # pylint: disable=too-many-arguments,too-many-locals
                     network_path=network_path,
                     network_hash=network_hash,
                     noise_seed=noise_seed,
+                    png_compression=png_compression,
                 )
     return None

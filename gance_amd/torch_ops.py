@@ -10,6 +10,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.jpeg_encode_rect(frames, quality)      [B, H, W, 3] u8  -> the same for frames that are not square
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
     torch.ops.gance.png_encode(frames)                     [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
+    torch.ops.gance.png_encode_lz(frames)                  [B, H, W, 3] u8  -> the same with an LZ77 match search: no file larger, flat areas far smaller
     torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
     torch.ops.gance.modconv3x3(x, style, demod, weight, up)        [B, Cin, S, S] f32 -> [B, Cout, S or 2S, ...] f32   differentiable
     torch.ops.gance.noise_bias_lrelu(x, noise, strength, bias)     [B, C, S, S] f32 -> the same                          differentiable
@@ -294,6 +295,26 @@ def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
 
 
+def _png_encode(frames: torch.Tensor, bounds, encode_device) -> Tuple[torch.Tensor, torch.Tensor]:  # type: ignore[no-untyped-def]
+    """The body of the two PNG ops: `bounds` / `encode_device` are hip_lib's pair of one encoder."""
+    _require_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [B, H, W, 3], got {tuple(frames.shape)}")
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if batch == 0:
+        return frames.new_empty((0,), dtype=torch.uint8), frames.new_zeros((1,), dtype=torch.int64)
+    workspace_bytes, capacity = bounds(batch, width, height)
+    frames = frames.contiguous()
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
+    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
+    encode_device(
+        frames.data_ptr(), batch, width, height, workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity, offsets.data_ptr(),
+        _stream(frames),
+    )
+    return data, offsets
+
+
 @torch.library.custom_op("gance::png_encode", mutates_args=(), device_types="cuda")
 def png_encode(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """
@@ -301,28 +322,30 @@ def png_encode(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     back, frame b at data[offsets[b]:offsets[b + 1]]; `capacity` is the worst case of the shape (hip_lib.png_encode_bounds),
     only offsets[-1] bytes are written. H and W are any sizes in [1, 8192]; B == 0 gives empty data and offsets [0].
     """
-    _require_cuda(frames, torch.uint8, "frames")
-    if frames.dim() != 4 or frames.shape[3] != 3:
-        raise ValueError(f"frames must be [B, H, W, 3], got {tuple(frames.shape)}")
-    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    if batch == 0:
-        return frames.new_empty((0,), dtype=torch.uint8), frames.new_zeros((1,), dtype=torch.int64)
-    workspace_bytes, capacity = hip_lib.png_encode_bounds(batch, width, height)
-    frames = frames.contiguous()
-    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
-    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
-    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
-    hip_lib.png_encode_device(
-        frames.data_ptr(), batch, width, height, workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity, offsets.data_ptr(),
-        _stream(frames),
-    )
-    return data, offsets
+    return _png_encode(frames, hip_lib.png_encode_bounds, hip_lib.png_encode_device)
 
 
 @png_encode.register_fake
 def _(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     capacity = hip_lib.png_encode_bounds(batch, width, height)[1] if batch else 0
+    return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+@torch.library.custom_op("gance::png_encode_lz", mutates_args=(), device_types="cuda")
+def png_encode_lz(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    `png_encode` with an LZ77 match search (hip_lib.png_encode_lz_device): the same pixels, the same capacity, and per
+    frame a file that is never larger; frames with flat or repeating areas come out several times smaller, noisy texture
+    byte for byte as `png_encode` writes it.
+    """
+    return _png_encode(frames, hip_lib.png_encode_lz_bounds, hip_lib.png_encode_lz_device)
+
+
+@png_encode_lz.register_fake
+def _(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    capacity = hip_lib.png_encode_lz_bounds(batch, width, height)[1] if batch else 0
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
 
 

@@ -405,7 +405,7 @@ int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t wi
  * smallest sum of |int8(filtered byte)|, ties to the lowest number; the filtered stream is deflated in independent
  * segments of 32768 bytes, each one dynamic-Huffman block over literals and end-of-block (no match search) closed by
  * an empty stored block, or one stored block whenever that is not larger; one IDAT chunk per segment and one for the
- * Adler-32. A frame of one flat colour therefore costs about 1 bit per byte.
+ * Adler-32. A frame of one flat colour therefore costs about 1 bit per byte (gance_png_encode_lz_u8 below does not).
  * gance_png_encode_bounds: host only; the workspace and output capacity one call needs. The capacity is exact for
  * the worst case (every segment stored): batch * (63 + 17 * segments + height * (3 * width + 1)).
  * batch >= 1, width and height in [1, 8192].
@@ -417,6 +417,21 @@ int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t wi
 int gance_png_encode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes, uint64_t* out_capacity);
 int gance_png_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, void* d_workspace,
                         uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream);
+
+/* The same encoder with an LZ77 match search, for frames with flat or repeating areas (plot panels, masks, smooth
+ * output). Filter, container, segments, Adler-32 and CRCs are those of gance_png_encode_u8; each segment takes the
+ * smallest of (a) one stored block, (b) the literal-only dynamic block plus the empty stored block, (c) one dynamic block
+ * of literals, length / distance pairs (RFC 1951: lengths 3 .. 258, overlapping copies allowed) and end-of-block plus the
+ * same empty stored block; on equal sizes the earlier. (a) and (b) are gance_png_encode_u8's bytes of that segment, so a
+ * file is never larger than its file of the same frame, and noisy texture comes out byte for byte the same. A match never
+ * reaches before its own segment's first byte: every segment inflates alone. The parse is greedy with a single-entry
+ * hash table (zlib level 1's design point); see DESIGN.md section 9 item 14 for measured sizes and rates.
+ * gance_png_encode_lz_bounds: the capacity is gance_png_encode_bounds' (the stored form stays the worst case); the
+ * workspace is larger by 4 * 32768 bytes per segment (one 4-byte token per filtered byte), about five times the other's.
+ * gance_png_encode_lz_u8: the contract and the refusals of gance_png_encode_u8. */
+int gance_png_encode_lz_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes, uint64_t* out_capacity);
+int gance_png_encode_lz_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, void* d_workspace,
+                           uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets, void* stream);
 
 /* ---- Motion-JPEG frame decoder -----------------------------------------------------------------
  * The other half of the encoder above, and what frames_in_video (gance/image_sources/video_common.py:229-298) gets from
