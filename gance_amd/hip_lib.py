@@ -364,6 +364,39 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_lpips_input_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_lpips_input_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_bias_relu_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "gance_bias_relu_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "gance_lpips_layer_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
+    "gance_lpips_layer_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "gance_lpips_layer_backward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p],
+    ),
+    "gance_lpips_normalize": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
 }
 
 # entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
@@ -377,7 +410,9 @@ ADDED_WITHIN_ABI = {
     "gance_torgb_skip_workspace_bytes", "gance_torgb_skip_forward", "gance_torgb_skip_backward",
     "gance_noise_bias_lrelu_backward_noise", "gance_noise_regularizer_workspace_bytes", "gance_noise_regularizer_forward",
     "gance_noise_regularizer_backward", "gance_pyramid_distance_workspace_bytes", "gance_pyramid_distance_forward",
-    "gance_pyramid_distance_backward", "gance_png_encode_lz_bounds", "gance_png_encode_lz_u8",
+    "gance_pyramid_distance_backward", "gance_png_encode_lz_bounds", "gance_png_encode_lz_u8", "gance_lpips_input_forward",
+    "gance_lpips_input_backward", "gance_bias_relu_forward", "gance_bias_relu_backward", "gance_lpips_layer_workspace_bytes",
+    "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1196,6 +1231,78 @@ def pyramid_distance_backward_device(  # pylint: disable=too-many-arguments
     _value_error_on_invalid_argument(
         lib, lib.gance_pyramid_distance_backward(d_grad_dist, d_workspace, workspace_bytes, batch, resolution, d_grad_image, stream or None)
     )
+
+
+# ---- LPIPS on VGG16 (csrc/lpips.hip): raw device pointers, asynchronous on `stream` ----
+
+
+def lpips_input_forward_device(  # pylint: disable=too-many-arguments
+    d_image: int, d_shift: int, d_scale: int, batch: int, resolution: int, side: int, d_out: int, stream: int = 0
+) -> None:
+    """image [batch, 3, R, R] -> [batch, 16, side, side]: area mean, (x - shift) / scale, zero channels 3 ... 15 (gance_lpips_input_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(lib, lib.gance_lpips_input_forward(d_image, d_shift, d_scale, batch, resolution, side, d_out, stream or None))
+
+
+def lpips_input_backward_device(d_grad: int, d_scale: int, batch: int, resolution: int, side: int, d_grad_image: int, stream: int = 0) -> None:
+    """grad_image [batch, 3, R, R] from grad [batch, 16, side, side] (gance_lpips_input_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(lib, lib.gance_lpips_input_backward(d_grad, d_scale, batch, resolution, side, d_grad_image, stream or None))
+
+
+def bias_relu_forward_device(  # pylint: disable=too-many-arguments
+    d_x: int, d_bias: int, batch: int, channels: int, side: int, pool: bool, d_y: int, d_p: int, stream: int = 0
+) -> None:
+    """y = max(x + bias, 0) and, with `pool`, p = the 2x2 max pool of y; `d_p` 0 without it (gance_bias_relu_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_bias_relu_forward(d_x, d_bias, batch, channels, side, int(pool), d_y, d_p or None, stream or None)
+    )
+
+
+def bias_relu_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_y: int, d_grad_p: int, d_y: int, batch: int, channels: int, side: int, pool: bool, d_grad_x: int, stream: int = 0
+) -> None:
+    """grad_x of `bias_relu_forward_device` from grad_y, grad_p (0 without `pool`) and the saved y (gance_bias_relu_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_bias_relu_backward(d_grad_y, d_grad_p or None, d_y, batch, channels, side, int(pool), d_grad_x, stream or None)
+    )
+
+
+def lpips_layer_workspace_bytes(batch: int, side: int) -> int:
+    """Workspace of one `lpips_layer_forward_device` call.
+    :raises ValueError: a side outside [4, 1024], a batch outside [1, 65535]."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_lpips_layer_workspace_bytes(batch, side, ctypes.byref(size)))
+    return int(size.value)
+
+
+def lpips_layer_forward_device(  # pylint: disable=too-many-arguments
+    d_f: int, d_target: int, d_lin: int, batch: int, channels: int, side: int, d_dist: int, d_workspace: int, workspace_bytes: int, stream: int = 0
+) -> None:
+    """dist [batch] of features f against normalised target features, weights lin [channels] (gance_lpips_layer_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_lpips_layer_forward(d_f, d_target, d_lin, batch, channels, side, d_dist, d_workspace, workspace_bytes, stream or None)
+    )
+
+
+def lpips_layer_backward_device(  # pylint: disable=too-many-arguments
+    d_grad_dist: int, d_f: int, d_target: int, d_lin: int, batch: int, channels: int, side: int, d_grad_f: int, stream: int = 0
+) -> None:
+    """grad_f of `lpips_layer_forward_device` from grad_dist [batch] (gance_lpips_layer_backward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_lpips_layer_backward(d_grad_dist, d_f, d_target, d_lin, batch, channels, side, d_grad_f, stream or None)
+    )
+
+
+def lpips_normalize_device(d_f: int, batch: int, channels: int, side: int, d_out: int, stream: int = 0) -> None:
+    """out = f / (|f|_2 over the channels + 1e-10) per pixel (gance_lpips_normalize)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(lib, lib.gance_lpips_normalize(d_f, batch, channels, side, d_out, stream or None))
 
 
 JPEG_STATUS_REASONS = {0: "ok", 1: "truncated data", 2: "invalid Huffman code", 3: "restart marker mismatch"}

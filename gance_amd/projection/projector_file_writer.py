@@ -159,7 +159,8 @@ def project_video_to_file(  # pylint: disable=too-many-locals,too-many-arguments
     Project a video (a Motion-JPEG AVI) to a projection file on disk. Parameters and defaults as the reference's; beyond them:
     :param frames_per_batch: frames projected at once, each independently.
     :param seed: of the projector's random draws; frame k's draws depend on (seed, k) only, not on frames_per_batch.
-    :param distance: a callable replacing the built-in pyramid distance (gance_amd.stylegan2.projector).
+    :param distance: a callable replacing the built-in pyramid distance (gance_amd.stylegan2.projector), for instance
+        gance_amd.stylegan2.lpips.VGG16Lpips(load_lpips_weights(path)): LPIPS on VGG16 from the caller's weights.
     :param projection_width_height: if given, it must be the network's (resolution, resolution): projection happens there.
     :param latents_histories_enabled: [steps, W, 512] float32 per frame, 37 MB per frame at 1000 steps, held until the end.
     :raises NotImplementedError: a destination that does not end in .npz; noises or images histories.

@@ -13,8 +13,9 @@ with w perturbed by Gaussian noise whose strength falls to zero over the first t
 differ from upstream and are meant to:
 
 * The built-in distance is `torch.ops.gance.pyramid_distance`, a weight-free multi-scale squared difference at 256^2 and
-  below. It is NOT upstream's LPIPS: the VGG16 weights LPIPS needs are not available here. `distance=` takes any torch
-  callable `(images [B, 3, R, R] float in -1 ... 1, targets [B, R, R, 3] uint8) -> [B]` for users who have one.
+  below. It is NOT upstream's LPIPS: no VGG16 weights are shipped. `distance=` takes any torch callable
+  `(images [B, 3, R, R] float in -1 ... 1, targets [B, R, R, 3] uint8) -> [B]`; `gance_amd.stylegan2.lpips.VGG16Lpips` is
+  upstream's LPIPS on VGG16 as such a callable, from weights the user supplies (`load_lpips_weights`).
 * `start` takes B frames; each has its own w, planes, Adam moments and random draws, and the loss is the sum over the
   frames, so the frames do not interact.
 * The random numbers of frame k (`frame_draws`) are a function of (seed, k) alone, whatever the batch it is projected in.

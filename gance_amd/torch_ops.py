@@ -806,3 +806,234 @@ def _pyramid_distance_grad(ctx, grad_dist: torch.Tensor):  # type: ignore[no-unt
 
 
 torch.library.register_autograd("gance::pyramid_distance", _pyramid_distance_grad, setup_context=_pyramid_distance_setup)
+
+
+# ---- LPIPS on VGG16 (csrc/lpips.hip; the convolutions are gance::modconv3x3 with unit style and demodulation) ----
+
+
+def _square_activation(x: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"`{name}` must be [B, C, S, S], got {list(x.shape)}")
+    return int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+
+
+def _lpips_image_shape(image: torch.Tensor) -> Tuple[int, int]:
+    if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] != image.shape[3]:
+        raise ValueError(f"`image` must be [B, 3, R, R], got {list(image.shape)}")
+    return int(image.shape[0]), int(image.shape[2])
+
+
+LPIPS_INPUT_CHANNELS = 16  # RGB and 13 zero channels: conv1_1 runs through modconv3x3, whose channel counts are multiples of 16
+
+
+@torch.library.custom_op("gance::lpips_input", mutates_args=(), device_types="cuda")
+def lpips_input(image: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, side: int) -> torch.Tensor:
+    """
+    The input of the VGG16 of LPIPS: image [B, 3, R, R] (R a multiple of `side`) is area-averaged by R / side, then
+    (x - shift[c]) / scale[c] -> [B, 16, side, side] with channels 3 ... 15 zero.
+    """
+    batch, resolution = _lpips_image_shape(image)
+    image = _f32_cuda(image, (batch, 3, resolution, resolution), "image")
+    shift, scale = _f32_cuda(shift, (3,), "shift"), _f32_cuda(scale, (3,), "scale")
+    out = torch.empty((batch, LPIPS_INPUT_CHANNELS, side, side), dtype=torch.float32, device=image.device)
+    hip_lib.lpips_input_forward_device(image.data_ptr(), shift.data_ptr(), scale.data_ptr(), batch, resolution, side, out.data_ptr(), _stream(image))
+    return out
+
+
+@lpips_input.register_fake
+def _(image: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, side: int) -> torch.Tensor:
+    return image.new_empty((image.shape[0], LPIPS_INPUT_CHANNELS, side, side))
+
+
+@torch.library.custom_op("gance::lpips_input_backward", mutates_args=(), device_types="cuda")
+def lpips_input_backward(grad: torch.Tensor, scale: torch.Tensor, resolution: int) -> torch.Tensor:
+    """grad_image [B, 3, R, R] of `lpips_input`: grad[:, :3] / (scale[c] * (R / side)^2) over each cell."""
+    batch, _, side = _square_activation(grad, "grad")
+    grad = _f32_cuda(grad, (batch, LPIPS_INPUT_CHANNELS, side, side), "grad")
+    scale = _f32_cuda(scale, (3,), "scale")
+    grad_image = torch.empty((batch, 3, resolution, resolution), dtype=torch.float32, device=grad.device)
+    hip_lib.lpips_input_backward_device(grad.data_ptr(), scale.data_ptr(), batch, resolution, side, grad_image.data_ptr(), _stream(grad))
+    return grad_image
+
+
+@lpips_input_backward.register_fake
+def _(grad: torch.Tensor, scale: torch.Tensor, resolution: int) -> torch.Tensor:
+    return grad.new_empty((grad.shape[0], 3, resolution, resolution))
+
+
+def _lpips_input_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    image, _, scale, _ = inputs
+    ctx.save_for_backward(scale)
+    ctx.resolution = int(image.shape[2])
+
+
+def _lpips_input_grad(ctx, grad: torch.Tensor):  # type: ignore[no-untyped-def]
+    (scale,) = ctx.saved_tensors
+    return lpips_input_backward(grad, scale, ctx.resolution), None, None, None  # (shift and scale have no gradient)
+
+
+torch.library.register_autograd("gance::lpips_input", _lpips_input_grad, setup_context=_lpips_input_setup)
+
+
+@torch.library.custom_op("gance::bias_relu", mutates_args=(), device_types="cuda")
+def bias_relu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """max(x + bias[c], 0) over x [B, C, S, S]."""
+    batch, channels, side = _square_activation(x, "x")
+    x, bias = _f32_cuda(x, (batch, channels, side, side), "x"), _f32_cuda(bias, (channels,), "bias")
+    y = torch.empty_like(x)
+    hip_lib.bias_relu_forward_device(x.data_ptr(), bias.data_ptr(), batch, channels, side, False, y.data_ptr(), 0, _stream(x))
+    return y
+
+
+@bias_relu.register_fake
+def _(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op("gance::bias_relu_backward", mutates_args=(), device_types="cuda")
+def bias_relu_backward(grad_y: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """grad_x of `bias_relu` from the saved output: (y > 0) * grad_y."""
+    batch, channels, side = _square_activation(y, "y")
+    y = _f32_cuda(y, (batch, channels, side, side), "y")
+    grad_y = _f32_cuda(grad_y, tuple(y.shape), "grad_y")
+    grad_x = torch.empty_like(y)
+    hip_lib.bias_relu_backward_device(grad_y.data_ptr(), 0, y.data_ptr(), batch, channels, side, False, grad_x.data_ptr(), _stream(y))
+    return grad_x
+
+
+@bias_relu_backward.register_fake
+def _(grad_y: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return y.new_empty(y.shape)
+
+
+def _bias_relu_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(output)
+
+
+def _bias_relu_grad(ctx, grad_y: torch.Tensor):  # type: ignore[no-untyped-def]
+    (y,) = ctx.saved_tensors
+    return bias_relu_backward(grad_y, y), None  # (the bias has no gradient)
+
+
+torch.library.register_autograd("gance::bias_relu", _bias_relu_grad, setup_context=_bias_relu_setup)
+
+
+@torch.library.custom_op("gance::bias_relu_pool", mutates_args=(), device_types="cuda")
+def bias_relu_pool(x: torch.Tensor, bias: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, p): y = max(x + bias[c], 0) over x [B, C, S, S], S even, and p [B, C, S / 2, S / 2] its 2x2 max pool, in one pass over x."""
+    batch, channels, side = _square_activation(x, "x")
+    x, bias = _f32_cuda(x, (batch, channels, side, side), "x"), _f32_cuda(bias, (channels,), "bias")
+    y = torch.empty_like(x)
+    p = torch.empty((batch, channels, side // 2, side // 2), dtype=torch.float32, device=x.device)
+    hip_lib.bias_relu_forward_device(x.data_ptr(), bias.data_ptr(), batch, channels, side, True, y.data_ptr(), p.data_ptr(), _stream(x))
+    return y, p
+
+
+@bias_relu_pool.register_fake
+def _(x: torch.Tensor, bias: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return x.new_empty(x.shape), x.new_empty((x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2))
+
+
+@torch.library.custom_op("gance::bias_relu_pool_backward", mutates_args=(), device_types="cuda")
+def bias_relu_pool_backward(grad_y: torch.Tensor, grad_p: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """
+    grad_x of `bias_relu_pool`: (y > 0) * (grad_y + grad_p routed to the selected element of its window), the largest y of the
+    window and the first in row-major order among equals.
+    """
+    batch, channels, side = _square_activation(y, "y")
+    y = _f32_cuda(y, (batch, channels, side, side), "y")
+    grad_y = _f32_cuda(grad_y, tuple(y.shape), "grad_y")
+    grad_p = _f32_cuda(grad_p, (batch, channels, side // 2, side // 2), "grad_p")
+    grad_x = torch.empty_like(y)
+    hip_lib.bias_relu_backward_device(
+        grad_y.data_ptr(), grad_p.data_ptr(), y.data_ptr(), batch, channels, side, True, grad_x.data_ptr(), _stream(y)
+    )
+    return grad_x
+
+
+@bias_relu_pool_backward.register_fake
+def _(grad_y: torch.Tensor, grad_p: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return y.new_empty(y.shape)
+
+
+def _bias_relu_pool_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(output[0])
+
+
+def _bias_relu_pool_grad(ctx, grad_y: torch.Tensor, grad_p: torch.Tensor):  # type: ignore[no-untyped-def]
+    (y,) = ctx.saved_tensors
+    return bias_relu_pool_backward(grad_y, grad_p, y), None  # (the bias has no gradient)
+
+
+torch.library.register_autograd("gance::bias_relu_pool", _bias_relu_pool_grad, setup_context=_bias_relu_pool_setup)
+
+
+def _lpips_layer_arguments(f: torch.Tensor, target: torch.Tensor, lin: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int, int, int]:
+    batch, channels, side = _square_activation(f, "f")
+    f = _f32_cuda(f, (batch, channels, side, side), "f")
+    return f, _f32_cuda(target, tuple(f.shape), "target"), _f32_cuda(lin, (channels,), "lin"), batch, channels, side
+
+
+@torch.library.custom_op("gance::lpips_layer", mutates_args=(), device_types="cuda")
+def lpips_layer(f: torch.Tensor, target: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    """
+    The LPIPS head of one tap: with u = f / (|f|_2 over the channels + 1e-10) per pixel and `target` [B, C, S, S] normalised
+    already (`lpips_normalize`), the mean over the pixels of sum_c lin[c] * (u_c - target_c)^2 -> [B].
+    """
+    f, target, lin, batch, channels, side = _lpips_layer_arguments(f, target, lin)
+    workspace_bytes = hip_lib.lpips_layer_workspace_bytes(batch, side)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=f.device)
+    dist = torch.empty((batch,), dtype=torch.float32, device=f.device)
+    hip_lib.lpips_layer_forward_device(
+        f.data_ptr(), target.data_ptr(), lin.data_ptr(), batch, channels, side, dist.data_ptr(), workspace.data_ptr(), workspace_bytes, _stream(f)
+    )
+    return dist
+
+
+@lpips_layer.register_fake
+def _(f: torch.Tensor, target: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    return f.new_empty((f.shape[0],))
+
+
+@torch.library.custom_op("gance::lpips_layer_backward", mutates_args=(), device_types="cuda")
+def lpips_layer_backward(grad_dist: torch.Tensor, f: torch.Tensor, target: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    """grad_f of `lpips_layer`; the norm and the per-pixel dot product are recomputed. At an all-zero pixel d|f| / df is taken as 0."""
+    f, target, lin, batch, channels, side = _lpips_layer_arguments(f, target, lin)
+    grad_dist = _f32_cuda(grad_dist, (batch,), "grad_dist")
+    grad_f = torch.empty_like(f)
+    hip_lib.lpips_layer_backward_device(
+        grad_dist.data_ptr(), f.data_ptr(), target.data_ptr(), lin.data_ptr(), batch, channels, side, grad_f.data_ptr(), _stream(f)
+    )
+    return grad_f
+
+
+@lpips_layer_backward.register_fake
+def _(grad_dist: torch.Tensor, f: torch.Tensor, target: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    return f.new_empty(f.shape)
+
+
+def _lpips_layer_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    ctx.save_for_backward(*inputs)
+
+
+def _lpips_layer_grad(ctx, grad_dist: torch.Tensor):  # type: ignore[no-untyped-def]
+    f, target, lin = ctx.saved_tensors
+    return lpips_layer_backward(grad_dist, f, target, lin), None, None  # (the target and lin have no gradient)
+
+
+torch.library.register_autograd("gance::lpips_layer", _lpips_layer_grad, setup_context=_lpips_layer_setup)
+
+
+@torch.library.custom_op("gance::lpips_normalize", mutates_args=(), device_types="cuda")
+def lpips_normalize(f: torch.Tensor) -> torch.Tensor:
+    """f / (|f|_2 over the channels + 1e-10) per pixel of f [B, C, S, S]: the target's side of `lpips_layer`. No gradient."""
+    batch, channels, side = _square_activation(f, "f")
+    f = _f32_cuda(f, (batch, channels, side, side), "f")
+    out = torch.empty_like(f)
+    hip_lib.lpips_normalize_device(f.data_ptr(), batch, channels, side, out.data_ptr(), _stream(f))
+    return out
+
+
+@lpips_normalize.register_fake
+def _(f: torch.Tensor) -> torch.Tensor:
+    return f.new_empty(f.shape)

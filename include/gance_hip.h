@@ -661,6 +661,47 @@ int gance_pyramid_distance_forward(const float* d_image, const float* d_target, 
 int gance_pyramid_distance_backward(const float* d_grad_dist, const void* d_workspace, uint64_t workspace_bytes, int32_t batch,
                                     int32_t resolution, float* d_grad_image, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* LPIPS on VGG16: what gance_amd/stylegan2/lpips.py adds to gance_modconv3x3 */
+/* ------------------------------------------------------------------------------------------ */
+/*
+ * Float32, C-contiguous, NCHW, square, on the device, asynchronous on `stream`, no atomics and one fixed summation order, as
+ * above. Refused with GANCE_ERR_INVALID_ARGUMENT before a device is touched: a NULL or misaligned pointer, a batch outside
+ * [1, 65535], a channel count that is not a multiple of 16 in [16, 512], a side outside [4, 1024], an odd side with `pool`, a
+ * resolution that is not a multiple of the side, a workspace below the bound.
+ *
+ * Input: d_image [batch][3][R][R] -> d_out [batch][16][S][S], R = resolution a multiple of S = side: channel c < 3 is
+ * ((the R / S x R / S area mean) - d_shift[c]) / d_scale[c], channels 3 ... 15 are zero (conv1_1 runs with 16 input channels).
+ * The backward reads d_grad [batch][16][S][S] and gives d_grad_image = grad[:, :3] / (scale_c * (R / S)^2) over each cell.
+ */
+int gance_lpips_input_forward(const float* d_image, const float* d_shift, const float* d_scale, int32_t batch, int32_t resolution, int32_t side,
+                              float* d_out, void* stream);
+int gance_lpips_input_backward(const float* d_grad, const float* d_scale, int32_t batch, int32_t resolution, int32_t side, float* d_grad_image,
+                               void* stream);
+/*
+ * y = max(x + bias[c], 0) over [batch][channels][side][side]; with pool != 0 also d_p [batch][channels][side / 2][side / 2], the
+ * maximum of each 2x2 window of y, in the same pass (without pool d_p is not read and may be NULL). The backward gives
+ * grad_x = (y > 0) * (grad_y + grad_p routed to the window's selected element): the largest y of the window, the first in
+ * row-major order among equals. Without pool d_grad_p is not read and may be NULL.
+ */
+int gance_bias_relu_forward(const float* d_x, const float* d_bias, int32_t batch, int32_t channels, int32_t side, int32_t pool, float* d_y,
+                            float* d_p, void* stream);
+int gance_bias_relu_backward(const float* d_grad_y, const float* d_grad_p, const float* d_y, int32_t batch, int32_t channels, int32_t side,
+                             int32_t pool, float* d_grad_x, void* stream);
+/*
+ * The LPIPS head of one tap: per pixel n = |f|_2 over the channels, u = f / (n + 1e-10);
+ * dist[b] = mean over the pixels of sum_c lin[c] * (u_c - target_c)^2, with d_target [batch][channels][side][side] already
+ * normalised (gance_lpips_normalize) and d_lin [channels]. The workspace (8-byte aligned) holds one fp64 partial per block. The
+ * backward recomputes n and gives d_grad_f from d_grad_dist [batch]; at an all-zero pixel the derivative of n is taken as 0.
+ * gance_lpips_normalize writes u.
+ */
+int gance_lpips_layer_workspace_bytes(int32_t batch, int32_t side, uint64_t* workspace_bytes);
+int gance_lpips_layer_forward(const float* d_f, const float* d_target, const float* d_lin, int32_t batch, int32_t channels, int32_t side,
+                              float* d_dist, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int gance_lpips_layer_backward(const float* d_grad_dist, const float* d_f, const float* d_target, const float* d_lin, int32_t batch,
+                               int32_t channels, int32_t side, float* d_grad_f, void* stream);
+int gance_lpips_normalize(const float* d_f, int32_t batch, int32_t channels, int32_t side, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
