@@ -130,6 +130,9 @@ struct ConvArgs {
     // something else holds for a while (a copy kernel of a collective) delays 1/k of its share, not the launch's tail)
     int grid_rounds;
     int xcd_blocking;  // winograd43 kernels, layers with 16 channel tiles: 1 = an XCD's 32 concurrent tiles are 4 pixel tiles x 8 channel tiles (else 2 x 16)
+    // winograd43 kernels (set by the launcher): log2 of m_tiles | log2 of tiles_x << 8 | log2 of tiles_y << 16 when all three are powers
+    // of two -- a tile id is then taken apart with shifts on the scalar unit; -1: some count is not, the kernel divides
+    int tile_shifts;
     // winograd43 kernels: host-visible word a block sets (to 43) when its SIMDs did not each get exactly two of its waves
     // (the pairing the kernel's roles rest on); the launch's output is then invalid and the engine says so on its next call
     int* fault_flag;

@@ -31,7 +31,9 @@
 //
 // Epilogue: output transform A^T M A in registers (the 36 positions of a (channel, tile) pair live in ONE lane),
 // demodulation, noise, bias, leaky ReLU, optional scale by the next layer's style, 16-byte stores (256 contiguous
-// bytes per 16 lanes). The two epilogues of a tile (one per channel tile = per wave of a SIMD) run in the SAME interval between two
+// bytes per 16 lanes; buffer stores: one lane offset per tile, scalar offsets per store), (RGB) the ToRGB channel sum as per-lane FMAs
+// added over the four lane rows by two lane swaps. What a tile costs outside its K loop is the issue time of this code: it is written
+// for few instructions, and scalar fp32 where packed would be shorter (HISTORY.md section D item 21). The two epilogues of a tile (one per channel tile = per wave of a SIMD) run in the SAME interval between two
 // barriers, the first interval of the block's next tile, beside that interval's multiplies: the wave that finishes a tile's K loop
 // first defers its epilogue by one interval (see the stream loop). One after the other, each with its SIMD partner parked at
 // the barrier, they cost 7.5 us per tile, which is 1.9 ms of the 1024^2 layer's 5.4.
@@ -56,6 +58,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kKC = 4;                         // input channels per chunk = one k-step of the 16x16x4 MFMA
@@ -83,7 +86,7 @@ struct Geo43 {
 constexpr int kNBUF = 3;                       // ring slots: chunk G + 2 is issued during k-step G
 // constants of a tile, fetched by LDS-DMA with its first chunk (a global load in the epilogue costs its whole latency once
 // per tile, and the wait behind it would drain the ring): demod | bias | next layer's style (32 each, padded to 64) |
-// noise [16][64] | (RGB) A operands of the ToRGB product [2 channel tiles][4 steps][64 lanes]
+// noise [16][64] | (RGB) the ToRGB coefficients in launch_winograd64_rgb_coef's layout [2 channel tiles][4 r][16 g + colour]
 constexpr int kConstD = 0, kConstB = 64, kConstS = 128, kConstNoise = 192, kConstRgb = kConstNoise + 1024, kConstFloats = kConstRgb + 512;
 constexpr int kStoresPerEpilogue = 16, kRgbStores = 12;
 // (RGB) the ToRGB sums of a wave's sixteen channels, left in LDS for the add with the sums of the wave that holds the OTHER sixteen
@@ -130,6 +133,29 @@ __device__ __forceinline__ void output_transform6(float m0, float m1, float m2, 
     y[1] = fmaf(2.f, d2, d1);
     y[2] = fmaf(4.f, s2, s1);
     y[3] = fmaf(8.f, d2, d1) + m5;
+}
+
+// f / D for 0 <= f < MAX as one 24-bit multiply and a shift: with m = ceil(2^16 / D), floor(f m / 2^16) = floor(f / D) as long as
+// f (m D - 2^16) < 2^16
+template <int D, int MAX>
+__device__ __forceinline__ unsigned div_small(unsigned f) {
+    constexpr unsigned m = (65536 + D - 1) / D;
+    static_assert((unsigned long long)MAX * (m * D - 65536) < 65536 && (unsigned long long)MAX * m < (1ull << 32) && MAX < (1 << 24), "multiplier exact over the range");
+    return __umul24(f, m) >> 16;
+}
+
+// One step of a sum over lane rows: v_permlane32_swap (v_permlane16_swap) exchanges the upper 32 lanes (the odd rows of 16) of `a` with
+// the lower 32 (the even rows) of `b`; a + b then holds the sums of a over the row pairs in the lower lanes (even rows) and those of b in
+// the upper (odd rows). Written as assembly: with the two results of __builtin_amdgcn_permlane32_swap feeding one add, hipcc added the instruction's
+// FIRST result to itself (v_add v0, v12, v12 behind v_permlane32_swap v12, v8). The s_nop covers the two wait states the instruction
+// needs behind a vector write of its operands, which the compiler cannot see into an asm statement to provide.
+template <int ROWS>
+__device__ __forceinline__ float swap_add(float a, float b) {
+    if constexpr (ROWS == 32)
+        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    else
+        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    return a + b;
 }
 
 struct Tile43 {
@@ -199,14 +225,28 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
             const int j = id & 63, sg = id >> 6;  // (64 ids = 4 pixel tiles x 16 channel tiles)
             t.m_tile = 8 * (j >> 5) + (j & 7);
             id = 4 * sg + ((j & 31) >> 3);
+        } else if (p.tile_shifts >= 0) {
+            const int sh = p.tile_shifts & 31;
+            t.m_tile = id & ~(-1 << sh);
+            id >>= sh;
         } else {
             t.m_tile = id % p.m_tiles;
             id /= p.m_tiles;
         }
-        t.x0 = (id % p.tiles_x) * kTW;
-        id /= p.tiles_x;
-        t.y0 = (id % p.tiles_y) * kTH;
-        t.b0 = id / p.tiles_y;
+        // (every shape winograd43_supported admits from this network has power-of-two counts: shifts on the scalar unit; an integer
+        // division is a reciprocal sequence on the vector unit with its result read back by lane, three per decode)
+        if (p.tile_shifts >= 0) {
+            const int shx = (p.tile_shifts >> 8) & 31, shy = (p.tile_shifts >> 16) & 31;
+            t.x0 = (id & ~(-1 << shx)) * kTW;
+            id >>= shx;
+            t.y0 = (id & ~(-1 << shy)) * kTH;
+            t.b0 = id >> shy;
+        } else {
+            t.x0 = (id % p.tiles_x) * kTW;
+            id /= p.tiles_x;
+            t.y0 = (id % p.tiles_y) * kTH;
+            t.b0 = id / p.tiles_y;
+        }
         return t;
     };
 
@@ -228,10 +268,14 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
             } else {
                 int f = (piece - kWPieces) * 64 + lane;
                 if (f >= kPatchF4) f = (piece - kWPieces) * 64;  // (the last piece is a quarter full: the rest re-copy its first float4 into padding)
-                const int q4 = f % (kPW / 4);
-                const int row = (f / (kPW / 4)) % kPH;
-                const int c = f / (kPW / 4 * kPH);
-                piece_voff[r] = ((c * Hp + row) * Wp + 4 * q4) * 4;
+                // f -> (channel, patch row, float4 of the row): this runs after every epilogue, so the two divisions are 24-bit multiplies
+                // and shifts (div_small) and the products 24-bit too (c Hp + row < 2^13, Wp < 2^11); a 32-bit v_mul_lo / v_mul_hi, which
+                // is what `/`, `%` and `*` compile to here, issues at a quarter of the rate
+                const unsigned t = div_small<kPW / 4, 64 * Geo::kPPieces>((unsigned)f);
+                const unsigned q4 = (unsigned)f - __umul24(t, kPW / 4);
+                const unsigned c = div_small<kPH, 64 * Geo::kPPieces>(t);
+                const unsigned row = t - __umul24(c, kPH);
+                piece_voff[r] = (int)((__umul24(__umul24(c, (unsigned)Hp) + row, (unsigned)Wp) + 4 * q4) * 4);
             }
         }
         win_off = kWFloats + g * kPlane + 4 * (pg * kTR + n16 / kTC) * kPW + 4 * (n16 % kTC);
@@ -273,7 +317,7 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(nz_rsrc, (lds_ptr_t)(set + kConstNoise + (wave - 3) * 256), 16,
                                                              ((t.y0 + row) * p.OW + t.x0 + 4 * (lane % kTC)) * 4, t.b0 * p.noise_b_stride * 4, 0, 0);
                 }
-            } else if (RGB) {  // the A operands of the ToRGB product: [b][Cout / 4 steps][64 lanes], steps 8 m_tile .. + 7: two 16-byte pieces
+            } else if (RGB) {  // the ToRGB coefficients (laid out as MFMA A operands): [b][Cout / 4 steps][64 lanes], steps 8 m_tile .. + 7: two 16-byte pieces
                 const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                     (void*)(p.rgb_coef + ((size_t)t.b0 * (p.Cout / 4) + 8 * t.m_tile) * 64), 0, 512 * 4, 0x00020000);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)(set + kConstRgb), 16, lane * 16, 0, 0, 0);
@@ -399,38 +443,42 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
     };
 
     // ---- epilogue of this block's tile i: lane (n16, g) holds channels 4 g + r (r = 0 .. 3) of tile n16 for all 36
-    // positions. Output transform, demodulation, noise, bias, leaky ReLU, (RGB) ToRGB product, stores. ----
+    // positions. Output transform, demodulation, noise, bias, leaky ReLU, (RGB) ToRGB channel sum, stores. ----
     auto epilogue = [&](int i) {
         const Tile43 t = decode(i);
         const float* const set = const0 + (i & 1) * kConstFloats;
         const int lane = fresh_lane();
         const int n16 = lane & 15, g = lane >> 4;
         const int ty4 = 4 * (pg * kTR + n16 / kTC), tx4 = 4 * (n16 % kTC);  // the lane's tile inside the block's pixel tile
-        const int oy0 = t.y0 + ty4, ox0 = t.x0 + tx4;
         const int ct = t.m_tile * 2 + cot;  // 16-channel tile of the layer
-        const int co0 = ct * 16 + 4 * g;
         const f32x4 dm = *reinterpret_cast<const f32x4*>(set + kConstD + cot * 16 + 4 * g);
         const f32x4 bm = *reinterpret_cast<const f32x4*>(set + kConstB + cot * 16 + 4 * g);
         f32x4 sn = f32x4{1.f, 1.f, 1.f, 1.f};
         if (p.s_next != nullptr) sn = *reinterpret_cast<const f32x4*>(set + kConstS + cot * 16 + 4 * g);
-        // (RGB) the layer's ToRGB channel sum over this wave's 16 channels rides on the matrix pipe: k-step r of the product
-        // takes B[k = g][n] = this lane's activation of channel 4 g + r and A[m][k] = style x weight of colour m < 3 (else
-        // 0) for channel 16 ct + 4 k + r, from the table launch_winograd64_rgb_coef prepares
-        f32x4 rgbacc[4][4];
-        if constexpr (RGB) {
-#pragma unroll
-            for (int oy = 0; oy < 4; ++oy)
-#pragma unroll
-                for (int ox = 0; ox < 4; ++ox) rgbacc[oy][ox] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // (RGB) the layer's ToRGB channel sum over this wave's 16 channels, on the vector unit: the lane adds its own four channels
+        // (colour c of channel 16 ct + 4 g + r: style x weight at [cot * 4 + r][16 g + c] of the table launch_winograd64_rgb_coef
+        // prepares as MFMA A operands), 3 colours x 16 pixels = 48 sums; the four lane rows are added behind the channel loop. (As a
+        // 16x16x4 MFMA product with 3 of 16 rows used, the sum held the matrix pipe for 2048 cycles per wave and tile and took 64
+        // accumulators.)
+        float rgb[3][4][4];  // [colour][output row][output column]
+        // The activation stores go through a buffer resource at the tile's origin (its sample, 16-channel tile and pixel tile: scalar
+        // arithmetic): the lane's part of an address is then ONE 32-bit offset for all sixteen stores and the (channel r, row oy) part a
+        // scalar offset, where a flat store wants a 64-bit address per store, built on the vector unit (launch_winograd43_conv checks that
+        // the offsets fit)
+        const int c_step = (int)p.out_c_stride * 4, row_step = p.out_row_stride * 4;  // bytes
+        __amdgpu_buffer_rsrc_t out_rsrc = w_rsrc;
+        int out_voff = 0;
+        if (p.out != nullptr) {
+            out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)t.b0 * p.out_b_stride + (size_t)(ct * 16) * p.out_c_stride +
+                                                                 (size_t)(t.y0 + p.out_y_off) * p.out_row_stride + t.x0 + p.out_x_off),
+                                                         0, 0x7fffffff, 0x00020000);
+            out_voff = 4 * g * c_step + ty4 * row_step + tx4 * 4;
         }
-        float* const out_base = p.out == nullptr ? nullptr
-                                                 : p.out + (size_t)t.b0 * p.out_b_stride + (size_t)co0 * p.out_c_stride +
-                                                       (size_t)(oy0 + p.out_y_off) * p.out_row_stride + ox0 + p.out_x_off;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             __builtin_amdgcn_sched_barrier(0);  // one channel's 36 accumulators at a time (unfenced, hipcc hoists all four and spills)
-            float a_rgb = 0.f;
-            if constexpr (RGB) a_rgb = set[kConstRgb + (cot * 4 + r) * 64 + lane] * 1.4142135623730951f;  // (the leaky ReLU's gain rides on the coefficient)
+            f32x4 a_rgb = f32x4{0.f, 0.f, 0.f, 0.f};  // (R, G, B, unused) coefficients of channel 4 g + r; the leaky ReLU's gain rides on them
+            if constexpr (RGB) a_rgb = *reinterpret_cast<const f32x4*>(set + kConstRgb + (cot * 4 + r) * 64 + 16 * g) * 1.4142135623730951f;
             const float s2 = sn[r] * 1.4142135623730951f;
             float tr[4][6];  // A^T M: [output row][position column]
 #pragma unroll
@@ -446,32 +494,47 @@ __device__ __forceinline__ void winograd43_body(const ConvArgs& p) {
                 output_transform6(tr[oy][0], tr[oy][1], tr[oy][2], tr[oy][3], tr[oy][4], tr[oy][5], yrow);
                 f32x4 nz = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (p.noise != nullptr) nz = *reinterpret_cast<const f32x4*>(set + kConstNoise + (ty4 + oy) * kTW + tx4) * p.noise_strength;
-                f32x4 v = f32x4{yrow[0], yrow[1], yrow[2], yrow[3]} * dm[r] + nz + bm[r];
+                // (element by element: as f32x4 arithmetic this becomes v_pk_mul / v_pk_fma / v_pk_add_f32 on register pairs the compiler first
+                // builds with moves, and beside the partner wave's MFMAs a packed fp32 instruction costs more than the two it replaces)
+                float v[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.2f * v[k]);  // (x sqrt(2): in a_rgb and s2)
+                for (int k = 0; k < 4; ++k) {
+                    v[k] = yrow[k] * dm[r] + nz[k] + bm[r];
+                    v[k] = fmaxf(v[k], 0.2f * v[k]);  // (x sqrt(2): in a_rgb and s2)
+                }
                 if constexpr (RGB) {
 #pragma unroll
-                    for (int ox = 0; ox < 4; ++ox) rgbacc[oy][ox] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_rgb, v[ox], rgbacc[oy][ox], 0, 0, 0);
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int ox = 0; ox < 4; ++ox) rgb[c][oy][ox] = r == 0 ? a_rgb[c] * v[ox] : fmaf(a_rgb[c], v[ox], rgb[c][oy][ox]);
                 }
-                // (the stored activation carries the next layer's style when that layer wants it so; the ToRGB product took the plain one)
-                if (out_base != nullptr) *reinterpret_cast<f32x4*>(out_base + (size_t)r * p.out_c_stride + (size_t)oy * p.out_row_stride) = v * s2;
+                // (the stored activation carries the next layer's style when that layer wants it so; the ToRGB sum took the plain one)
+                if (p.out != nullptr) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[0] * s2, v[1] * s2, v[2] * s2, v[3] * s2}), out_rsrc, out_voff, r * c_step + oy * row_step, 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (RGB) {
-            // Partial image of the block's 32 channels: [Cout / 32][B][3][OH][OW]. Lanes 0 .. 15 of a wave hold (R, G, B, 0)
-            // of their tile's pixels for the wave's 16 channels; the other wave of the SIMD holds the other 16 channels of the
+            // The sums of the four lane rows (channels 4 g + r, g = 0 .. 3) in two steps, each one swap and one add per two registers:
+            // v_permlane32_swap of the sums of output rows (0, 2) / (1, 3) leaves rows 0 / 1 of both in the lower 32 lanes and rows
+            // 2 / 3 in the upper; v_permlane16_swap of those two results leaves lane row g with the complete sums of OUTPUT row g:
+            // 48 -> 24 -> 12 registers, and every lane row holds a different quarter of the tile's sums.
+            float q[3][4];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int ox = 0; ox < 4; ++ox) {
+                    const float h02 = swap_add<32>(rgb[c][0][ox], rgb[c][2][ox]), h13 = swap_add<32>(rgb[c][1][ox], rgb[c][3][ox]);
+                    q[c][ox] = swap_add<16>(h02, h13);
+                }
+            // Partial image of the block's 32 channels: [Cout / 32][B][3][OH][OW]. Lane row g of a wave holds (R, G, B) of output
+            // row g of its tile's pixels for the wave's 16 channels; the other wave of the SIMD holds the other 16 channels of the
             // same pixels. Both epilogues of a tile run between the same two barriers, so neither wave can read the other's sums
-            // here: each leaves its own in its role's buffer, and the role-0 wave adds and stores them behind the next barrier
-            // (finish_rgb). The buffers are written again at the next tile boundary, n >= 4 barriers later (winograd43_supported):
-            // one buffer per role is enough, no second set by tile parity.
-            f32x4* const xchg = reinterpret_cast<f32x4*>(rgb_xchg + cot * kRgbXchgFloats) + (pg * 12) * 16 + n16;
-            if (g == 0) {
+            // here: each leaves its own in its role's buffer (three 16-byte units per lane), and the role-0 wave adds and stores them
+            // behind the next barrier (finish_rgb). The buffers are written again at the next tile boundary, n >= 4 barriers later
+            // (winograd43_supported): one buffer per role is enough, no second set by tile parity.
+            f32x4* const xchg = reinterpret_cast<f32x4*>(rgb_xchg + cot * kRgbXchgFloats) + (pg * 12 + g) * 16 + n16;
 #pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int oy = 0; oy < 4; ++oy) xchg[(c * 4 + oy) * 16] = f32x4{rgbacc[oy][0][c], rgbacc[oy][1][c], rgbacc[oy][2][c], rgbacc[oy][3][c]};
-            }
+            for (int c = 0; c < 3; ++c) xchg[c * 4 * 16] = f32x4{q[c][0], q[c][1], q[c][2], q[c][3]};
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (in LDS before this wave's next barrier)
             rgb_off = (((size_t)t.m_tile * p.B + t.b0) * 3) * p.OH * p.OW + (size_t)t.y0 * p.OW + t.x0;
         }
@@ -701,6 +764,9 @@ hipError_t launch_winograd43_conv(const ConvArgs& args, hipStream_t stream) {
     if (!winograd43_supported(args.Cin, args.Cout, args.H, args.W)) return hipErrorInvalidValue;
     if (rgb ? (!winograd43_rgb_supported(args.Cout) || args.rgb_coef == nullptr || args.rgb_y == nullptr) : (args.epilogue != kEpilogueFull || args.out == nullptr))
         return hipErrorInvalidValue;
+    // (the epilogue's stores address a tile's 16 channels x 16 rows with 32-bit byte offsets from the tile's origin)
+    if (args.out != nullptr && (args.out_c_stride <= 0 || args.out_row_stride <= 0 || 16 * args.out_c_stride + 16 * (long long)args.out_row_stride + 64 >= (1ll << 29)))
+        return hipErrorInvalidValue;
     const bool narrow = args.W % 64 != 0;  // the 32 x 32 pixel geometry
     void (*const kernel)(const ConvArgs) = narrow ? (rgb ? winograd43_w32_rgb_kernel : winograd43_w32_kernel) : (rgb ? winograd43_rgb_kernel : winograd43_kernel);
     const int tw = narrow ? 32 : 64, th = 1024 / tw;
@@ -727,6 +793,9 @@ hipError_t launch_winograd43_conv(const ConvArgs& args, hipStream_t stream) {
     a.m_tiles = a.Cout / kBM;
     a.total_chunks = a.Cin / kKC;
     a.total_tiles = a.m_tiles * a.tiles_x * a.tiles_y * a.B;
+    const auto log2_exact = [](int v) { return v > 0 && (v & (v - 1)) == 0 ? __builtin_ctz((unsigned)v) : -1; };
+    const int shm = log2_exact(a.m_tiles), shx = log2_exact(a.tiles_x), shy = log2_exact(a.tiles_y);
+    a.tile_shifts = shm >= 0 && shx >= 0 && shy >= 0 ? shm | shx << 8 | shy << 16 : -1;  // (-1: the kernel divides)
     if ((a.tiles_x * a.tiles_y * a.B) % 4 != 0) a.xcd_blocking = 0;  // (the 4 x 8 blocking walks pixel tiles four at a time)
     // blocks per CU (ConvArgs::grid_rounds), as long as a block's stream stays long beside its ring prologue (about two k-steps):
     // at least 64 k-steps per block, else fewer, larger blocks (one frame per call: one block per CU as before)
