@@ -36,14 +36,6 @@
 
 #include "kernels.h"
 
-// Timing ablations (GANCE_DEBUG_CONV: 1 no stores, 2 no DMA after the first chunk, 4 no MFMA,
-// 16 per-block phase stamps, 64 no XCD remap) are compiled in only with -DGANCE_CONV_DEBUG=1:
-// their uniform branches cost scalar registers and one branch per store in the product kernel.
-#ifndef GANCE_CONV_DEBUG
-#define GANCE_CONV_DEBUG 0
-#endif
-#define GANCE_DBG(flag) (GANCE_CONV_DEBUG && (p.debug_flags & (flag)))
-
 namespace gance {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -150,9 +142,6 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
     const int l31 = lane & 31;
     const int lh = lane >> 5;
 
-    unsigned long long stamp0 = 0, stamp1 = 0, stamp2 = 0;
-    if (GANCE_DBG(16)) stamp0 = __builtin_amdgcn_s_memrealtime();
-
     const int Hp = p.H + 2, Wp = p.W + 8;
 
     // ---- block id -> tile. XCD-aware remap: the ids handled by one XCD (v % 8) form a contiguous
@@ -165,7 +154,6 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
             const int nwg = p.total_tiles;
             const int q = nwg >> 3, r = nwg & 7, xcd = v & 7;
             id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-            if (GANCE_DBG(64)) id = v;
         }
         g.m_tile = id % p.m_tiles;
         id /= p.m_tiles;
@@ -420,10 +408,9 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (GANCE_DBG(16) && k == 0) stamp1 = __builtin_amdgcn_s_memrealtime();
         float* const cur_buf = buf0 + ring * T::kBufFloats;
         float* const nxt_buf = buf0 + (ring ^ 1) * T::kBufFloats;
-        if (k + 1 < nchunks && !GANCE_DBG(2)) stage(k + 1, nxt_buf);
+        if (k + 1 < nchunks) stage(k + 1, nxt_buf);
         ring ^= 1;
         const float* Wl = cur_buf + aoff;
         const float* Pl = cur_buf + T::kWlRegion;
@@ -455,7 +442,6 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
                 if (TB > 1) dst[j] *= s_lds[stb[j] + ci0 + 2 * kk];
             }
         };
-        if (GANCE_DBG(4)) continue;
         load_a(0, afrag[0], sfrag[0]);
         if (UP) {
 #pragma unroll
@@ -493,7 +479,6 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
         }
     }
 
-    if (GANCE_DBG(16)) stamp2 = __builtin_amdgcn_s_memrealtime();
     // ---- epilogue: demodulate, (noise, bias, leaky relu), store 32 consecutive pixels per reg ----
     // Per-channel constants come out of LDS in one batch (one exposed LDS round trip, not one per
     // element). Stores are MUBUF with the channel plane in the SCALAR offset (register r of a
@@ -544,7 +529,7 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
                 for (int c = 0; c < NCLS; ++c) {
                     // class c = (py, px): valid positions shrink by one where the parity is odd
                     const bool ok = in_batch && oy < p.OH - (UP ? (c >> 1) : 0) && ox < p.OW - (UP ? (c & 1) : 0);
-                    if (!ok || GANCE_DBG(1)) continue;
+                    if (!ok) continue;
                     const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                         (void*)(out_tile + (size_t)c * p.cls_stride + (size_t)(i * 32) * p.out_c_stride), 0, 0x7fffffff,
                         0x00020000);
@@ -621,7 +606,7 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const float y = rgb[k] + p.rgb_bias[k];
-                if (p.rgb_y != nullptr && lh == 0 && ok && !GANCE_DBG(1)) p.rgb_y[((size_t)b0 * 3 + k) * R * R + pix] = y;
+                if (p.rgb_y != nullptr && lh == 0 && ok) p.rgb_y[((size_t)b0 * 3 + k) * R * R + pix] = y;
                 // tf.saturate_cast(x * 127.5 + 128): two roundings (the barrier keeps them apart)
                 float q = y * 127.5f;
                 asm volatile("" : "+v"(q));
@@ -637,7 +622,7 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
             const unsigned word = skew == 0 ? (lo | (hi << 24)) : (skew == 1 ? ((lo >> 8) | (hi << 16)) : ((lo >> 16) | (hi << 8)));
             // (the tile is 64 pixels wide and R % 64 == 0, so a 32-pixel group is whole or absent)
             const bool group_ok = b0 < p.B && oy < p.OH && (ox - l31) + 31 < p.OW;
-            if (p.rgb_u8 != nullptr && lh == 0 && l31 < 24 && group_ok && !GANCE_DBG(1))
+            if (p.rgb_u8 != nullptr && lh == 0 && l31 < 24 && group_ok)
                 reinterpret_cast<unsigned*>(p.rgb_u8 + ((size_t)b0 * R * R + (pix - l31)) * 3)[l31] = word;
         }
     };
@@ -654,19 +639,6 @@ __global__ __launch_bounds__(256, UP ? (RT ? 2 : 3) : 4) void modconv_mfma_kerne
             emit(std::true_type{});
         else
             emit(std::false_type{});
-    }
-    if (GANCE_DBG(16) && tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned int hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned int xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        unsigned long long* dst = p.debug_stamps + (size_t)blockIdx.x * 5;
-        dst[0] = stamp0;
-        dst[1] = stamp1;
-        dst[2] = stamp2;
-        dst[3] = __builtin_amdgcn_s_memrealtime();
-        dst[4] = ((unsigned long long)(xcc & 0xf) << 32) | hwid;
     }
 }
 

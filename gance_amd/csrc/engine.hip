@@ -364,9 +364,8 @@ gance::ConvArgs conv_args(const gance_engine* e, int li, const LayerStep& step, 
     a.slab_stride = o.slab_stride;
     a.cls_stride = o.cls_stride;
     a.x_b_stride = x_b_stride;
-    a.debug_flags = e->tune.debug_conv;
     a.grid_rounds = e->tune.w43_rounds;
-    a.xcd_blocking = e->tune.w43_xcd ? 1 : 0;  // (the launcher drops it where the launch's pixel tiles are not a multiple of four)
+    a.xcd_blocking = 1;  // (the launcher drops it where the launch's pixel tiles are not a multiple of four)
     a.fault_flag = e->ws->fault_flag;
     return a;
 }
@@ -377,12 +376,6 @@ int run_conv(gance_engine* e, int li, const LayerStep& step, const float* x, lon
     const LayerPlan& p = step.p;
     const char* name = step.name;
     gance::ConvArgs a = conv_args(e, li, step, x, x_b_stride, H, W, o, B, rgb, s_next);
-    const int debug_flags = e->tune.debug_conv;
-    static unsigned long long* stamps = nullptr;
-    if (debug_flags & 16) {
-        if (stamps == nullptr) hipMalloc((void**)&stamps, (size_t)5 * 8 * 65536);
-        a.debug_stamps = stamps;
-    }
     double flops = 2.0 * 9 * (double)c.cin * c.cout * H * W * B;
     const double out_elems = (double)B * c.cout * (c.up ? 4.0 * H * W : (double)H * W) * p.nsplit;
     double bytes = 4.0 * ((double)B * c.cin * H * W + out_elems + 9.0 * c.cin * c.cout);
@@ -403,30 +396,6 @@ int run_conv(gance_engine* e, int li, const LayerStep& step, const float* x, lon
         return GANCE_OK;
     }
     GANCE_HIP_CHECK(gance::launch_modconv(p.tile_id, a, p.total_blocks, stream));
-    if ((debug_flags & 16) && p.total_blocks <= 65536) {
-        // timing experiment: dump per-block phase stamps (100 MHz clock) of this launch
-        hipStreamSynchronize(stream);
-        std::vector<unsigned long long> h((size_t)5 * p.total_blocks);
-        hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
-        unsigned long long t_min = ~0ull, t_max = 0;
-        double pro = 0, main_ = 0, epi = 0;
-        for (int i = 0; i < p.total_blocks; ++i) {
-            t_min = std::min(t_min, h[5 * i]);
-            t_max = std::max(t_max, h[5 * i + 3]);
-            pro += (double)(h[5 * i + 1] - h[5 * i]);
-            main_ += (double)(h[5 * i + 2] - h[5 * i + 1]);
-            epi += (double)(h[5 * i + 3] - h[5 * i + 2]);
-        }
-        const double n = p.total_blocks, span = (double)(t_max - t_min) / 100.0;
-        // concurrency: sum of block lifetimes / span / 256 CUs
-        const double life = (pro + main_ + epi) / 100.0;
-        std::fprintf(stderr, "STAMPS %s blocks %d span %.1f us | per block: prologue %.2f us, main %.2f us, epilogue %.2f us | avg resident blocks/CU %.2f\n",
-                     name, p.total_blocks, span, pro / n / 100.0, main_ / n / 100.0, epi / n / 100.0, life / span / 256.0);
-        if (!e->tune.debug_dump.empty() && std::strstr(name, e->tune.debug_dump.c_str())) {
-            for (int i = 0; i < p.total_blocks; ++i)
-                std::fprintf(stderr, "BLK %d %llu %llu %llu %llu %llx\n", i, h[5 * i] - t_min, h[5 * i + 1] - t_min, h[5 * i + 2] - t_min, h[5 * i + 3] - t_min, h[5 * i + 4]);
-        }
-    }
     return GANCE_OK;
 }
 
@@ -1022,7 +991,7 @@ int gance_engine_create(const gance_engine_config* config, const float* host_wei
     for (int i = 0; i < nconv; ++i) {
         const ConvLayerHost& c = e->convs[i];
         for (int B = 1; B <= Bmax; ++B) {
-            const LayerPlan p = plan_layer(c, B, e->tune);
+            const LayerPlan p = plan_layer(c, B);
             if (c.up) e->t_units[i] = std::max(e->t_units[i], p.nsplit * B);
             else if (p.nsplit > 1)
                 slab_max = std::max(slab_max, (size_t)p.nsplit * B * c.cout << (2 * c.res_log2));

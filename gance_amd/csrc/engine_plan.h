@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 #include "../../include/gance_hip.h"
@@ -34,13 +33,10 @@ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 int layer_bm(int cout) { return cout == 16 ? 16 : (cout == 32 ? 32 : (cout == 64 ? 64 : 128)); }  // (16: conv16_mfma.hip, config-e at 1024^2)
 
-// Every GANCE_TUNE_* / GANCE_DEBUG_* value engine.hip reads (the kernel files read their own launch-geometry knobs). read_tuning() is
-// the only place that looks at the environment. All fields are read ONCE PER PROCESS (several size the workspace, which engines
-// share) except `engine`, read each time an engine is created (tests set those between engines of one process).
+// Every GANCE_TUNE_* value the library reads: read_tuning() is the only place in csrc/ that looks at the environment. All fields
+// are read ONCE PER PROCESS (several size the workspace, which engines share) except `engine`, read each time an engine is created
+// (tests set those between engines of one process).
 struct Tuning {
-    // GANCE_TUNE_STRIPS_MIN: smallest input side whose wide transposed conv takes the strip tiles; default 16. Strips pay once the
-    // position grid has several tiles per side; below that the launch is latency-bound and extra blocks only hurt
-    int strips_min = 16;
     // GANCE_TUNE_UPFIR16X = 0: the fused up layers whose input the 64-column strips tile stay in direct form; 1 (default): they run in
     // the pair form (F(2,2) along x) when their input arrives pre-scaled.
     int upfir16x = 1;
@@ -58,12 +54,6 @@ struct Tuning {
     // sweep). Like every Winograd form it is off in engines created with conv_form "direct" (or "winograd": F(2x2,3x3) only).
     int winogemm_min_columns = 64;
     int wino43 = -1;  // GANCE_TUNE_WINO43: overrides the default F(4x4,3x3) resolution limit (wino43_max_res): 0 = off, else a resolution
-    bool fuse_rgb = true;  // GANCE_TUNE_FUSE_RGB = 0: the network's last conv does not absorb its ToRGB (conv_form_of)
-    // GANCE_TUNE_LAST_WINO64 = 0 / 1: ... unless it runs in Winograd form on the 16x16x4 kernel's 32-channel geometry with the ToRGB
-    // product in its epilogue (measured: see DESIGN.md §3)
-    int last_wino64 = 1;
-    int winograd = -1;  // GANCE_TUNE_WINOGRAD = 0 / 1 / 2: overrides the engine flags' Winograd mode (never / where it fills the chip / always)
-    int upfir = -1;  // GANCE_TUNE_UPFIR = 0 / 1 / 2: overrides the engine flags' fused-up mode (never / auto / always)
     // GANCE_TUNE_PRESCALE_UP = 0: a Winograd launch never scales its stores by the next (fused up) layer's style; that kernel then
     // scales in its own K loop
     bool prescale_up = true;
@@ -73,42 +63,27 @@ struct Tuning {
     // thousands), and a CU that something else holds for a while -- the RCCL copy kernels of the frame gather on a multi-GPU job --
     // then delays a quarter of its share instead of the tail of the launch. 1: one block per CU.
     int w43_rounds = 4;
-    // GANCE_TUNE_W43_XCD = 0: the channel tile fastest in the F(4x4,3x3) launches' tile order (round 3's); default: 4 x 8 blocking per
-    // XCD where the layer has 16 channel tiles
-    bool w43_xcd = true;
-    bool graph = true;       // GANCE_TUNE_GRAPH = 0 keeps every host-buffer call eager (host_call)
-    int debug_conv = 0;      // GANCE_DEBUG_CONV: ConvArgs::debug_flags; bit 16 dumps per-block phase stamps of the direct-form launches
-    std::string debug_dump;  // GANCE_DEBUG_DUMP: ... and every block's stamps of the launches whose name contains this
+    bool graph = true;  // GANCE_TUNE_GRAPH = 0 keeps every host-buffer call eager (host_call)
     struct PerEngine {
         int upfir_split = 1;  // GANCE_TUNE_UPFIR_SPLIT: 0 never, 1 (default) where a launch fills the chip without row segments, 2 wherever supported
         int upfir_split_narrow = 1;  // GANCE_TUNE_UPFIR_SPLIT_NARROW: the split form's narrow geometries (inputs 32 and 16 wide) in mode 1 and 2 by the fill rule; 0 never
-        int upfir_split_max_res = 1024;  // GANCE_TUNE_UPFIR_SPLIT_MAXRES: the largest OUTPUT side that takes the split form in mode 1 (measured: DESIGN.md section 3; 512 until the staging went to 16-byte loads)
     } engine;
 };
 
 Tuning read_tuning() {
     Tuning t;
     const auto number = [](const char* name, int unset) { const char* v = std::getenv(name); return v ? std::atoi(v) : unset; };
-    t.strips_min = number("GANCE_TUNE_STRIPS_MIN", 16);
     t.upfir16x = number("GANCE_TUNE_UPFIR16X", 1);
     t.upgemm_min_columns = number("GANCE_TUNE_UPGEMM", 128);
     t.upgemm_buffer_columns = std::max(4096, number("GANCE_TUNE_UPGEMM_COLUMNS", 16384));
     t.winogemm_min_columns = number("GANCE_TUNE_WINOGEMM", 64);
     t.wino43 = number("GANCE_TUNE_WINO43", -1);
-    t.fuse_rgb = number("GANCE_TUNE_FUSE_RGB", 1) != 0;
-    t.last_wino64 = number("GANCE_TUNE_LAST_WINO64", 1);
-    t.winograd = number("GANCE_TUNE_WINOGRAD", -1);
-    t.upfir = number("GANCE_TUNE_UPFIR", -1);
     t.prescale_up = number("GANCE_TUNE_PRESCALE_UP", 1) != 0;
     t.w64_rgb = number("GANCE_TUNE_W64_RGB", 1) != 0;
     const int rounds = number("GANCE_TUNE_W43_ROUNDS", 0);
     t.w43_rounds = rounds > 0 ? rounds : 4;
-    t.w43_xcd = number("GANCE_TUNE_W43_XCD", 1) != 0;
     t.graph = number("GANCE_TUNE_GRAPH", 1) != 0;
-    t.debug_conv = number("GANCE_DEBUG_CONV", 0);
-    if (const char* v = std::getenv("GANCE_DEBUG_DUMP")) t.debug_dump = v;
     t.engine.upfir_split = std::max(0, std::min(2, number("GANCE_TUNE_UPFIR_SPLIT", 1)));
-    t.engine.upfir_split_max_res = number("GANCE_TUNE_UPFIR_SPLIT_MAXRES", 1024);
     t.engine.upfir_split_narrow = number("GANCE_TUNE_UPFIR_SPLIT_NARROW", 1) == 0 ? 0 : 1;
     return t;
 }
@@ -155,10 +130,14 @@ int choose_nsplit(int base_blocks, int chunks) {
     return chunks;
 }
 
-LayerPlan plan_layer(const ConvLayerHost& c, int B, const Tuning& tune) {
+// Smallest input side whose wide transposed conv takes the strip tiles. Strips pay once the position grid has several tiles per
+// side; below that the launch is latency-bound and extra blocks only hurt
+constexpr int kStripsMinSide = 16;
+
+LayerPlan plan_layer(const ConvLayerHost& c, int B) {
     LayerPlan p{};
     const int res = 1 << c.res_log2;
-    const bool strips = c.up && layer_bm(c.cout) == 128 && res / 2 >= tune.strips_min;  // (Tuning::strips_min says why)
+    const bool strips = c.up && layer_bm(c.cout) == 128 && res / 2 >= kStripsMinSide;
     const int grid = c.up ? (strips ? res / 2 : res / 2 + 1) : res;  // the tiled grid
     p.OH = p.OW = c.up ? res / 2 + 1 : res;
     p.tile_id = choose_tile(c.cout, c.up, grid, grid, B);
@@ -273,25 +252,22 @@ struct ConvForm {
 ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool have_y_then) {
     const ConvLayerHost& c = ctx.convs[idx];
     const LayerCaps& caps = ctx.caps[idx];
-    const Tuning& tune = ctx.tune;
     const int res = 1 << c.res_log2, B = ctx.B;
     ConvForm form{};
     // the network's last conv absorbs its ToRGB when one block holds all channels of a pixel
     // (BM = Cout = 32, i.e. the 1024^2 generator of config-f and the 512^2 one of config-e, or BM = Cout = 16, config-e at
     // 1024^2): neither its activation nor the fp32 image is
-    // written, only the uint8 frame (Tuning::fuse_rgb turns this off) -- so not where a debug tap reads that activation:
+    // written, only the uint8 frame -- so not where a debug tap reads that activation:
     // gance_engine_debug_read_activation would return whatever an earlier call left in the buffer
     const auto& tile = gance::kConvTiles[p.tile_id];
-    form.fused_rgb = tune.fuse_rgb && c.res_log2 == ctx.convs.back().res_log2 && ctx.limit() == ctx.num_convs() && p.nsplit == 1 &&
+    form.fused_rgb = c.res_log2 == ctx.convs.back().res_log2 && ctx.limit() == ctx.num_convs() && p.nsplit == 1 &&
                      p.m_tiles == 1 && tile.TB == 1 && (tile.BM == 32 || tile.BM == 16) && have_y_then && ctx.stop_after <= 0;
-    // Winograd form: engine flags choose (DIRECT_CONV = never, FORCE_WINOGRAD = whatever the block count);
-    // Tuning::winograd = 0 / 1 / 2 overrides them for tuning.
-    const int wino_mode = tune.winograd >= 0 ? tune.winograd
-                                             : ((ctx.flags & GANCE_FLAG_DIRECT_CONV) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_WINOGRAD) ? 2 : 1));
+    // Winograd form: the engine flags choose (0 never: DIRECT_CONV, 1 where the launch fills the chip, 2 whatever the block count: FORCE_WINOGRAD)
+    const int wino_mode = (ctx.flags & GANCE_FLAG_DIRECT_CONV) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_WINOGRAD) ? 2 : 1);
     // ... unless the layer runs in Winograd form on the 16x16x4 kernel's 32-channel geometry (or in F(4x4,3x3) form) with the ToRGB
-    // channel sum in its epilogue (Tuning::last_wino64; measured: see DESIGN.md §3): where the launch fills the chip, or Winograd is forced
+    // channel sum in its epilogue (measured: see DESIGN.md §3): where the launch fills the chip, or Winograd is forced
     const long long last_tiles = (long long)(res / 16) * (res / 32) * B;
-    if (form.fused_rgb && tune.last_wino64 != 0 && c.cout == 32 && caps.has[kWino64] && !(ctx.flags & GANCE_FLAG_DIRECT_CONV) &&
+    if (form.fused_rgb && c.cout == 32 && caps.has[kWino64] && !(ctx.flags & GANCE_FLAG_DIRECT_CONV) &&
         (wino_mode == 2 || last_tiles >= ctx.num_cus))
         form.fused_rgb = false;
     // Winograd F(2x2,3x3) form where the layer supports it and the launch fills the chip (one block per CU).
@@ -312,8 +288,8 @@ ConvForm conv_form_of(const PlanContext& ctx, int idx, const LayerPlan& p, bool 
 }
 
 // Whether up layer idx runs as the fused kernel (transposed conv + FIR in one launch): where it is supported and fills
-// the chip; Tuning::upfir = 0 / 1 / 2 overrides the engine flags (never / auto / always). The layer BEFORE it has to know:
-// fed by a 16x16x4 Winograd launch the fused kernel takes its input pre-scaled by its style (plan_call's second pass).
+// the chip; the engine flags choose (0 never: SPLIT_UPFIR, 1 by that rule, 2 wherever supported: FORCE_FUSED_UPFIR). The layer BEFORE
+// it has to know: fed by a 16x16x4 Winograd launch the fused kernel takes its input pre-scaled by its style (plan_call's second pass).
 // split: the split-operand form (launch_upfir_split); fp32: the fp32-MFMA forms (launch_upfir16_fused)
 enum class FusedUp { no, fp32, split };
 FusedUp up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
@@ -321,8 +297,7 @@ FusedUp up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
     const LayerCaps& caps = ctx.caps[idx];
     const Tuning::PerEngine& knobs = ctx.tune.engine;
     const int H = (1 << c.res_log2) / 2, B = ctx.B;
-    const int upfir_mode = ctx.tune.upfir >= 0 ? ctx.tune.upfir
-                                               : ((ctx.flags & GANCE_FLAG_SPLIT_UPFIR) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_FUSED_UPFIR) ? 2 : 1));
+    const int upfir_mode = (ctx.flags & GANCE_FLAG_SPLIT_UPFIR) ? 0 : ((ctx.flags & GANCE_FLAG_FORCE_FUSED_UPFIR) ? 2 : 1);
     if (!c.up || upfir_mode == 0 || !caps.has[kUpfir16]) return FusedUp::no;
     gance::UpFirArgs u{};
     u.Cin = c.cin;
@@ -335,7 +310,7 @@ FusedUp up_runs_fused(const PlanContext& ctx, int idx, gance::UpFirArgs* plan) {
         // segments reach that many blocks: 645 / 895 / 899 / 1080 / 934 / 1055 / 1136 / 1202 frames/s against 614 / 817 / 861 / 960 / - / 980 / - / 1047)
         // (mode 2 forces the wide geometry only; the narrow ones -- 64 / W channel tiles per block -- take the fill rule in both modes)
         const bool narrow = !gance::upfirs_supported(c.cin, c.cout, H, H);
-        if ((knobs.upfir_split == 2 && !narrow) || (u.total_blocks >= ctx.num_cus * 9 / 16 && 2 * H <= knobs.upfir_split_max_res)) {
+        if ((knobs.upfir_split == 2 && !narrow) || u.total_blocks >= ctx.num_cus * 9 / 16) {
             *plan = u;
             return FusedUp::split;
         }
@@ -389,7 +364,7 @@ std::vector<LayerStep> plan_call(const std::vector<ConvLayerHost>& convs, const 
         const ConvLayerHost& c = convs[li];
         const int res = 1 << c.res_log2, H = res / 2;
         LayerStep& s = steps[li];
-        s.p = plan_layer(c, B, tune);
+        s.p = plan_layer(c, B);
         s.last_of_all = c.res_log2 == convs.back().res_log2 && limit == ctx.num_convs();
         s.may_skip_y_store = s.last_of_all && res > 128;
         if (!c.up) {

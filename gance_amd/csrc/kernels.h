@@ -136,8 +136,6 @@ struct ConvArgs {
     // winograd43 kernels: host-visible word a block sets (to 43) when its SIMDs did not each get exactly two of its waves
     // (the pairing the kernel's roles rest on); the launch's output is then invalid and the engine says so on its next call
     int* fault_flag;
-    unsigned long long* debug_stamps;  // [blocks][4] s_memrealtime stamps when debug_flags & 16
-    int debug_flags;       // timing ablations only (GANCE_DEBUG_CONV): 1 no stores, 2 no DMA after chunk 0, 4 no MFMA
 };
 
 struct ConvTileInfo {
@@ -191,8 +189,6 @@ struct UpFirArgs {
     int noise_b_stride;  // 0 (one plane for the batch) or 4 H W (a plane per sample), as in ConvArgs
     int m_tiles, strips, segs, rows_per_seg, total_blocks;  // set by upfir16_plan / upfirs_plan
     int step_rows;                                           // position rows per step (set by the plan: 8, or 16 in the narrow strip geometries of upfir16_fused.hip)
-    int stagger_phases, stagger_ticks;                       // set by the plan: start delay (phase * ticks of 10 ns)
-    int debug_flags;  // timing ablations (GANCE_DEBUG_UPFIR): 1 no stores, 2 no epilogue at all, 4 no MFMA, 8 no DMA after the first chunk
     long long x_b_stride;
     // nullptr, or the style of the NEXT layer, s_next[b * s_stride + co]: folded into the leaky ReLU, i.e. the stored
     // activation is multiplied by it (the Winograd kernel on 16x16x4 MFMAs takes its input pre-scaled)

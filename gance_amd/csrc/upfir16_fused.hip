@@ -58,19 +58,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
-
-// Timing ablations (GANCE_DEBUG_UPFIR: 1 no stores, 2 no epilogue, 4 no MFMA, 8 no DMA after the first chunk, 16 no
-// accumulator dump into the T window, 32 no FIR rows, 64 no barrier per chunk, 128 no operand reads in the K loop, 256 non-temporal
-// output stores) exist only in a -DGANCE_UPFIR16_DEBUG=1 build (Makefile target
-// upfir16dbg): wrong results, and their uniform branches cost scalar registers.
-#ifndef GANCE_UPFIR16_DEBUG
-#define GANCE_UPFIR16_DEBUG 0
-#endif
-#define UPFIR16_DBG (GANCE_UPFIR16_DEBUG ? p.debug_flags : 0)
 
 namespace gance {
 
@@ -268,13 +258,6 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
         for (int r = 0; r < kPiecesPerWave; ++r) stage_piece_n(r, chunk, buf);
     };
 
-    // Staggered start (experiment, off by default: GANCE_TUNE_UPFIR16_STAGGER_US): the two blocks of a CU start together and do
-    // the same work, so they reach their epilogues -- and their flush steps, which are bound by DMA latency -- together. Every
-    // second wave of 256 blocks (the second resident block of each CU in the launch's first round) waits `stagger_ticks` x 10 ns.
-    if (p.stagger_ticks > 0 && ((blockIdx.x >> 8) & 1)) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)p.stagger_ticks) __builtin_amdgcn_s_sleep(32);
-    }
     stage_setup(y_begin + kTH * step_first);
     stage_chunk(0, ring0);
 
@@ -352,7 +335,7 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
 
         for (int k = 0; k < nchunks; ++k) {
             if (!(k == 0 && landed)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(UPFIR16_DBG & 64)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             float* const cur_buf = ring0 + ring * kSlot;
             float* const nxt_buf = ring0 + (ring ^ 1) * kSlot;
@@ -360,8 +343,7 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
             // the next chunk of the stream (this step's k+1, or the first one of the next step): its DMA pieces
             // are issued one at a time BETWEEN the MFMA groups below
             int next_chunk = -1;
-            if (UPFIR16_DBG & 8) {
-            } else if (k + 1 < nchunks) {
+            if (k + 1 < nchunks) {
                 next_chunk = k + 1;
             } else if (si + 1 < step_last) {
                 stage_setup(y0 + kTH);
@@ -369,10 +351,6 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
             }
             ring ^= 1;
 
-            if (UPFIR16_DBG & 4) {
-                if (next_chunk >= 0) stage_chunk(next_chunk, nxt_buf);
-                continue;
-            }
             if constexpr (!kFlush && WX) {
                 // Pair form. A chunk = two k-steps x two groups of two pair tiles (position row w + 4 rw, pair tiles pt = 0, 1: 64 columns)
                 // = 30 MFMAs each. Fragments of a pair tile and row tap dy: e0 - e1, e1, e1 - e2, e2 with (e0, e1, e2) = input columns
@@ -517,12 +495,10 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
                 float a[2][9], bf[2][4][4], bh[kHaloTiles][4];
                 const unsigned a_lb = lds_a + ring_bytes, b_lb = lds_b + ring_bytes;
                 auto load_a = [&](int jj, float(&dst)[9]) {
-                    if (UPFIR16_DBG & 128) return;
 #pragma unroll
                     for (int t = 0; t < 9; ++t) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(dst[t]) : "v"(a_lb), "i"((t * kKC + 4 * jj) * kBM * 4));
                 };
                 auto load_b = [&](int grp, float(&dst)[4][4]) {  // group grp = (k-step grp / kGroups, tiles 4 (grp % kGroups) .. + 3)
-                    if (UPFIR16_DBG & 128) return;
 #pragma unroll
                     for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -686,7 +662,6 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
         lds_barrier();
 
         // ---- epilogue: 4 RW passes (four position rows of the step x channel group) ----
-        if (UPFIR16_DBG & 2) return;
         // per-lane roles (re-derived here: see fresh_lane)
         const int elane = fresh_lane();
         const int en16 = elane & 15, eq4 = elane >> 4;
@@ -700,7 +675,7 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
         const int rg = elane / kCG;
         // (per lane: channel plane, the row group's first row, column group)
         const int o_voff = (int)((fc * oplane + (long long)(kFR * rg) * OWp + 4 * cg) * 4);
-        const bool emit = si >= 0 && !(UPFIR16_DBG & 32);
+        const bool emit = si >= 0;
         // Noise of the step's output rows [8 RW][2 kSW] (the same for every channel): by DMA into the part of ring slot 1 the T
         // window leaves free, so that it costs no registers and no vector load sits behind the stores (the single vmcnt counter: a
         // load behind a store waits for it). A lane's 16 bytes: float f = 256 piece + 4 lane of the region; rows above / below the
@@ -744,7 +719,7 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
                         dst[kTW + 2] = m[6][g] - m[7][g];
                         dst[kTW + 3] = m[9][g];
                     }
-                } else if (!(UPFIR16_DBG & 16)) {
+                } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -800,10 +775,7 @@ __device__ __forceinline__ void upfir16_body(const UpFirArgs& p) {
                             if (has_noise) v += ns2 * *reinterpret_cast<const f32x4*>(nz_lds + (kPassRows * rw + rr) * (2 * kSW) + 4 * cg);
 #pragma unroll
                             for (int o = 0; o < 4; ++o) v[o] = fmaf(lr6, v[o], lr4 * __builtin_fabsf(v[o]));
-                            if (UPFIR16_DBG & 256)  // (experiment: non-temporal stores)
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, o_voff, o_soff + r * OWp * 4, 2);
-                            else if (!(UPFIR16_DBG & 1) || v[0] == 12345.f)
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, o_voff, o_soff + r * OWp * 4, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, o_voff, o_soff + r * OWp * 4, 0);
                         }
                     }
                 }
@@ -890,11 +862,6 @@ void upfir16_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* a) {
     a->segs = segs;
     a->rows_per_seg = H / segs;
     a->total_blocks = base * segs;
-    static const int env_stagger_us = [] { const char* v = std::getenv("GANCE_TUNE_UPFIR16_STAGGER_US"); return v ? std::atoi(v) : 0; }();
-    a->stagger_phases = 1;
-    a->stagger_ticks = env_stagger_us * 100;  // (s_memrealtime ticks of 10 ns)
-    static const int env_debug = [] { const char* v = std::getenv("GANCE_DEBUG_UPFIR"); return v ? std::atoi(v) : 0; }();
-    a->debug_flags = env_debug;
 }
 
 // (plain kernels around the templated body: see winograd64_conv.hip on kernel templates and the host pass)

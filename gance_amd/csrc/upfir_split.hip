@@ -747,9 +747,6 @@ void upfirs_arrange_weights(const float* w_in, int cin, int cout, const int* up_
 
 void upfirs_plan(int B, int cout, int H, int W, int num_cus, UpFirArgs* a) {
     a->step_rows = kTH;
-    a->stagger_phases = 1;
-    a->stagger_ticks = 0;
-    a->debug_flags = 0;
     if (W < kSW) {  // (a narrow strip: blocks of 64 / W channel tiles; an image of two or four steps is never cut into segments)
         a->m_tiles = cout / (kBM * (kSW / W));
         a->strips = 1;

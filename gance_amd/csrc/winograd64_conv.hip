@@ -29,17 +29,10 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
 
-// Timing ablations (GANCE_DEBUG_W64: 2 no DMA after the prologue, 4 no MFMA, 32 no input transform, 64 no per-k-step wait
-// and barrier) exist only in a -DGANCE_W64_DEBUG=1 build.
-#ifndef GANCE_W64_DEBUG
-#define GANCE_W64_DEBUG 0
-#endif
-#define W64_DBG (GANCE_W64_DEBUG ? p.debug_flags : 0)
 // Compile-time epilogue ablation (results are wrong): 1 no stores (make w64ablate).
 #ifndef GANCE_W64_ABLATE
 #define GANCE_W64_ABLATE 0
@@ -570,7 +563,6 @@ __device__ __forceinline__ void winograd64_body(const ConvArgs& p) {
                 // barrier, so the matrix pipe works while the wave does the staging bookkeeping (scalar, branchy) and waits
                 // for its siblings.
                 auto mfma_positions = [&](int first, int last) {
-                    if (W64_DBG & 4) return;
 #pragma unroll
                     for (int pos = first; pos < last; ++pos)
 #pragma unroll
@@ -589,7 +581,7 @@ __device__ __forceinline__ void winograd64_body(const ConvArgs& p) {
                 // younger chunks stay in flight -- and the block synchronises. Behind the barrier both are visible to every
                 // wave, and the slots the pair's DMA pieces go to (chunks q+5 and q+6 into the slots of q-1 and q) were last
                 // read in k-steps q-2 and q-1, which every wave has left.
-                if (half == 0 && !(W64_DBG & 64)) {
+                if (half == 0) {
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kNBUF - 4) * G::kPiecesPerWave) : "memory");
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
@@ -598,11 +590,9 @@ __device__ __forceinline__ void winograd64_body(const ConvArgs& p) {
                 load_window(next_off, style_here);
 #pragma unroll
                 for (int pos = 0; pos < 16; ++pos) afrag[(half + 1) & 1][pos] = *reinterpret_cast<const afrag_t*>(Un + aoff + pos * kKC * kBM);
-                if (!(W64_DBG & 32)) transform(V[(half + 1) & 1]);
-                if (!(W64_DBG & 2)) {
+                transform(V[(half + 1) & 1]);
 #pragma unroll
-                    for (int r = 0; r < kPiecesPerWave; ++r) stage_piece(r);
-                }
+                for (int r = 0; r < kPiecesPerWave; ++r) stage_piece(r);
                 mfma_positions(4, 16);
                 // weave: 48 x (1 MFMA, then what fits in its shadow): the LDS reads first (16 weight fragments + 9 per window:
                 // they feed everything else), the 40 transform instructions per window and the DMA issues spread over the rest
@@ -682,8 +672,6 @@ static hipError_t launch_variant(void (*kernel)(const ConvArgs), const ConvArgs&
         &resident_blocks);
     if (e != hipSuccess) return e;
     ConvArgs a = args;
-    static const int env_debug = [] { const char* v = std::getenv("GANCE_DEBUG_W64"); return v ? std::atoi(v) : 0; }();
-    a.debug_flags = env_debug;
     a.tiles_x = a.W / kTW;
     a.tiles_y = a.H / G::kTH;
     a.m_tiles = a.Cout / G::kBM;

@@ -1,22 +1,24 @@
-"""Dev check: Winograd conv path against the direct path, same engine inputs (fp32 image and uint8 frames)."""
-import os, subprocess, sys
+"""Dev check: a Winograd conv form against the direct form, same engine inputs (fp32 image and uint8 frames).
+
+    python tools/gpu_debug_wino.py [winograd|winograd43|auto]     (conv_form of hip_lib.Engine; default winograd43)
+"""
+import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 
-if len(sys.argv) > 1:
-    from gance_amd import hip_lib
-    from gance_amd.stylegan2 import spec
-    variables = spec.make_random_variables(1024, seed=0, perturb=True)
-    engine = hip_lib.Engine(variables, 1024, max_batch=4, device=0)
-    z = np.random.RandomState(1).randn(4, 512).astype(np.float32)
+from gance_amd import hip_lib
+from gance_amd.stylegan2 import spec
+
+form = sys.argv[1] if len(sys.argv) > 1 else "winograd43"
+variables = spec.make_random_variables(1024, seed=0, perturb=True)
+z = np.random.RandomState(1).randn(4, 512).astype(np.float32)
+frames = {}
+for conv_form in ("direct", form):
+    engine = hip_lib.Engine(variables, 1024, max_batch=4, device=0, conv_form=conv_form)
     u8, f32 = engine.synthesize_z(z, want_float=True)
-    np.save(sys.argv[1], f32)
-    np.save(sys.argv[1] + ".u8.npy", u8)
-    sys.exit(0)
-for flag in ("0", "2"):
-    subprocess.run([sys.executable, __file__, f"/tmp/wino_{flag}.npy"], env=dict(os.environ, GANCE_TUNE_WINOGRAD=flag), check=True)
-a, b = np.load("/tmp/wino_0.npy"), np.load("/tmp/wino_2.npy")
-print("image range", a.min(), a.max(), "max abs diff direct vs winograd", np.abs(a - b).max(), "rms", np.sqrt(np.mean((a - b) ** 2)))
-ua, ub = np.load("/tmp/wino_0.npy.u8.npy"), np.load("/tmp/wino_2.npy.u8.npy")
+    frames[conv_form] = (np.array(u8), np.array(f32))
+    engine.close()
+(ua, a), (ub, b) = frames["direct"], frames[form]
+print("image range", a.min(), a.max(), f"max abs diff direct vs {form}", np.abs(a - b).max(), "rms", np.sqrt(np.mean((a - b) ** 2)))
 print("u8 differing", int((ua != ub).sum()), "of", ua.size, "max", int(np.abs(ua.astype(int) - ub.astype(int)).max()))
