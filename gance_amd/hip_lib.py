@@ -397,6 +397,16 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_conv3x3_form": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    "gance_conv3x3_workspace_bytes": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_conv3x3_forward": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
 }
 
 # entries added without an ABI bump: an older build of the same ABI (GANCE_HIP_LIBRARY, e.g. the A/B tools'
@@ -412,7 +422,8 @@ ADDED_WITHIN_ABI = {
     "gance_noise_regularizer_backward", "gance_pyramid_distance_workspace_bytes", "gance_pyramid_distance_forward",
     "gance_pyramid_distance_backward", "gance_png_encode_lz_bounds", "gance_png_encode_lz_u8", "gance_lpips_input_forward",
     "gance_lpips_input_backward", "gance_bias_relu_forward", "gance_bias_relu_backward", "gance_lpips_layer_workspace_bytes",
-    "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize",
+    "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize", "gance_conv3x3_form",
+    "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1303,6 +1314,39 @@ def lpips_normalize_device(d_f: int, batch: int, channels: int, side: int, d_out
     """out = f / (|f|_2 over the channels + 1e-10) per pixel (gance_lpips_normalize)."""
     lib = load_library()
     _value_error_on_invalid_argument(lib, lib.gance_lpips_normalize(d_f, batch, channels, side, d_out, stream or None))
+
+
+# ---- the plain 3x3 convolution (csrc/conv3x3.hip): raw device pointers, asynchronous on `stream` ----
+
+
+def conv3x3_form(cin: int, cout: int, side: int) -> int:
+    """The kernel form `conv3x3_forward_device` launches for a shape (include/gance_hip.h); a host-side function of the
+    shape alone, never of the batch.
+    :raises ValueError: a shape the kernels refuse."""
+    lib = load_library()
+    form = ctypes.c_int32()
+    _value_error_on_invalid_argument(lib, lib.gance_conv3x3_form(cin, cout, side, ctypes.byref(form)))
+    return int(form.value)
+
+
+def conv3x3_workspace_bytes(batch: int, cin: int, cout: int, side: int) -> int:
+    """Workspace of one `conv3x3_forward_device` call (never 0).
+    :raises ValueError: a shape the kernels refuse (include/gance_hip.h)."""
+    lib = load_library()
+    size = ctypes.c_uint64()
+    _value_error_on_invalid_argument(lib, lib.gance_conv3x3_workspace_bytes(batch, cin, cout, side, ctypes.byref(size)))
+    return int(size.value)
+
+
+def conv3x3_forward_device(  # pylint: disable=too-many-arguments
+    d_x: int, d_weight: int, batch: int, cin: int, cout: int, height: int, width: int, d_y: int, d_workspace: int, workspace_bytes: int,
+    stream: int = 0,
+) -> None:
+    """y = conv3x3(x, weight), zero padding 1, stride 1, weight [3, 3, cin, cout] (gance_conv3x3_forward)."""
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_conv3x3_forward(d_x, d_weight, batch, cin, cout, height, width, d_y, d_workspace, workspace_bytes, stream or None)
+    )
 
 
 JPEG_STATUS_REASONS = {0: "ok", 1: "truncated data", 2: "invalid Huffman code", 3: "restart marker mismatch"}

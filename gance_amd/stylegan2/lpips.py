@@ -10,7 +10,8 @@ the publications, so parity with an upstream run is unpinned (DESIGN.md section 
     distance = sum_l mean over the pixels of sum_c lin_l[c] * (u_c(image) - u_c(target))^2
 
 `VGG16Lpips` is a `projector.Distance`: `Projector(distance=VGG16Lpips(load_lpips_weights(path)))`. The convolutions run
-through torch.ops.gance.modconv3x3 with unit style and demodulation; the rest is csrc/lpips.hip.
+through torch.ops.gance.modconv3x3 with unit style and demodulation or, with `convolution="conv3x3"`, through the plain
+convolution torch.ops.gance.conv3x3 (csrc/conv3x3.hip); the rest is csrc/lpips.hip.
 """
 
 from pathlib import Path
@@ -35,6 +36,7 @@ TAP_CHANNELS = tuple(CONV_LAYERS[index][2] for index in TAP_LAYERS)
 DEFAULT_SHIFT = (-0.030, -0.088, -0.188)
 DEFAULT_SCALE = (0.458, 0.448, 0.450)
 DEFAULT_SIDE = 256  # upstream's projector judges at 256^2
+CONVOLUTIONS = ("modconv3x3", "conv3x3")  # the op the thirteen convolutions run through
 # torchvision's vgg16().features: the Sequential indices of the thirteen Conv2d
 TORCHVISION_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
 
@@ -180,12 +182,18 @@ class VGG16Lpips:
     is handed over (the projector hands one tensor for every step of a `start`).
     """
 
-    def __init__(self, weights: LpipsWeights, side: int = DEFAULT_SIDE, device: Optional[Union[int, torch.device]] = None) -> None:
+    def __init__(
+        self, weights: LpipsWeights, side: int = DEFAULT_SIDE, device: Optional[Union[int, torch.device]] = None, convolution: str = "modconv3x3"
+    ) -> None:
         """
-        :raises ValueError: bad `side` or weights, before a device is touched.
+        :param convolution: "modconv3x3" (gance::modconv3x3 with unit style and demodulation) or "conv3x3" (gance::conv3x3).
+        :raises ValueError: bad `side`, `convolution` or weights, before a device is touched.
         :raises RuntimeError: no GPU (there is no CPU path).
         """
         self.side = check_side(side)
+        if convolution not in CONVOLUTIONS:
+            raise ValueError(f"`convolution` must be one of {list(CONVOLUTIONS)}, got {convolution!r}")
+        self.convolution = convolution
         weights = validate_lpips_weights(weights)
         if not torch.cuda.is_available():
             raise RuntimeError("VGG16Lpips needs an MI355X: there is no CPU fallback")
@@ -197,6 +205,8 @@ class VGG16Lpips:
             if cin < torch_ops.LPIPS_INPUT_CHANNELS:  # conv1_1: the input op's zero channels meet zero weights
                 weight = np.concatenate([weight, np.zeros((3, 3, torch_ops.LPIPS_INPUT_CHANNELS - cin, weight.shape[3]), dtype=np.float32)], axis=2)
             self._convs.append((torch.from_numpy(np.ascontiguousarray(weight)).to(self.device), torch.from_numpy(bias).to(self.device)))
+        # the images under which gance::conv3x3 is its own input gradient, built once
+        self._transposed = [torch_ops.conv3x3_transposed_weight(weight) for weight, _ in self._convs] if convolution == "conv3x3" else []
         self._lins = [torch.from_numpy(lin).to(self.device) for lin in weights.lins]
         self._shift, self._scale = torch.from_numpy(weights.shift).to(self.device), torch.from_numpy(weights.scale).to(self.device)
         self._ones: dict = {}
@@ -230,7 +240,10 @@ class VGG16Lpips:
         x = torch.ops.gance.lpips_input(images, self._shift, self._scale, self.judged_side(int(images.shape[2])) if side is None else side)
         taps = []
         for index, (weight, bias) in enumerate(self._convs):
-            x = torch.ops.gance.modconv3x3(x, self._unit(batch, int(weight.shape[2])), self._unit(batch, int(weight.shape[3])), weight, False)
+            if self.convolution == "conv3x3":
+                x = torch.ops.gance.conv3x3(x, weight, self._transposed[index])
+            else:
+                x = torch.ops.gance.modconv3x3(x, self._unit(batch, int(weight.shape[2])), self._unit(batch, int(weight.shape[3])), weight, False)
             if index in POOL_LAYERS:
                 y, x = torch.ops.gance.bias_relu_pool(x, bias)
             else:

@@ -16,6 +16,8 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.noise_bias_lrelu(x, noise, strength, bias)     [B, C, S, S] f32 -> the same                          differentiable
     torch.ops.gance.torgb_skip(x, style, weight, bias, y_prev)     [B, Cin, S, S] f32 -> [B, 3, S, S] f32                differentiable
     (each with a `_backward` op; gradients reach x, style, demod, y_prev and the noise planes: gance_amd/stylegan2/differentiable.py is the user)
+    torch.ops.gance.conv3x3(x, weight, weight_transposed)          [B, Cin, S, S] f32 -> [B, Cout, S, S] f32             differentiable in x
+    (the plain 3x3 convolution, csrc/conv3x3.hip; `conv3x3_transposed_weight` builds the third argument)
     torch.ops.gance.noise_regularizer(noise)                       [B, 1, S, S] f32 -> [B] f32                           differentiable
     torch.ops.gance.pyramid_distance(image, target)                [B, 3, R, R], [B, 3, min(R, 256), ...] f32 -> [B]     differentiable
     (projection's losses: gance_amd/stylegan2/projector.py is the user)
@@ -806,6 +808,70 @@ def _pyramid_distance_grad(ctx, grad_dist: torch.Tensor):  # type: ignore[no-unt
 
 
 torch.library.register_autograd("gance::pyramid_distance", _pyramid_distance_grad, setup_context=_pyramid_distance_setup)
+
+
+# ---- the plain 3x3 convolution (csrc/conv3x3.hip): no style, no demodulation, no weight gradient ----
+
+
+def conv3x3_transposed_weight(weight: torch.Tensor) -> torch.Tensor:
+    """wt[ty, tx, o, i] = w[2 - ty, 2 - tx, i, o] of a weight [3, 3, Cin, Cout]: the image under which `conv3x3` is its own
+    input gradient (and the weight's own image again: an involution)."""
+    _modconv_weight_shape(weight)
+    return weight.flip(0, 1).transpose(2, 3).contiguous()
+
+
+def _conv3x3_f32_cuda(tensor: torch.Tensor, shape: Tuple[int, ...], name: str) -> None:
+    """:raises ValueError: a tensor the kernel does not take as it is (nothing is copied or converted on the way in)."""
+    if not tensor.is_cuda:
+        raise ValueError(f"gance::conv3x3 runs on an MI355X only: `{name}` is on {tensor.device} (there is no CPU fallback)")
+    if tensor.dtype != torch.float32:
+        raise ValueError(f"`{name}` must be torch.float32, got {tensor.dtype}")
+    if tuple(tensor.shape) != tuple(shape):
+        raise ValueError(f"`{name}` must be {list(shape)}, got {list(tensor.shape)}")
+    if not tensor.is_contiguous():
+        raise ValueError(f"`{name}` must be contiguous")
+
+
+# (registered for every device, so that a CPU tensor reaches the ValueError below instead of the dispatcher's NotImplementedError)
+@torch.library.custom_op("gance::conv3x3", mutates_args=())
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, weight_transposed: torch.Tensor) -> torch.Tensor:
+    """
+    The 3x3 convolution with zero padding 1 and stride 1 (cross-correlation) of x [B, Cin, S, S] with weight [3, 3, Cin, Cout];
+    `weight_transposed` [3, 3, Cout, Cin] = `conv3x3_transposed_weight(weight)` is read by the backward only: grad_x =
+    conv3x3(grad_y, weight_transposed, weight). The weights receive no gradient.
+    """
+    batch, cin, height, width = _activation_shape(x)
+    cout = _modconv_weight_shape(weight)[1]
+    if height != width:
+        raise ValueError(f"`x` must be square, got {list(x.shape)}")
+    _conv3x3_f32_cuda(x, (batch, cin, height, width), "x")
+    _conv3x3_f32_cuda(weight, (3, 3, cin, cout), "weight")
+    _conv3x3_f32_cuda(weight_transposed, (3, 3, cout, cin), "weight_transposed")
+    workspace_bytes = hip_lib.conv3x3_workspace_bytes(batch, cin, cout, height)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=x.device)
+    y = torch.empty((batch, cout, height, width), dtype=torch.float32, device=x.device)
+    hip_lib.conv3x3_forward_device(
+        x.data_ptr(), weight.data_ptr(), batch, cin, cout, height, width, y.data_ptr(), workspace.data_ptr(), workspace_bytes, _stream(x)
+    )
+    return y
+
+
+@conv3x3.register_fake
+def _(x: torch.Tensor, weight: torch.Tensor, weight_transposed: torch.Tensor) -> torch.Tensor:
+    return x.new_empty((x.shape[0], weight.shape[3], x.shape[2], x.shape[3]))
+
+
+def _conv3x3_setup(ctx, inputs, output) -> None:  # type: ignore[no-untyped-def]
+    _, weight, weight_transposed = inputs
+    ctx.save_for_backward(weight, weight_transposed)
+
+
+def _conv3x3_grad(ctx, grad_y: torch.Tensor):  # type: ignore[no-untyped-def]
+    weight, weight_transposed = ctx.saved_tensors
+    return conv3x3(grad_y.contiguous(), weight_transposed, weight), None, None
+
+
+torch.library.register_autograd("gance::conv3x3", _conv3x3_grad, setup_context=_conv3x3_setup)
 
 
 # ---- LPIPS on VGG16 (csrc/lpips.hip; the convolutions are gance::modconv3x3 with unit style and demodulation) ----

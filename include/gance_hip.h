@@ -702,6 +702,29 @@ int gance_lpips_layer_backward(const float* d_grad_dist, const float* d_f, const
                                int32_t channels, int32_t side, float* d_grad_f, void* stream);
 int gance_lpips_normalize(const float* d_f, int32_t batch, int32_t channels, int32_t side, float* d_out, void* stream);
 
+/*
+ * The plain 3x3 convolution of gance::conv3x3 (csrc/conv3x3.hip), which VGG16Lpips runs on with
+ * convolution="conv3x3": y[b][o][oy][ox] = sum_{ty, tx, i} w[ty][tx][i][o] * x[b][i][oy + ty - 1][ox + tx - 1], zero padding 1,
+ * stride 1 (cross-correlation: gance_modconv3x3_forward with up = 0, unit style and unit demodulation). d_x [batch][cin][S][S],
+ * d_weight [3][3][cin][cout], d_y [batch][cout][S][S]; exact fp32 on v_mfma_f32_16x16x4_f32, a chunk of 16 contracted channels
+ * summed on its own and then added to the total. No style, no demodulation, no weight gradient. The input gradient is the
+ * same entry point applied to grad_y and wt[ty][tx][o][i] = w[2 - ty][2 - tx][i][o].
+ *
+ * Refused as above: a NULL or misaligned pointer, channel counts that are not multiples of 16 in [16, 512], a side outside
+ * [4, 1024], height != width, a batch outside [1, 65535], a workspace below gance_conv3x3_workspace_bytes (never 0).
+ *
+ * gance_conv3x3_form (host only, no device): the kernel form launched for a shape, a function of (cin, cout, side) and never of
+ * the batch, so a sample's bits do not depend on the batch it arrives in. form = 8 * t + s:
+ *   t = 0, 1, 2: a block computes 8 x 16 pixels x 16, 32, 64 output channels (cout 16; 32 or 48; 64 and above);
+ *   s = log2(splits): the chunks of contracted channels are divided over 2^s blocks whose partial sums go to the workspace and
+ *   are added in rising order by a second launch. splits is the largest power of two that is at most 16 for a side up to 16,
+ *   4 up to 32, 2 up to 64 and 1 above, and at most cin / 32 (no run of fewer than two chunks).
+ */
+int gance_conv3x3_form(int32_t cin, int32_t cout, int32_t side, int32_t* form);
+int gance_conv3x3_workspace_bytes(int32_t batch, int32_t cin, int32_t cout, int32_t side, uint64_t* workspace_bytes);
+int gance_conv3x3_forward(const float* d_x, const float* d_weight, int32_t batch, int32_t cin, int32_t cout, int32_t height, int32_t width,
+                          float* d_y, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,13 +4,15 @@ random-init config-f 1024^2 network whose noise strengths are set to 0.1:
 
 * ms per whole `Projector.step()` at 1024^2, one and four frames, with (a) the built-in `pyramid_distance`, (b) `VGG16Lpips`
   (gance::modconv3x3 convolutions, csrc/lpips.hip for the rest), (c) the same LPIPS composed of plain torch ops on the same
-  device (conv2d, relu, max_pool2d, avg_pool2d, vector_norm);
-* forward + backward of the distance alone (images [B, 3, 1024, 1024] -> [B] -> image gradient) for (b) and (c).
+  device (conv2d, relu, max_pool2d, avg_pool2d, vector_norm), (d) `VGG16Lpips(convolution="conv3x3")` (gance::conv3x3,
+  csrc/conv3x3.hip), the leg `hip-conv3x3`;
+* forward + backward of the distance alone (images [B, 3, 1024, 1024] -> [B] -> image gradient) for (b), (c) and (d).
 
 Every measurement is a child process of its own under `timeout -k 10`; the first one that fails ends the run. A child warms
 up, then runs three rounds that alternate its legs, every leg timed with device events; medians are reported with every
-round beside them. No bar is set. `--measure distance --batch 1 --legs hip` alone is the run to put under a kernel trace
-(`timeout -k 10 400 rocprofv3 --kernel-trace --stats -- python tools/gpu_lpips_rate.py --measure distance --batch 1 --legs hip`).
+round beside them. No bar is set. `--measure distance --batch 1 --legs hip` (or `hip-conv3x3`) alone is the run to put under a
+kernel trace
+(`timeout -k 10 400 rocprofv3 --kernel-trace --stats -- python tools/gpu_lpips_rate.py --measure distance --batch 1 --legs hip-conv3x3`).
 """
 
 import argparse
@@ -36,6 +38,7 @@ BATCHES = (1, 4)
 ROUNDS = 3
 NUM_STEPS = 1000
 CHILD_SECONDS = 600
+LEGS = ("hip", "torch", "hip-conv3x3")  # the LPIPS legs, alternated in this order in every round
 
 
 class TorchLpips:
@@ -98,7 +101,12 @@ def alternate(legs: Dict[str, Callable[[], object]], calls: int) -> dict:
 
 def make_distances(names: List[str]) -> Dict[str, object]:
     weights = lpips.random_lpips_weights(0)
-    makers = {"pyramid": lambda: None, "hip": lambda: lpips.VGG16Lpips(weights), "torch": lambda: TorchLpips(weights)}
+    makers = {
+        "pyramid": lambda: None,
+        "hip": lambda: lpips.VGG16Lpips(weights),
+        "torch": lambda: TorchLpips(weights),
+        "hip-conv3x3": lambda: lpips.VGG16Lpips(weights, convolution="conv3x3"),
+    }
     return {name: makers[name]() for name in names}
 
 
@@ -151,21 +159,26 @@ def child(measure: str, batch: int, names: List[str]) -> dict:
 
 def main() -> None:
     parser = argparse.ArgumentParser(description=__doc__)
-    parser.add_argument("--out", type=Path, default=REPO_ROOT / "profiles" / "lpips_rate.json")
+    parser.add_argument("--out", type=Path, default=REPO_ROOT / "profiles" / "lpips_conv3x3_rate.json")
     parser.add_argument("--measure", choices=("steps", "distance"), help="run one measurement in this process and print its JSON line")
     parser.add_argument("--batch", type=int, default=1)
-    parser.add_argument("--legs", default="", help="comma-separated: pyramid (steps only), hip, torch")
+    parser.add_argument("--legs", default="", help="comma-separated: pyramid (steps only), hip, torch, hip-conv3x3")
     args = parser.parse_args()
     if args.measure is not None:
-        names = args.legs.split(",") if args.legs else (["pyramid", "hip", "torch"] if args.measure == "steps" else ["hip", "torch"])
+        names = args.legs.split(",") if args.legs else (["pyramid"] if args.measure == "steps" else []) + list(LEGS)
         print(json.dumps((measure_steps if args.measure == "steps" else measure_distance)(args.batch, names)))
         return
     result = {
         "network": "random init, perturb=True, config-f, 1024^2, noise strengths 0.1; LPIPS weights random_lpips_weights(0), side 256",
         "device": torch.cuda.get_device_name(0),
-        "legs": {"pyramid": "gance::pyramid_distance", "hip": "VGG16Lpips (gance::modconv3x3 + csrc/lpips.hip)", "torch": "plain torch ops (MIOpen conv2d)"},
-        "projector_step_ms": {f"B={batch}": child("steps", batch, ["pyramid", "hip", "torch"]) for batch in BATCHES},
-        "distance_forward_backward_ms": {f"B={batch}": child("distance", batch, ["hip", "torch"]) for batch in BATCHES},
+        "legs": {
+            "pyramid": "gance::pyramid_distance",
+            "hip": "VGG16Lpips (gance::modconv3x3 + csrc/lpips.hip)",
+            "torch": "plain torch ops (MIOpen conv2d)",
+            "hip-conv3x3": "VGG16Lpips(convolution='conv3x3') (gance::conv3x3 + csrc/lpips.hip)",
+        },
+        "projector_step_ms": {f"B={batch}": child("steps", batch, ["pyramid", *LEGS]) for batch in BATCHES},
+        "distance_forward_backward_ms": {f"B={batch}": child("distance", batch, list(LEGS)) for batch in BATCHES},
     }
     args.out.parent.mkdir(parents=True, exist_ok=True)
     args.out.write_text(json.dumps(result, indent=1) + "\n")
