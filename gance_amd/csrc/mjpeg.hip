@@ -21,6 +21,15 @@
 //                              per frame and of the frame sizes, then header + segments + RSTn + EOI per frame, frames
 //                              back to back
 // Every buffer is sized for the worst case (a block is at most 1660 bits before stuffing), so nothing can truncate.
+//
+// The optimised mode (gance_jpeg_encode_rect_optimized_*, libjpeg's optimize_coding) codes each frame with the optimal
+// tables of its own symbols. Between launches 1 and 3 it runs, in place of launch 2:
+//   2a. mjpeg_symbol_count_kernel    one thread per block, the walk of launch 2 with + 1 on a symbol in place of its bits:
+//                                    histograms in LDS, flushed into per-frame counts (integer atomics: order-independent)
+//   2b. mjpeg_optimal_tables_kernel  one wave per (frame, table): jchuff.c jpeg_gen_optimal_table, then the frame's DHT
+//                                    segments and encoder views (gance_jpeg_optimal_tables is this kernel on given counts)
+//   2c. mjpeg_huffman_frame_kernel   launch 2 with the frame's tables staged in LDS
+// and the layout and pack kernels take a header length per frame. The standard mode's kernels are the code they were.
 
 #include <hip/hip_runtime.h>
 
@@ -68,6 +77,30 @@ constexpr HuffTables make_tables() {
 
 __constant__ HuffTables kHuff = make_tables();
 
+// The four tables in the order of a file's DHT segments: DC luma, AC luma, DC chroma, AC chroma. A frame of the optimised
+// mode carries its own four: the DHT payloads (class byte, 16 counts, symbols) and the encoder views in this order.
+constexpr int kFrameTables = 4;
+constexpr int kDhtCapacity = 4 * (2 + 2 + 1 + 16) + 2 * (12 + 162);  // 432: what the Annex K tables take as well
+
+struct StandardDht {
+    uint8_t bits[kFrameTables][16];
+    uint8_t values[kFrameTables][162];
+};
+
+constexpr StandardDht make_standard_dht() {
+    StandardDht d{};
+    const uint8_t* bits[kFrameTables] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
+    const uint8_t* values[kFrameTables] = {kDcValues, kAcLumaValues, kDcValues, kAcChromaValues};
+    for (int t = 0; t < kFrameTables; ++t) {
+        int count = 0;
+        for (int i = 0; i < 16; ++i) d.bits[t][i] = bits[t][i], count += bits[t][i];
+        for (int i = 0; i < count; ++i) d.values[t][i] = values[t][i];
+    }
+    return d;
+}
+
+__constant__ StandardDht kStandardDht = make_standard_dht();
+
 // Quantisation of one quality, natural order: d / 2 and ceil(2^32 / d) with d = 8 q (the islow DCT's output is 8x)
 struct QuantArgs {
     uint32_t half[2][64];
@@ -101,6 +134,7 @@ static QuantArgs make_quant(int quality) {
 struct Header {
     uint8_t bytes[kHeaderCapacity];
     int length;
+    int dht_begin, dht_end;  // the four DHT segments are bytes [dht_begin, dht_end)
 };
 
 // SOI, APP0 (JFIF 1.01, aspect 1:1), DQT x2 (zigzag), SOF0 (Y 2x1, Cb 1x1, Cr 1x1), DHT x4, DRI, SOS
@@ -126,6 +160,7 @@ static Header make_header(int width, int height, int quality) {
     const uint8_t* bits[4] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
     const uint8_t* values[4] = {kDcValues, kAcLumaValues, kDcValues, kAcChromaValues};
     const int classes[4] = {0x00, 0x10, 0x01, 0x11};
+    h.dht_begin = n;
     for (int t = 0; t < 4; ++t) {
         int count = 0;
         for (int i = 0; i < 16; ++i) count += bits[t][i];
@@ -133,6 +168,7 @@ static Header make_header(int width, int height, int quality) {
         for (int i = 0; i < 16; ++i) put(bits[t][i]);
         for (int i = 0; i < count; ++i) put(values[t][i]);
     }
+    h.dht_end = n;
     put16(0xFFDD); put16(4); put16(width / 16);
     put16(0xFFDA); put16(12); put(3);
     put(1); put(0x00);
@@ -149,11 +185,13 @@ struct Layout {
     int64_t segment_capacity;                       // stuffed bytes of a worst-case segment, rounded to 16
     int64_t coef_bytes, bits_bytes, bitlen_bytes, slot_bytes, size_bytes, dst_bytes;
     int64_t workspace_bytes, frame_capacity, out_capacity;
+    // the optimised mode's own regions, after the others (all 0 in the standard mode)
+    int64_t count_bytes, table_bytes, dht_bytes, dht_length_bytes, table_bits_bytes, table_values_bytes, table_status_bytes;
 };
 
 static int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
 
-static Layout layout_of(int64_t batch, int64_t width, int64_t height) {
+static Layout layout_of(int64_t batch, int64_t width, int64_t height, bool optimized = false) {
     Layout l{};
     l.mcu_cols = width / 16;
     l.mcu_rows = height / 8;
@@ -168,7 +206,19 @@ static Layout layout_of(int64_t batch, int64_t width, int64_t height) {
     l.size_bytes = round16(l.segments * 4);
     l.dst_bytes = round16(l.segments * 4);
     l.workspace_bytes = l.coef_bytes + l.bits_bytes + l.bitlen_bytes + l.slot_bytes + l.size_bytes + l.dst_bytes;
-    // header + segments + (rows - 1) RST markers + EOI
+    if (optimized) {
+        l.count_bytes = batch * kFrameTables * 256 * 4;
+        l.table_bytes = batch * kFrameTables * (int64_t)sizeof(HuffTable);
+        l.dht_bytes = batch * kDhtCapacity;
+        l.dht_length_bytes = round16(batch * 4);
+        l.table_bits_bytes = batch * kFrameTables * 16;
+        l.table_values_bytes = batch * kFrameTables * 256;
+        l.table_status_bytes = batch * kFrameTables * 4;
+        l.workspace_bytes += l.count_bytes + l.table_bytes + l.dht_bytes + l.dht_length_bytes + l.table_bits_bytes +
+                             l.table_values_bytes + l.table_status_bytes;
+    }
+    // header + segments + (rows - 1) RST markers + EOI; a frame's own tables take at most the Annex K tables' room in the
+    // header (12 and 162 symbols), and a code is at most 16 bits in either mode, so both modes share the capacity
     l.frame_capacity = kHeaderCapacity + l.mcu_rows * (2 * ((l.segment_blocks * kMaxBlockBits + 7) / 8)) + 2 * l.mcu_rows;
     l.out_capacity = batch * l.frame_capacity;
     return l;
@@ -396,12 +446,294 @@ __global__ void __launch_bounds__(256) mjpeg_huffman_kernel(const int16_t* __res
     bit_counts[g] = huffman_block(coef + g * 64, previous_dc, kHuff.dc[c], kHuff.ac[c], bits + g * kBlockWords);
 }
 
+// ---- 2b. the optimised mode: a frame's own tables (jchuff.c htest_one_block, jpeg_gen_optimal_table) ------------------
+// Thread t of a frame (kind-major inside a segment, as above) -> its block's index in the call and the previous DC
+struct FrameBlock {
+    int64_t g;
+    int previous_dc, component;
+};
+
+__device__ __forceinline__ FrameBlock frame_block(const int16_t* __restrict__ coef, int64_t frame, int64_t t, int64_t mcu_cols,
+                                                  int64_t frame_blocks) {
+    const int64_t segment_blocks = 4 * mcu_cols;
+    const int64_t segment = frame * (frame_blocks / segment_blocks) + t / segment_blocks;
+    const int within = (int)(t % segment_blocks);
+    const int kind = within / (int)mcu_cols, mcu = within % (int)mcu_cols;
+    const int p = 4 * mcu + kind;
+    const int previous = previous_of(p);
+    FrameBlock b;
+    b.g = segment * segment_blocks + p;
+    b.previous_dc = previous < 0 ? 0 : coef[(segment * segment_blocks + previous) * 64];
+    b.component = kind < 2 ? 0 : 1;
+    return b;
+}
+
+// The symbols huffman_block codes, counted: the walk is the same (the mask of the nonzero coefficients restated, so that
+// huffman_block stays the code it was), a put of a code becomes + 1 on its symbol
+__device__ inline void count_block(const int16_t* __restrict__ block, int previous_dc, int* __restrict__ dc, int* __restrict__ ac) {
+    uint64_t nonzero = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint4 v = ((const uint4*)block)[i];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            nonzero |= (uint64_t)((w[j] & 0xFFFF) != 0) << (8 * i + 2 * j);
+            nonzero |= (uint64_t)((w[j] >> 16) != 0) << (8 * i + 2 * j + 1);
+        }
+    }
+    nonzero &= ~1ull;  // AC only
+    const int dc_value = block[0];
+    int temp = dc_value - previous_dc;
+    if (temp < 0) temp = -temp;
+    atomicAdd(&dc[bit_length((uint32_t)temp)], 1);
+    int last = 0;
+    while (nonzero) {
+        const int k = __builtin_ctzll(nonzero);
+        nonzero &= nonzero - 1;
+        int run = k - last - 1;
+        last = k;
+        if (run > 15) atomicAdd(&ac[0xF0], run >> 4);
+        temp = block[k];
+        if (temp < 0) temp = -temp;
+        atomicAdd(&ac[((run & 15) << 4) + bit_length((uint32_t)temp)], 1);
+    }
+    if (last < 63) atomicAdd(&ac[0], 1);
+}
+
+// counts [frames][4][256], zeroed by the caller: one thread per block, a workgroup's blocks all of one frame. The
+// histograms are summed in LDS and then into HBM with integer atomics, so the counts do not depend on the order.
+__global__ void __launch_bounds__(256) mjpeg_symbol_count_kernel(const int16_t* __restrict__ coef, int64_t mcu_cols, int64_t frame_blocks,
+                                                                 int groups_per_frame, int* __restrict__ counts) {
+    __shared__ int histogram[kFrameTables * 256];
+    const int64_t frame = blockIdx.x / groups_per_frame;
+    const int64_t t = (int64_t)(blockIdx.x % groups_per_frame) * blockDim.x + threadIdx.x;
+    for (int i = threadIdx.x; i < kFrameTables * 256; i += blockDim.x) histogram[i] = 0;
+    __syncthreads();
+    if (t < frame_blocks) {
+        const FrameBlock b = frame_block(coef, frame, t, mcu_cols, frame_blocks);
+        count_block(coef + b.g * 64, b.previous_dc, histogram + 512 * b.component, histogram + 512 * b.component + 256);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kFrameTables * 256; i += blockDim.x)
+        if (histogram[i] != 0) atomicAdd(&counts[frame * kFrameTables * 256 + i], histogram[i]);
+}
+
+// The two smallest keys of a wave: (a, b) of every lane merged with the pair of lane ^ d, six times
+__device__ __forceinline__ uint64_t shuffle_xor64(uint64_t v, int d) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ void wave_two_smallest(uint64_t* a, uint64_t* b) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t oa = shuffle_xor64(*a, d), ob = shuffle_xor64(*b, d);
+        const uint64_t low = *a < oa ? *a : oa, high = *a < oa ? oa : *a, rest = *b < ob ? *b : ob;
+        *a = low;
+        *b = high < rest ? high : rest;
+    }
+}
+
+constexpr int kTableThreads = 64 * kFrameTables;  // one wave per table, a frame's four in one workgroup
+
+// jpeg_gen_optimal_table of `tables` count vectors [256] (negative counts as 0), one wave each: bits [16], values [256]
+// (unused entries 0) and status per table: 0 a table, 1 a code past 32 bits before the limiting (libjpeg's
+// JERR_HUFF_CLEN_OVERFLOW), 2 nothing counted; bits and values are 0 unless the status is 0.
+// The merge: entry i of the 257 (256 = the reserved symbol, count 1) is held by lane i % 64 with its count, the entry
+// that heads its group and its code size. A step takes the two smallest nonzero counts, ties to the larger index (the
+// key is count << 9 | 256 - index, smallest first), adds the second into the first and zeroes it, and every lane adds 1
+// to the code size of its entries of either group and moves them into the first: what libjpeg's chain walks do.
+// With frame_tables (the encoder; tables = 4 per frame in DHT order, a workgroup = a frame) it also writes the frame's
+// encoder views, its four DHT segments and their length: the Annex K ones, all four, unless all four statuses are 0 and
+// the symbols fit a baseline table (12 DC categories, 162 run/size pairs).
+__global__ void __launch_bounds__(kTableThreads) mjpeg_optimal_tables_kernel(const int* __restrict__ counts, int64_t tables,
+                                                                             uint8_t* __restrict__ out_bits, uint8_t* __restrict__ out_values,
+                                                                             int* __restrict__ out_status, HuffTable* __restrict__ frame_tables,
+                                                                             uint8_t* __restrict__ frame_dht, int* __restrict__ frame_dht_length) {
+    __shared__ int s_bits[kFrameTables][34];       // symbols per code size, the reserved one included; [33] collects overflows
+    __shared__ int s_before[kFrameTables][34];     // symbols 0..255 with a smaller code size (before the limiting)
+    __shared__ uint8_t s_size[kFrameTables][256];  // code size per symbol before the limiting
+    __shared__ uint8_t s_values[kFrameTables][256];
+    __shared__ int s_first_code[kFrameTables][17], s_first_rank[kFrameTables][18];
+    __shared__ int s_status[kFrameTables], s_count[kFrameTables];
+    __shared__ HuffTable s_table[kFrameTables];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t table = (int64_t)blockIdx.x * kFrameTables + wave;
+    const bool active = table < tables;
+
+    int64_t freq[5];
+    int group[5], size[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int index = lane + 64 * k;
+        int count = 0;
+        if (index < 256 && active) count = counts[table * 256 + index];
+        if (index == 256) count = 1;
+        freq[k] = count > 0 ? count : 0;
+        group[k] = index;
+        size[k] = 0;
+    }
+    for (;;) {
+        uint64_t a = ~0ull, b = ~0ull;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int index = lane + 64 * k;
+            if (index <= 256 && freq[k] > 0) {
+                const uint64_t key = ((uint64_t)freq[k] << 9) | (uint64_t)(256 - index);
+                if (key < a) b = a, a = key;
+                else if (key < b) b = key;
+            }
+        }
+        wave_two_smallest(&a, &b);
+        if (b == ~0ull) break;  // one group left
+        const int c1 = 256 - (int)(a & 511), c2 = 256 - (int)(b & 511);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int index = lane + 64 * k;
+            if (index == c1) freq[k] += (int64_t)(b >> 9);
+            if (index == c2) freq[k] = 0;
+            if (group[k] == c1 || group[k] == c2) ++size[k], group[k] = c1;
+        }
+    }
+
+    for (int i = lane; i < 34; i += 64) s_bits[wave][i] = 0, s_before[wave][i] = 0;
+    for (int i = lane; i < 256; i += 64) s_table[wave].code[i] = 0, s_table[wave].size[i] = 0, s_values[wave][i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int index = lane + 64 * k;
+        if (index > 256) continue;
+        const int clamped = size[k] > 32 ? 33 : size[k];
+        if (index < 256) s_size[wave][index] = (uint8_t)clamped;
+        if (clamped > 0) atomicAdd(&s_bits[wave][clamped], 1);
+        if (clamped > 0 && index < 256) atomicAdd(&s_before[wave][clamped], 1);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int* bits = s_bits[wave];
+        int status = 0, total = 0;
+        for (int l = 1; l <= 33; ++l) {  // the histogram of the symbols 0..255 into its exclusive prefix
+            const int here = s_before[wave][l];
+            s_before[wave][l] = total;
+            total += here;
+        }
+        if (total == 0) status = 2;  // the reserved symbol alone: it never merged
+        else if (bits[33] > 0) status = 1;
+        if (status == 0) {
+            // Annex K.3 figure K.3 as jchuff.c has it, then the reserved symbol out of the longest size in use
+            for (int i = 32; i > 16; --i)
+                while (bits[i] > 0) {
+                    int j = i - 2;
+                    while (j > 0 && bits[j] == 0) --j;
+                    if (j == 0) { status = 1; bits[i] = 0; break; }  // not a prefix code's sizes: cannot come out of the merge
+                    bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+                }
+            int i = 16;
+            while (i > 0 && bits[i] == 0) --i;
+            if (i > 0) --bits[i];
+        }
+        if (status == 0) {
+            int code = 0, rank = 0;
+            for (int l = 1; l <= 16; ++l) {
+                s_first_code[wave][l] = code, s_first_rank[wave][l] = rank;
+                code = (code + bits[l]) << 1, rank += bits[l];
+            }
+            s_first_rank[wave][17] = rank;
+            s_count[wave] = rank;
+            if (frame_tables != nullptr && rank > ((wave & 1) ? 162 : 12)) status = 1;  // not a baseline table
+        }
+        s_status[wave] = status;
+    }
+    __syncthreads();
+    const int status = s_status[wave];
+    if (status == 0) {
+        // libjpeg lists the symbols by their code size BEFORE the limiting, then by value; the limited counts then give
+        // the listed symbols their final sizes in that order
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int index = lane + 64 * k;
+            const int mine = size[k];
+            if (mine == 0) continue;
+            int rank = s_before[wave][mine];
+            for (int j = 0; j < index; ++j) rank += s_size[wave][j] == mine;
+            s_values[wave][rank] = (uint8_t)index;
+        }
+    }
+    __syncthreads();
+    if (status == 0) {
+        for (int rank = lane; rank < s_count[wave]; rank += 64) {
+            int l = 1;
+            while (rank >= s_first_rank[wave][l + 1]) ++l;
+            const int symbol = s_values[wave][rank];
+            s_table[wave].code[symbol] = (uint16_t)(s_first_code[wave][l] + rank - s_first_rank[wave][l]);
+            s_table[wave].size[symbol] = (uint8_t)l;
+        }
+    }
+    __syncthreads();
+    if (active) {
+        if (lane < 16) out_bits[table * 16 + lane] = status == 0 ? (uint8_t)s_bits[wave][lane + 1] : 0;
+        for (int i = lane; i < 256; i += 64) out_values[table * 256 + i] = status == 0 ? s_values[wave][i] : 0;
+        if (lane == 0) out_status[table] = status;
+    }
+    if (frame_tables == nullptr || !active) return;
+    const int64_t frame = blockIdx.x;
+    const bool standard = (s_status[0] | s_status[1] | s_status[2] | s_status[3]) != 0;
+    const HuffTable& view = wave == 0 ? kHuff.dc[0] : wave == 1 ? kHuff.ac[0] : wave == 2 ? kHuff.dc[1] : kHuff.ac[1];
+    HuffTable* out_table = frame_tables + frame * kFrameTables + wave;
+    for (int i = lane; i < 256; i += 64) {
+        out_table->code[i] = standard ? view.code[i] : s_table[wave].code[i];
+        out_table->size[i] = standard ? view.size[i] : s_table[wave].size[i];
+    }
+    int count = 0, before = 0;  // symbols of this table, DHT bytes of the frame's earlier tables
+    for (int w = 0; w < kFrameTables; ++w) {
+        int n = 0;
+        if (standard)
+            for (int i = 0; i < 16; ++i) n += kStandardDht.bits[w][i];
+        else
+            n = s_count[w];
+        if (w < wave) before += 21 + n;
+        if (w == wave) count = n;
+    }
+    uint8_t* dht = frame_dht + frame * kDhtCapacity + before;
+    for (int i = lane; i < 21 + count; i += 64) {
+        uint8_t byte;
+        if (i == 0) byte = 0xFF;
+        else if (i == 1) byte = 0xC4;
+        else if (i == 2) byte = (uint8_t)((19 + count) >> 8);
+        else if (i == 3) byte = (uint8_t)((19 + count) & 0xFF);
+        else if (i == 4) byte = (uint8_t)(((wave & 1) << 4) | (wave >> 1));
+        else if (i < 21) byte = standard ? kStandardDht.bits[wave][i - 5] : (uint8_t)s_bits[wave][i - 4];
+        else byte = standard ? kStandardDht.values[wave][i - 21] : s_values[wave][i - 21];
+        dht[i] = byte;
+    }
+    if (wave == kFrameTables - 1 && lane == 0) frame_dht_length[frame] = before + 21 + count;
+}
+
+// mjpeg_huffman_kernel with the frame's own tables, staged in LDS: a workgroup's blocks are all of one frame
+__global__ void __launch_bounds__(256) mjpeg_huffman_frame_kernel(const int16_t* __restrict__ coef, int64_t mcu_cols, int64_t frame_blocks,
+                                                                  int groups_per_frame, const HuffTable* __restrict__ frame_tables,
+                                                                  uint32_t* __restrict__ bits, int* __restrict__ bit_counts) {
+    __shared__ HuffTable tables[kFrameTables];
+    const int64_t frame = blockIdx.x / groups_per_frame;
+    const int64_t t = (int64_t)(blockIdx.x % groups_per_frame) * blockDim.x + threadIdx.x;
+    const uint4* src = (const uint4*)(frame_tables + frame * kFrameTables);
+    uint4* dst = (uint4*)tables;
+    constexpr int kVectors = kFrameTables * (int)sizeof(HuffTable) / 16;
+    for (int i = threadIdx.x; i < kVectors; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+    if (t >= frame_blocks) return;
+    const FrameBlock b = frame_block(coef, frame, t, mcu_cols, frame_blocks);
+    bit_counts[b.g] = huffman_block(coef + b.g * 64, b.previous_dc, tables[2 * b.component], tables[2 * b.component + 1],
+                                    bits + b.g * kBlockWords);
+}
+
 // ---- 3. one restart segment ----------------------------------------------------------------------------------------
 // Bits [32 w, 32 w + 32) of the segment, given the blocks' bit offsets (offsets[n] = total): OR of the overlapping
 // blocks' bits, then 1-padding past the end.
 __host__ __device__ inline uint32_t segment_word(const uint32_t* __restrict__ bits, const int* __restrict__ offsets, int n, int w) {
     const int lo = 32 * w;
-    // last block starting at or before `lo` (offsets strictly increase: a block has >= 4 bits)
+    // last block starting at or before `lo` (offsets strictly increase: a block has >= 4 bits, >= 2 with a frame's own tables)
     int a = 0, b = n - 1;
     while (a < b) {
         const int mid = (a + b + 1) >> 1;
@@ -496,12 +828,15 @@ __global__ void __launch_bounds__(kSegmentThreads) mjpeg_segment_kernel(const ui
 // ---- 4. frame layout and packing -----------------------------------------------------------------------------------
 // One workgroup per frame: where each segment lands relative to its frame (a block scan of the segment sizes, each + 2
 // for the RSTn or EOI after it), and the frame's size into offsets[frame + 1].
+// kOwnTables (the optimised mode): header_bytes is the header without its DHT segments, dht_length[frame] their bytes.
+template <bool kOwnTables>
 __global__ void __launch_bounds__(kSegmentThreads) mjpeg_frame_layout_kernel(const int* __restrict__ segment_sizes, int mcu_rows,
-                                                                              int header_bytes, int* __restrict__ segment_dst,
-                                                                              int64_t* __restrict__ offsets) {
+                                                                              int header_bytes, const int* __restrict__ dht_length,
+                                                                              int* __restrict__ segment_dst, int64_t* __restrict__ offsets) {
     __shared__ int scratch[kSegmentThreads];
     const int64_t frame = blockIdx.x;
     int carry = header_bytes;  // a frame is < 2^31 bytes: at most 1024 rows of < 850 000 bytes (side <= 8192)
+    if (kOwnTables) carry += dht_length[frame];
     for (int base = 0; base < mcu_rows; base += kSegmentThreads) {
         const int r = base + threadIdx.x;
         const int size = r < mcu_rows ? segment_sizes[frame * mcu_rows + r] + 2 : 0;
@@ -528,9 +863,13 @@ __global__ void __launch_bounds__(kSegmentThreads) mjpeg_frame_offsets_kernel(in
     if (threadIdx.x == 0) offsets[0] = 0;
 }
 
+// kOwnTables (the optimised mode): the header's DHT segments are the frame's, frame_dht [frames][kDhtCapacity] of
+// dht_length[frame] bytes, between the parts of `header` in front of and behind its own.
+template <bool kOwnTables>
 __global__ void __launch_bounds__(256) mjpeg_pack_kernel(const uint8_t* __restrict__ slots, int64_t segment_capacity,
                                                          const int* __restrict__ segment_sizes, const int* __restrict__ segment_dst,
                                                          const int64_t* __restrict__ offsets, int mcu_rows, Header header,
+                                                         const uint8_t* __restrict__ frame_dht, const int* __restrict__ dht_length,
                                                          uint8_t* __restrict__ out) {
     const int64_t segment = blockIdx.x;
     const int64_t frame = segment / mcu_rows;
@@ -545,7 +884,16 @@ __global__ void __launch_bounds__(256) mjpeg_pack_kernel(const uint8_t* __restri
     }
     if (row == 0) {
         uint8_t* head = out + offsets[frame];
-        for (int i = threadIdx.x; i < header.length; i += blockDim.x) head[i] = header.bytes[i];
+        if (kOwnTables) {
+            const int own = dht_length[frame];
+            const uint8_t* dht = frame_dht + frame * kDhtCapacity;
+            for (int i = threadIdx.x; i < header.dht_begin; i += blockDim.x) head[i] = header.bytes[i];
+            for (int i = threadIdx.x; i < own; i += blockDim.x) head[header.dht_begin + i] = dht[i];
+            for (int i = threadIdx.x; i < header.length - header.dht_end; i += blockDim.x)
+                head[header.dht_begin + own + i] = header.bytes[header.dht_end + i];
+        } else {
+            for (int i = threadIdx.x; i < header.length; i += blockDim.x) head[i] = header.bytes[i];
+        }
     }
 }
 
@@ -571,11 +919,11 @@ static int check_rect_sizes(int32_t batch, int32_t width, int32_t height) {
 // The encode of `batch` frames [height][width][3]; sizes, quality and pointers (NULL) are checked by the callers.
 static int encode(const char* entry, const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality,
                   void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity, int64_t* d_offsets,
-                  void* stream_ptr) {
+                  void* stream_ptr, bool optimized = false) {
     if (quality < 1 || quality > 100) return fail(GANCE_ERR_INVALID_ARGUMENT, "quality must be in [1, 100], got " + std::to_string(quality));
     if ((uintptr_t)d_frames % 16 != 0 || (uintptr_t)d_workspace % 16 != 0)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "frames and workspace must be 16-byte aligned");
-    const Layout l = layout_of(batch, width, height);
+    const Layout l = layout_of(batch, width, height, optimized);
     const std::string bounds = std::string(" needed (") + entry + ")";
     if (workspace_bytes < (uint64_t)l.workspace_bytes)
         return fail(GANCE_ERR_INVALID_ARGUMENT, "workspace of " + std::to_string(workspace_bytes) + " bytes, " +
@@ -600,14 +948,42 @@ static int encode(const char* entry, const uint8_t* d_frames, int32_t batch, int
     hipStream_t stream = (hipStream_t)stream_ptr;
     const unsigned grid = (unsigned)((l.blocks + 255) / 256);
     mjpeg_transform_kernel<<<grid, 256, 0, stream>>>(d_frames, width, height, l.mcu_rows, l.mcu_cols, l.blocks, make_quant(quality), coef);
-    mjpeg_huffman_kernel<<<grid, 256, 0, stream>>>(coef, l.mcu_cols, l.blocks, bits, bit_counts);
-    mjpeg_segment_kernel<<<(unsigned)l.segments, kSegmentThreads, 0, stream>>>(bits, bit_counts, (int)l.segment_blocks, l.segment_capacity,
-                                                                               slots, segment_sizes);
-    mjpeg_frame_layout_kernel<<<(unsigned)batch, kSegmentThreads, 0, stream>>>(segment_sizes, (int)l.mcu_rows, header.length, segment_dst,
-                                                                               d_offsets);
-    mjpeg_frame_offsets_kernel<<<1, kSegmentThreads, 0, stream>>>(batch, d_offsets);
-    mjpeg_pack_kernel<<<(unsigned)l.segments, 256, 0, stream>>>(slots, l.segment_capacity, segment_sizes, segment_dst, d_offsets,
-                                                                (int)l.mcu_rows, header, d_out);
+    if (!optimized) {
+        mjpeg_huffman_kernel<<<grid, 256, 0, stream>>>(coef, l.mcu_cols, l.blocks, bits, bit_counts);
+        mjpeg_segment_kernel<<<(unsigned)l.segments, kSegmentThreads, 0, stream>>>(bits, bit_counts, (int)l.segment_blocks, l.segment_capacity,
+                                                                                   slots, segment_sizes);
+        mjpeg_frame_layout_kernel<false><<<(unsigned)batch, kSegmentThreads, 0, stream>>>(segment_sizes, (int)l.mcu_rows, header.length, nullptr,
+                                                                                          segment_dst, d_offsets);
+        mjpeg_frame_offsets_kernel<<<1, kSegmentThreads, 0, stream>>>(batch, d_offsets);
+        mjpeg_pack_kernel<false><<<(unsigned)l.segments, 256, 0, stream>>>(slots, l.segment_capacity, segment_sizes, segment_dst, d_offsets,
+                                                                           (int)l.mcu_rows, header, nullptr, nullptr, d_out);
+    } else {
+        char* own = (char*)(segment_dst) + l.dst_bytes;
+        int* counts = (int*)own;
+        HuffTable* frame_tables = (HuffTable*)(own + l.count_bytes);
+        uint8_t* frame_dht = (uint8_t*)(own + l.count_bytes + l.table_bytes);
+        int* dht_length = (int*)(own + l.count_bytes + l.table_bytes + l.dht_bytes);
+        uint8_t* table_bits = (uint8_t*)(own + l.count_bytes + l.table_bytes + l.dht_bytes + l.dht_length_bytes);
+        uint8_t* table_values = table_bits + l.table_bits_bytes;
+        int* table_status = (int*)(table_values + l.table_values_bytes);
+        const int64_t frame_blocks = l.blocks / batch;
+        const int groups_per_frame = (int)((frame_blocks + 255) / 256);
+        const unsigned frame_grid = (unsigned)(batch * (int64_t)groups_per_frame);
+        const hipError_t zeroed = hipMemsetAsync(counts, 0, (size_t)l.count_bytes, stream);
+        if (zeroed != hipSuccess) return fail(GANCE_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(zeroed));
+        mjpeg_symbol_count_kernel<<<frame_grid, 256, 0, stream>>>(coef, l.mcu_cols, frame_blocks, groups_per_frame, counts);
+        mjpeg_optimal_tables_kernel<<<(unsigned)batch, kTableThreads, 0, stream>>>(counts, (int64_t)batch * kFrameTables, table_bits, table_values,
+                                                                                   table_status, frame_tables, frame_dht, dht_length);
+        mjpeg_huffman_frame_kernel<<<frame_grid, 256, 0, stream>>>(coef, l.mcu_cols, frame_blocks, groups_per_frame, frame_tables, bits,
+                                                                   bit_counts);
+        mjpeg_segment_kernel<<<(unsigned)l.segments, kSegmentThreads, 0, stream>>>(bits, bit_counts, (int)l.segment_blocks, l.segment_capacity,
+                                                                                   slots, segment_sizes);
+        mjpeg_frame_layout_kernel<true><<<(unsigned)batch, kSegmentThreads, 0, stream>>>(
+            segment_sizes, (int)l.mcu_rows, header.length - (header.dht_end - header.dht_begin), dht_length, segment_dst, d_offsets);
+        mjpeg_frame_offsets_kernel<<<1, kSegmentThreads, 0, stream>>>(batch, d_offsets);
+        mjpeg_pack_kernel<true><<<(unsigned)l.segments, 256, 0, stream>>>(slots, l.segment_capacity, segment_sizes, segment_dst, d_offsets,
+                                                                          (int)l.mcu_rows, header, frame_dht, dht_length, d_out);
+    }
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(GANCE_ERR_HIP, std::string("mjpeg launch: ") + hipGetErrorString(err));
     return GANCE_OK;
@@ -656,6 +1032,48 @@ int gance_jpeg_encode_u8(const uint8_t* d_frames, int32_t batch, int32_t side, i
     if (const int status = check_sizes(batch, side)) return status;
     return encode("gance_jpeg_encode_bounds", d_frames, batch, side, side, quality, d_workspace, workspace_bytes, d_out, out_capacity,
                   d_offsets, stream_ptr);
+}
+
+int gance_jpeg_encode_rect_optimized_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes,
+                                            uint64_t* out_capacity) {
+    using namespace gance_mjpeg;
+    if (workspace_bytes == nullptr || out_capacity == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_rect_optimized_bounds");
+    if (const int status = check_rect_sizes(batch, width, height)) return status;
+    const Layout l = layout_of(batch, width, height, true);
+    *workspace_bytes = (uint64_t)l.workspace_bytes;
+    *out_capacity = (uint64_t)l.out_capacity;
+    return GANCE_OK;
+}
+
+int gance_jpeg_encode_rect_optimized_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality,
+                                        void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                        int64_t* d_offsets, void* stream_ptr) {
+    using namespace gance_mjpeg;
+    if (d_frames == nullptr || d_workspace == nullptr || d_out == nullptr || d_offsets == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_encode_rect_optimized_u8");
+    if (const int status = check_rect_sizes(batch, width, height)) return status;
+    return encode("gance_jpeg_encode_rect_optimized_bounds", d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out,
+                  out_capacity, d_offsets, stream_ptr, true);
+}
+
+int gance_jpeg_optimal_tables(const int32_t* d_counts, int32_t n, uint8_t* d_bits, uint8_t* d_values, int32_t* d_status,
+                              void* stream_ptr) {
+    using namespace gance_mjpeg;
+    if (d_counts == nullptr || d_bits == nullptr || d_values == nullptr || d_status == nullptr)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_jpeg_optimal_tables");
+    if (n < 1) return fail(GANCE_ERR_INVALID_ARGUMENT, "n must be >= 1, got " + std::to_string(n));
+    int device_count = 0;
+    if (hipGetDeviceCount(&device_count) != hipSuccess || device_count == 0)
+        return fail(GANCE_ERR_NO_DEVICE, "no HIP device visible; libgance_hip has no CPU path");
+    gance::DeviceGuard guard(gance::device_of_pointer(d_counts));
+    if (guard.status() != hipSuccess) return fail(GANCE_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.status()));
+    const unsigned grid = (unsigned)(((int64_t)n + kFrameTables - 1) / kFrameTables);
+    mjpeg_optimal_tables_kernel<<<grid, kTableThreads, 0, (hipStream_t)stream_ptr>>>(d_counts, n, d_bits, d_values, d_status, nullptr, nullptr,
+                                                                                    nullptr);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(GANCE_ERR_HIP, std::string("mjpeg tables launch: ") + hipGetErrorString(err));
+    return GANCE_OK;
 }
 
 }  // extern "C"

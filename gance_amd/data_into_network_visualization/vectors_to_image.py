@@ -11,7 +11,7 @@ from typing import Iterator, Tuple, Union
 import numpy as np
 import torch
 
-from gance_amd import torch_ops  # noqa: F401  (registers torch.ops.gance.*)
+from gance_amd import torch_ops  # (registers torch.ops.gance.*)
 from gance_amd.debug_video import compose
 from gance_amd.debug_video.latents_panel import LatentsPanel, LatentsPanelDrawer
 from gance_amd.vector_sources.vector_sources_common import sub_vectors
@@ -22,15 +22,19 @@ CHUNK_FRAMES = 64
 
 
 def write_chunks_to_avi(  # pylint: disable=too-many-arguments
-    chunks: Iterator[Tuple[int, torch.Tensor]], output_path: Path, width: int, height: int, video_fps: float, jpeg_quality: int
+    chunks: Iterator[Tuple[int, torch.Tensor]], output_path: Path, width: int, height: int, video_fps: float, jpeg_quality: int,
+    jpeg_huffman: str = "standard",
 ) -> int:
     """
     Composed chunks (first frame, [n, height, width, 3] uint8 in HBM) -> a Motion-JPEG AVI without audio: every chunk goes
-    through torch.ops.gance.jpeg_encode_rect and its frames to the writer in order. Returns the frames written.
+    through torch.ops.gance.jpeg_encode_rect (`jpeg_huffman` "optimized": jpeg_encode_optimized, each frame's own Huffman
+    tables) and its frames to the writer in order. Returns the frames written.
+    :raises ValueError: an unknown `jpeg_huffman`, before the file is opened.
     """
+    encode = torch_ops.jpeg_encode_op(jpeg_huffman, square=False)
     with mjpeg_avi.MjpegAviWriter(output_path, height, video_fps, width=width, height=height) as writer:
         for _first, chunk in chunks:
-            data, offsets = torch.ops.gance.jpeg_encode_rect(chunk, int(jpeg_quality))
+            data, offsets = encode(chunk, int(jpeg_quality))
             offsets_host = offsets.cpu().numpy()  # (waits for the encode)
             data_host = data[: int(offsets_host[-1])].cpu().numpy()
             for index in range(int(chunk.shape[0])):
@@ -69,12 +73,13 @@ def vectors_frame_chunks(
 
 
 def vectors_to_video(
-    labeled_data: Union[VectorsLabel, MatricesLabel], output_path: Path, video_height: int, video_fps: float, jpeg_quality: int = 90
+    labeled_data: Union[VectorsLabel, MatricesLabel], output_path: Path, video_height: int, video_fps: float, jpeg_quality: int = 90,
+    jpeg_huffman: str = "standard",
 ) -> Path:
     """
     The canonical video of some vectors / matrices (vectors_to_image.py:222-259) as a Motion-JPEG AVI, `video_height`
-    square. Returns `output_path` once the video has been written.
+    square. Returns `output_path` once the video has been written. `jpeg_huffman`: see write_chunks_to_avi.
     """
     side = compose.validate_side_length(video_height)
-    write_chunks_to_avi(vectors_frame_chunks(labeled_data, side), Path(output_path), side, side, video_fps, jpeg_quality)
+    write_chunks_to_avi(vectors_frame_chunks(labeled_data, side), Path(output_path), side, side, video_fps, jpeg_quality, jpeg_huffman)
     return output_path

@@ -21,7 +21,8 @@ class DebugVideo(NamedTuple):
     The keyword-only `debug` argument of projection_file_blend_frame_chunks and noise_blend_frame_chunks: what the debug stream looks like and who
     receives it. `on_encoded(first_frame, EncodedFrames)` gets every chunk of JPEG-encoded debug frames in frame
     order; `on_composed(first_frame, frames [n, side, P * side, 3] uint8 in HBM)`, if given, sees the raw frames
-    first (on the reader stream: copy what is to be kept).
+    first (on the reader stream: copy what is to be kept). `jpeg_huffman`: "standard" (the Annex K tables) or "optimized"
+    (each frame's own tables; a debug frame is mostly flat panels, where they save the most).
     """
 
     side_length: int
@@ -29,6 +30,7 @@ class DebugVideo(NamedTuple):
     on_encoded: Callable[[int, object], None]
     on_composed: Optional[Callable[[int, torch.Tensor], None]] = None
     jpeg_quality: int = 90
+    jpeg_huffman: str = "standard"
 
 
 class DebugSources(NamedTuple):

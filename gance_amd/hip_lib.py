@@ -230,6 +230,19 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_jpeg_encode_rect_optimized_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_jpeg_encode_rect_optimized_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "gance_jpeg_optimal_tables": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_jpeg_parse_header": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "gance_png_encode_bounds": (
         ctypes.c_int,
@@ -423,7 +436,8 @@ ADDED_WITHIN_ABI = {
     "gance_pyramid_distance_backward", "gance_png_encode_lz_bounds", "gance_png_encode_lz_u8", "gance_lpips_input_forward",
     "gance_lpips_input_backward", "gance_bias_relu_forward", "gance_bias_relu_backward", "gance_lpips_layer_workspace_bytes",
     "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize", "gance_conv3x3_form",
-    "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward",
+    "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward", "gance_jpeg_encode_rect_optimized_bounds",
+    "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1012,6 +1026,57 @@ def jpeg_encode_rect_device(  # pylint: disable=too-many-arguments
             d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
         ),
     )
+
+
+JPEG_HUFFMAN_MODES = ("standard", "optimized")
+
+
+def check_jpeg_huffman(jpeg_huffman: str) -> str:
+    """`jpeg_huffman` if it names a table mode of the JPEG encoder. Host only.
+    :raises ValueError: anything but "standard" (the Annex K tables) or "optimized" (each frame's own tables)."""
+    if jpeg_huffman not in JPEG_HUFFMAN_MODES:
+        raise ValueError(f"jpeg_huffman must be one of {JPEG_HUFFMAN_MODES}, got {jpeg_huffman!r}")
+    return jpeg_huffman
+
+
+def jpeg_encode_rect_optimized_bounds(batch: int, width: int, height: int) -> Tuple[int, int]:
+    """(workspace bytes, output capacity) of one `jpeg_encode_rect_optimized_device` call: the capacity of
+    `jpeg_encode_rect_bounds`, a workspace larger by the frames' symbol counts and tables.
+    :raises ValueError: width or height not a multiple of 16 in [16, 8192], or batch < 1."""
+    lib = load_library()
+    workspace, capacity = ctypes.c_uint64(), ctypes.c_uint64()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_jpeg_encode_rect_optimized_bounds(batch, width, height, ctypes.byref(workspace), ctypes.byref(capacity))
+    )
+    return int(workspace.value), int(capacity.value)
+
+
+def jpeg_encode_rect_optimized_device(  # pylint: disable=too-many-arguments
+    d_frames: int, batch: int, width: int, height: int, quality: int, d_workspace: int, workspace_bytes: int, d_out: int,
+    out_capacity: int, d_offsets: int, stream: int = 0,
+) -> None:
+    """
+    `jpeg_encode_rect_device` with each frame's four Huffman tables built from the frame's own symbol counts as libjpeg's
+    optimize_coding builds them: the same coefficients and decoded pixels, smaller files, a header length per frame.
+    :raises ValueError: bad width or height, quality outside 1..100, workspace or capacity below `jpeg_encode_rect_optimized_bounds`.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_jpeg_encode_rect_optimized_u8(
+            d_frames, batch, width, height, quality, d_workspace, workspace_bytes, d_out, out_capacity, d_offsets, stream or None
+        ),
+    )
+
+
+def jpeg_optimal_tables_device(d_counts: int, count: int, d_bits: int, d_values: int, d_status: int, stream: int = 0) -> None:  # pylint: disable=too-many-arguments
+    """
+    The table build of the optimised mode on `count` given count vectors: d_counts [count][256] int32 -> d_bits [count][16] u8,
+    d_values [count][256] u8, d_status [count] int32 (0 a table, 1 a code past 32 bits before the limiting, 2 nothing counted).
+    :raises ValueError: count < 1.
+    """
+    lib = load_library()
+    _value_error_on_invalid_argument(lib, lib.gance_jpeg_optimal_tables(d_counts, count, d_bits, d_values, d_status, stream or None))
 
 
 # filtered bytes per independently deflated segment of a PNG (kSegmentBytes of csrc/png.hip): one IDAT chunk each

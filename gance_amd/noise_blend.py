@@ -168,6 +168,7 @@ def noise_blend_frame_chunks(  # pylint: disable=too-many-arguments
     *,
     debug: Optional[DebugVideo] = None,
     noise_seed: Optional[int] = None,
+    jpeg_huffman: str = "standard",
 ) -> Iterator[Tuple[int, int, np.ndarray]]:
     """
     The frame stream of the command: a generator of (first_frame_index, total_frames, frames [n, S, S, 3] uint8, or
@@ -185,7 +186,7 @@ def noise_blend_frame_chunks(  # pylint: disable=too-many-arguments
     random init every noise strength is zero and the planes are never read).
     :raises ValueError: as the projection stream, for the same mistakes, before anything is loaded.
     """
-    projection_file_blend._check_stream_arguments(drain, None, jpeg_quality, output_side_length, debug)  # pylint: disable=protected-access
+    projection_file_blend._check_stream_arguments(drain, None, jpeg_quality, output_side_length, debug, jpeg_huffman)  # pylint: disable=protected-access
 
     def prepare(resident: MultiNetwork, device: torch.device):
         return _prepare_noise_inputs(
@@ -194,7 +195,7 @@ def noise_blend_frame_chunks(  # pylint: disable=too-many-arguments
 
     yield from projection_file_blend._frame_stream(  # pylint: disable=protected-access
         prepare, network_paths, output_side_length, frames_per_call, None, networks, timings, drain, on_total, jpeg_quality, debug,
-        noise_seed=noise_seed,
+        noise_seed=noise_seed, jpeg_huffman=jpeg_huffman,
     )
 
 
@@ -216,6 +217,7 @@ def noise_blend_api(  # pylint: disable=too-many-arguments,too-many-locals
     output_format: str = "npy",
     jpeg_quality: int = 90,
     noise_seed: Optional[int] = None,
+    jpeg_huffman: str = "standard",
 ) -> None:
     """
     Same parameter list as the reference command (music_into_networks.py:285-401). Frames are written to `output_path`
@@ -224,13 +226,13 @@ def noise_blend_api(  # pylint: disable=too-many-arguments,too-many-locals
     WAVs as its audio stream, encoded in HBM at `jpeg_quality` (raw frames never reach the host). With `debug_path` the
     debug video is written there as a second AVI with the song: per frame the hero frame scaled to `debug_side_length`
     beside the synthesis-inputs plot (windows of `debug_window` frames, a fifth of the run if None). The AVI and the debug
-    video force drain="rank0". `drain`, `output_format`, `jpeg_quality` mean what they mean in
+    video force drain="rank0". `drain`, `output_format`, `jpeg_quality`, `jpeg_huffman` mean what they mean in
     projection_file_blend_api; `noise_seed`: see noise_blend_frame_chunks.
     :raises ValueError: before any device is touched, with the messages of projection_file_blend_api: an unknown
-    output_format; "avi" with a side that is not a multiple of 16, a jpeg_quality outside 1..100 or a frame rate AVI cannot
+    output_format or jpeg_huffman; "avi" with a side that is not a multiple of 16, a jpeg_quality outside 1..100 or a frame rate AVI cannot
     hold; `debug_path` without a `debug_side_length` that is a multiple of 16 in [16, 4096].
     """
-    encode = projection_file_blend.check_output_arguments(output_format, output_side_length, jpeg_quality, output_fps)
+    encode = projection_file_blend.check_output_arguments(output_format, output_side_length, jpeg_quality, output_fps, jpeg_huffman)
     drain = drain or os.environ.get("GANCE_STREAM_DRAIN", "rank0")
     debug_side = projection_file_blend.check_debug_arguments(debug_path, debug_side_length, debug_window, False, jpeg_quality, output_fps)
     if encode or debug_path is not None:
@@ -240,9 +242,10 @@ def noise_blend_api(  # pylint: disable=too-many-arguments,too-many-locals
     def chunks_of(on_total, quality, debug):
         return noise_blend_frame_chunks(
             wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled, fft_amplitude_range,
-            drain=drain, on_total=on_total, jpeg_quality=quality, debug=debug, noise_seed=noise_seed,
+            drain=drain, on_total=on_total, jpeg_quality=quality, debug=debug, noise_seed=noise_seed, jpeg_huffman=jpeg_huffman,
         )
 
     projection_file_blend.write_frame_stream(
-        chunks_of, wav, output_path, output_fps, output_side_length, debug_path, debug_side, debug_window, debug_panels, drain, encode, int(jpeg_quality)
+        chunks_of, wav, output_path, output_fps, output_side_length, debug_path, debug_side, debug_window, debug_panels, drain, encode,
+        int(jpeg_quality), jpeg_huffman,
     )

@@ -344,33 +344,39 @@ def _video_side(video_height: Optional[int], panel_count: int) -> int:
     return side
 
 
-def visualize_final_latents(projection_file_path: Path, output_video_path: Path, video_height: Optional[int] = 1024, jpeg_quality: int = 90) -> None:
-    """The target next to the final projection, with the final latents (:214-267), at the projection's fps."""
+def visualize_final_latents(  # pylint: disable=too-many-arguments
+    projection_file_path: Path, output_video_path: Path, video_height: Optional[int] = 1024, jpeg_quality: int = 90,
+    jpeg_huffman: str = "standard",
+) -> None:
+    """The target next to the final projection, with the final latents (:214-267), at the projection's fps. `jpeg_huffman`:
+    "standard" or "optimized" (each frame's own Huffman tables: the same pixels, smaller files), as write_chunks_to_avi takes it."""
     side = _video_side(video_height, 3)
     chunks = final_latents_frame_chunks(projection_file_path, side)
-    write_chunks_to_avi(chunks, Path(output_video_path), 3 * side, side, _fps_of(projection_file_path), jpeg_quality)
+    write_chunks_to_avi(chunks, Path(output_video_path), 3 * side, side, _fps_of(projection_file_path), jpeg_quality, jpeg_huffman)
 
 
 def visualize_projection_history(  # pylint: disable=too-many-arguments
     projection_file_path: Path, output_video_path: Path, projection_network_path: Path, network_not_matching_ok: bool,
     video_height: Optional[int] = 1024, start_frame_index: Optional[int] = None, end_frame_index: Optional[int] = None,
-    jpeg_quality: int = 90,
+    jpeg_quality: int = 90, jpeg_huffman: str = "standard",
 ) -> None:
-    """Every latent of every projection history as it approaches the target (:308-381), at the projection's fps."""
+    """Every latent of every projection history as it approaches the target (:308-381), at the projection's fps. `jpeg_huffman`:
+    see visualize_final_latents."""
     side = _video_side(video_height, 3)
     chunks = projection_history_frame_chunks(
         projection_file_path, projection_network_path, network_not_matching_ok, side, start_frame_index, end_frame_index
     )
-    write_chunks_to_avi(chunks, Path(output_video_path), 3 * side, side, _fps_of(projection_file_path), jpeg_quality)
+    write_chunks_to_avi(chunks, Path(output_video_path), 3 * side, side, _fps_of(projection_file_path), jpeg_quality, jpeg_huffman)
 
 
 def visualize_partial_projection_history(  # pylint: disable=too-many-arguments
     projection_file_path: Path, output_video_path: Path, projection_network_path: Path, network_not_matching_ok: bool,
-    projection_step_to_take: int, video_height: Optional[int] = 1024, jpeg_quality: int = 90,
+    projection_step_to_take: int, video_height: Optional[int] = 1024, jpeg_quality: int = 90, jpeg_huffman: str = "standard",
 ) -> None:
-    """What taking step `projection_step_to_take` instead of the final latents does to every frame (:384-451), at 1 fps."""
+    """What taking step `projection_step_to_take` instead of the final latents does to every frame (:384-451), at 1 fps.
+    `jpeg_huffman`: see visualize_final_latents."""
     side = _video_side(video_height, 4)
     chunks = partial_projection_history_frame_chunks(
         projection_file_path, projection_network_path, network_not_matching_ok, projection_step_to_take, side
     )
-    write_chunks_to_avi(chunks, Path(output_video_path), 4 * side, side, 1.0, jpeg_quality)
+    write_chunks_to_avi(chunks, Path(output_video_path), 4 * side, side, 1.0, jpeg_quality, jpeg_huffman)

@@ -627,35 +627,47 @@ class _EncodedHostRing:
 
 
 def encode_into_ring(  # pylint: disable=too-many-arguments
-    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream
+    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream, jpeg_huffman: str = "standard"
 ) -> Iterator[Tuple[int, Optional[tuple]]]:
     """
     Encode device frames [n, S, S, 3] on the reader stream, at most `piece_frames` per encoder call, and push each piece into
     the ring. Yields (bytes moved to the host, the chunk the push finished or None) after EVERY push, so the consumer
-    takes a finished chunk before the next push can reuse its slot.
+    takes a finished chunk before the next push can reuse its slot. `jpeg_huffman` picks the op: torch.ops.gance.jpeg_encode
+    ("standard") or jpeg_encode_optimized ("optimized": each frame's own Huffman tables).
     """
     side = int(frames.shape[1])
+    encode = torch_ops.jpeg_encode_op(jpeg_huffman, square=True)
     for start in range(0, int(frames.shape[0]), piece_frames):
         with torch.cuda.stream(reader_stream):
-            data, offsets = torch.ops.gance.jpeg_encode(frames[start : start + piece_frames], quality)
+            data, offsets = encode(frames[start : start + piece_frames], quality)
         yield ring.push(first + start, data, offsets, side, reader_stream)
 
 
 def encode_debug_into_ring(  # pylint: disable=too-many-arguments
-    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream
+    ring: _EncodedHostRing, first: int, frames: torch.Tensor, quality: int, piece_frames: int, reader_stream, jpeg_huffman: str = "standard"
 ) -> Iterator[Tuple[int, Optional[tuple]]]:
-    """`encode_into_ring` for composed debug frames [n, side, P * side, 3]: torch.ops.gance.jpeg_encode_rect."""
+    """`encode_into_ring` for composed debug frames [n, side, P * side, 3]: torch.ops.gance.jpeg_encode_rect or jpeg_encode_optimized."""
     side, width = int(frames.shape[1]), int(frames.shape[2])
+    encode = torch_ops.jpeg_encode_op(jpeg_huffman, square=False)
     for start in range(0, int(frames.shape[0]), piece_frames):
         with torch.cuda.stream(reader_stream):
-            data, offsets = torch.ops.gance.jpeg_encode_rect(frames[start : start + piece_frames], quality)
+            data, offsets = encode(frames[start : start + piece_frames], quality)
         yield ring.push(first + start, data, offsets, side, reader_stream, width=width)
 
 
+def _huffman_mode(jpeg_huffman: str) -> Dict[str, str]:
+    """The keyword the two ring encoders take for a table mode: none for the default, whose call stays the one it was."""
+    return {} if jpeg_huffman == "standard" else {"jpeg_huffman": jpeg_huffman}
+
+
 def _check_stream_arguments(  # pylint: disable=too-many-arguments
-    drain: str, overlay: Optional[OverlayParameters], jpeg_quality: Optional[int], output_side_length: Optional[int], debug: Optional[DebugVideo]
+    drain: str, overlay: Optional[OverlayParameters], jpeg_quality: Optional[int], output_side_length: Optional[int], debug: Optional[DebugVideo],
+    jpeg_huffman: str = "standard",
 ) -> None:
     """The argument checks of a frame stream, before anything is loaded. :raises ValueError: see the generators' docstrings."""
+    hip_lib.check_jpeg_huffman(jpeg_huffman)
+    if debug is not None:
+        hip_lib.check_jpeg_huffman(debug.jpeg_huffman)
     if drain not in frame_sharding.DRAIN_MODES:
         raise ValueError(f"drain must be one of {frame_sharding.DRAIN_MODES}, got {drain!r}")
     if drain == "per-rank" and overlay is not None:
@@ -690,6 +702,7 @@ def _frame_stream(  # pylint: disable=too-many-arguments,too-many-locals,too-man
     jpeg_quality: Optional[int],
     debug: Optional[DebugVideo],
     noise_seed: Optional[int] = None,
+    jpeg_huffman: str = "standard",
 ) -> Iterator[Tuple[int, int, np.ndarray]]:
     """
     The frame stream both commands share, behind their argument checks: rank 0 prepares the per-frame network inputs
@@ -794,7 +807,9 @@ def _frame_stream(  # pylint: disable=too-many-arguments,too-many-locals,too-man
                 if done is not None:
                     yield done
                 return
-            for moved, done in encode_into_ring(ring, ready_first, ready_frames, int(jpeg_quality), frames_per_call, reader_stream):
+            for moved, done in encode_into_ring(
+                ring, ready_first, ready_frames, int(jpeg_quality), frames_per_call, reader_stream, **_huffman_mode(jpeg_huffman)
+            ):
                 bytes_to_host += moved
                 if done is not None:
                     yield done
@@ -806,7 +821,8 @@ def _frame_stream(  # pylint: disable=too-many-arguments,too-many-locals,too-man
                     with torch.cuda.stream(reader_stream):
                         debug.on_composed(composed_first, composed_frames)
                 for _moved, done in encode_debug_into_ring(
-                    debug_ring, composed_first, composed_frames, int(debug.jpeg_quality), frames_per_call, reader_stream
+                    debug_ring, composed_first, composed_frames, int(debug.jpeg_quality), frames_per_call, reader_stream,
+                    **_huffman_mode(debug.jpeg_huffman),
                 ):
                     if done is not None:
                         debug.on_encoded(done[0], done[1])
@@ -892,6 +908,7 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     jpeg_quality: Optional[int] = None,
     *,
     debug: Optional[DebugVideo] = None,
+    jpeg_huffman: str = "standard",
 ) -> Iterator[Tuple[int, int, np.ndarray]]:
     """
     The frame stream of the reference's pipeline (gance/projection_file_blend.py:343 hands an iterator of frames to
@@ -918,6 +935,9 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     call, and drains only the offsets and the compressed bytes to a pinned host ring: the generator yields
     (first_frame_index, total_frames, EncodedFrames) and raw frames never reach the host; timings["bytes_to_host"] counts
     the compressed bytes. Needs drain="rank0" and an output side that is a multiple of 16.
+    :param jpeg_huffman: "standard" (default): the Annex K Huffman tables. "optimized": torch.ops.gance.jpeg_encode_optimized,
+    each frame's own tables as libjpeg's optimize_coding builds them: the same pixels in smaller files. The debug video
+    has its own, `debug.jpeg_huffman`.
     :param debug: None (default): nothing changes. A DebugVideo: rank 0 also composes the debug frames of every released
     chunk in HBM on the reader stream (gance_amd/debug_video/compose.py: output, foreground, final images, synthesis
     inputs, overlay computation, overlay binary mask, side by side), encodes them with torch.ops.gance.jpeg_encode_rect at
@@ -926,7 +946,7 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
     their window are complete: at most one debug window plus one chunk (timings["debug_frames_held_max"]). Needs
     drain="rank0"; with `overlay`, `debug.window` must be given.
     """
-    _check_stream_arguments(drain, overlay, jpeg_quality, output_side_length, debug)
+    _check_stream_arguments(drain, overlay, jpeg_quality, output_side_length, debug, jpeg_huffman)
 
     def prepare(resident: MultiNetwork, device: torch.device) -> _BlendInputs:
         return _prepare_blend_inputs(
@@ -935,7 +955,8 @@ def projection_file_blend_frame_chunks(  # pylint: disable=too-many-arguments,to
         )
 
     yield from _frame_stream(
-        prepare, network_paths, output_side_length, frames_per_call, overlay, networks, timings, drain, on_total, jpeg_quality, debug
+        prepare, network_paths, output_side_length, frames_per_call, overlay, networks, timings, drain, on_total, jpeg_quality, debug,
+        jpeg_huffman=jpeg_huffman,
     )
 
 
@@ -977,12 +998,15 @@ def _npy_path(output_path: str) -> str:
     return output_path if output_path.endswith(".npy") else output_path + ".npy"
 
 
-def check_output_arguments(output_format: str, output_side_length: Optional[int], jpeg_quality: int, output_fps: float) -> bool:
+def check_output_arguments(
+    output_format: str, output_side_length: Optional[int], jpeg_quality: int, output_fps: float, jpeg_huffman: str = "standard"
+) -> bool:
     """
     The output checks both commands make before any device is touched; True: the output is a video.
-    :raises ValueError: an unknown output_format; "avi" with a side that is not a multiple of 16, a jpeg_quality outside
-    1..100 or a frame rate AVI cannot hold.
+    :raises ValueError: an unknown output_format or jpeg_huffman; "avi" with a side that is not a multiple of 16, a
+    jpeg_quality outside 1..100 or a frame rate AVI cannot hold.
     """
+    hip_lib.check_jpeg_huffman(jpeg_huffman)
     if output_format not in ("npy", "avi"):
         raise ValueError(f"output_format must be \"npy\" or \"avi\", got {output_format!r}")
     encode = output_format == "avi"
@@ -1028,12 +1052,14 @@ def write_frame_stream(  # pylint: disable=too-many-arguments,too-many-locals
     drain: str,
     encode: bool,
     jpeg_quality: int,
+    jpeg_huffman: str = "standard",
 ) -> None:
     """
     Opens the outputs of a command and writes its frame stream into them, chunk by chunk: the `.npy` memory map or the
     Motion-JPEG AVI at `output_path`, and the debug AVI of `debug_panels` square panels per frame at `debug_path`.
     `chunks_of(on_total, jpeg_quality or None, debug)` is the command's generator (projection_file_blend_frame_chunks,
-    noise_blend_frame_chunks) with everything else bound.
+    noise_blend_frame_chunks) with everything else bound, its own `jpeg_huffman` included; the debug video is written
+    in the `jpeg_huffman` given here.
     """
     # frame chunks go straight from the pinned ring into the (memory-mapped) output file: nothing holds the video
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -1066,7 +1092,11 @@ def write_frame_stream(  # pylint: disable=too-many-arguments,too-many-locals
         for index in range(len(encoded)):
             state["debug_writer"].add_frame(encoded.frame(index))
 
-    debug = DebugVideo(debug_side, debug_window, write_debug_frames, jpeg_quality=int(jpeg_quality)) if debug_path is not None else None
+    debug = (
+        DebugVideo(debug_side, debug_window, write_debug_frames, jpeg_quality=int(jpeg_quality), jpeg_huffman=jpeg_huffman)
+        if debug_path is not None
+        else None
+    )
     try:
         for first, _total, frames in chunks_of(open_output, int(jpeg_quality) if encode else None, debug):
             if encode and state.get("avi_side_pending") and state["writer"] is None:
@@ -1113,6 +1143,7 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     *,
     output_format: str = "npy",
     jpeg_quality: int = 90,
+    jpeg_huffman: str = "standard",
 ) -> None:
     """
     Same parameter list as the reference API (gance/projection_file_blend.py:56-76). Frames are
@@ -1133,11 +1164,14 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
     is missing. "avi": what write_source_to_disk_forward + add_wavs_to_video write (video_common.py:67-79, 301-376) as
     Motion-JPEG: frames encoded in HBM on rank 0 (torch.ops.gance.jpeg_encode at `jpeg_quality`), an OpenDML AVI at
     `output_path` exactly, the WAVs concatenated as its audio stream (gance_amd/video/mjpeg_avi.py); forces drain="rank0".
-    :raises ValueError: (also) an unknown output_format, or "avi" with an output side that is not a multiple of 16 (checked
+    :param jpeg_huffman: (not a parameter of the reference) "standard" (default): both videos carry the Annex K Huffman
+    tables. "optimized": every frame of both carries its own (torch.ops.gance.jpeg_encode_optimized): the same pixels,
+    smaller files, flat debug panels most of all.
+    :raises ValueError: (also) an unknown output_format or jpeg_huffman, or "avi" with an output side that is not a multiple of 16 (checked
     before any synthesis; with output_side_length None the networks' own side, checked once they are loaded); `debug_path`
     without a `debug_side_length` that is a multiple of 16, or with the overlay on and no `debug_window` (before any synthesis).
     """
-    encode = check_output_arguments(output_format, output_side_length, jpeg_quality, output_fps)
+    encode = check_output_arguments(output_format, output_side_length, jpeg_quality, output_fps, jpeg_huffman)
     drain = drain or os.environ.get("GANCE_STREAM_DRAIN", "rank0")
     overlay_enabled = all(param is not None for param in (phash_distance, bbox_distance, track_length))
     overlay_music_mask_enabled = all(
@@ -1161,9 +1195,10 @@ def projection_file_blend_api(  # pylint: disable=too-many-arguments,too-many-lo
         return projection_file_blend_frame_chunks(
             wav, network_paths, frames_to_visualize, output_fps, output_side_length, alpha, fft_roll_enabled,
             fft_amplitude_range, projection_file_path, blend_depth, overlay=overlay, drain=drain, on_total=on_total,
-            jpeg_quality=quality, debug=debug,
+            jpeg_quality=quality, debug=debug, jpeg_huffman=jpeg_huffman,
         )
 
     write_frame_stream(
-        chunks_of, wav, output_path, output_fps, output_side_length, debug_path, debug_side, debug_window, debug_panels, drain, encode, int(jpeg_quality)
+        chunks_of, wav, output_path, output_fps, output_side_length, debug_path, debug_side, debug_window, debug_panels, drain, encode,
+        int(jpeg_quality), jpeg_huffman,
     )

@@ -9,7 +9,9 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.blend(audio, latent_row0, blend)       [samples] f32, [F, L] f32 -> ([N, depth, L] f32, [N] i32)
     torch.ops.gance.jpeg_encode_rect(frames, quality)      [B, H, W, 3] u8  -> the same for frames that are not square
     torch.ops.gance.jpeg_encode(frames, quality)           [B, S, S, 3] u8  -> ([capacity] u8, [B + 1] i64): B JFIF files
-    torch.ops.gance.png_encode(frames)                     [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
+    torch.ops.gance.jpeg_encode_optimized(frames, quality) [B, H, W, 3] u8  -> the same with each frame's own optimised Huffman tables: smaller files
+    torch.ops.gance.jpeg_optimal_huffman(counts)           [N, 256] i32     -> ([N, 16] u8, [N, 256] u8, [N] i32): bits, values, status of that table build
+    torch.ops.gance.png_encode(frames)              [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
     torch.ops.gance.png_encode_lz(frames)                  [B, H, W, 3] u8  -> the same with an LZ77 match search: no file larger, flat areas far smaller
     torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
     torch.ops.gance.modconv3x3(x, style, demod, weight, up)        [B, Cin, S, S] f32 -> [B, Cout, S or 2S, ...] f32   differentiable
@@ -295,6 +297,73 @@ def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
     batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     _, capacity = hip_lib.jpeg_encode_rect_bounds(batch, width, height)
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+@torch.library.custom_op("gance::jpeg_encode_optimized", mutates_args=(), device_types="cuda")
+def jpeg_encode_optimized(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """
+    `jpeg_encode_rect` with per-frame optimised Huffman tables (libjpeg's optimize_coding, PIL's optimize=True): the same
+    (data, offsets) and capacity, the same decoded pixels, smaller files; each file carries its own four DHT segments, so
+    header lengths differ between frames.
+    """
+    _require_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames must be [B, H, W, 3], got {tuple(frames.shape)}")
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    workspace_bytes, capacity = hip_lib.jpeg_encode_rect_optimized_bounds(batch, width, height)
+    frames = frames.contiguous()
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=frames.device)
+    data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((batch + 1,), dtype=torch.int64, device=frames.device)
+    hip_lib.jpeg_encode_rect_optimized_device(
+        frames.data_ptr(), batch, width, height, int(quality), workspace.data_ptr(), workspace_bytes, data.data_ptr(), capacity,
+        offsets.data_ptr(), _stream(frames),
+    )
+    return data, offsets
+
+
+@jpeg_encode_optimized.register_fake
+def _(frames: torch.Tensor, quality: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    batch, height, width = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    _, capacity = hip_lib.jpeg_encode_rect_optimized_bounds(batch, width, height)
+    return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
+
+
+@torch.library.custom_op("gance::jpeg_optimal_huffman", mutates_args=(), device_types="cuda")
+def jpeg_optimal_huffman(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """
+    The table build of `jpeg_encode_optimized` on given symbol counts [N, 256] i32 (jchuff.c jpeg_gen_optimal_table):
+    (bits [N, 16] u8: codes per length 1..16, values [N, 256] u8: the symbols in code order, status [N] i32: 0 a table,
+    1 a code of more than 32 bits before the limiting, 2 no symbol counted). Bits and values are 0 unless the status is 0.
+    """
+    _require_cuda(counts, torch.int32, "counts")
+    if counts.dim() != 2 or counts.shape[0] < 1 or counts.shape[1] != 256:
+        raise ValueError(f"counts must be [N, 256] with N >= 1, got {tuple(counts.shape)}")
+    counts = counts.contiguous()
+    count = int(counts.shape[0])
+    bits = torch.empty((count, 16), dtype=torch.uint8, device=counts.device)
+    values = torch.empty((count, 256), dtype=torch.uint8, device=counts.device)
+    status = torch.empty((count,), dtype=torch.int32, device=counts.device)
+    hip_lib.jpeg_optimal_tables_device(counts.data_ptr(), count, bits.data_ptr(), values.data_ptr(), status.data_ptr(), _stream(counts))
+    return bits, values, status
+
+
+@jpeg_optimal_huffman.register_fake
+def _(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    count = int(counts.shape[0])
+    return (
+        counts.new_empty((count, 16), dtype=torch.uint8),
+        counts.new_empty((count, 256), dtype=torch.uint8),
+        counts.new_empty((count,), dtype=torch.int32),
+    )
+
+
+def jpeg_encode_op(jpeg_huffman: str, square: bool):  # type: ignore[no-untyped-def]
+    """The encode op of a table mode ("standard" / "optimized", hip_lib.check_jpeg_huffman): `square` picks
+    torch.ops.gance.jpeg_encode over jpeg_encode_rect in the standard mode; the optimised op takes any frames."""
+    if hip_lib.check_jpeg_huffman(jpeg_huffman) == "optimized":
+        return torch.ops.gance.jpeg_encode_optimized
+    return torch.ops.gance.jpeg_encode if square else torch.ops.gance.jpeg_encode_rect
 
 
 def _png_encode(frames: torch.Tensor, bounds, encode_device) -> Tuple[torch.Tensor, torch.Tensor]:  # type: ignore[no-untyped-def]

@@ -398,6 +398,26 @@ int gance_jpeg_encode_rect_u8(const uint8_t* d_frames, int32_t batch, int32_t wi
                               void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
                               int64_t* d_offsets, void* stream);
 
+/* The same files with per-frame optimised Huffman tables (libjpeg's optimize_coding, PIL's optimize=True): each frame's four
+ * DHT segments are jchuff.c's jpeg_gen_optimal_table of that frame's own symbol counts (htest_one_block: DC categories with
+ * the predictors reset per restart interval, AC run/size pairs over the zigzag order, luma into tables 0, Cb and Cr into
+ * tables 1), limited to 16 bits as Annex K.3 does. Quantised coefficients, and so the decoded pixels, are those of
+ * gance_jpeg_encode_rect_u8; only the DHT segments and the entropy-coded bytes differ, and the header length differs per
+ * frame. A frame whose merge gives a code of more than 32 bits (libjpeg's JERR_HUFF_CLEN_OVERFLOW) is coded with the four
+ * Annex K tables. Arguments and checks as gance_jpeg_encode_rect_*; the output capacity is the same, the workspace larger
+ * by about 8.5 KiB per frame. Deterministic (the counts are integer sums); a frame's bytes do not depend on its batch. */
+int gance_jpeg_encode_rect_optimized_bounds(int32_t batch, int32_t width, int32_t height, uint64_t* workspace_bytes,
+                                            uint64_t* out_capacity);
+int gance_jpeg_encode_rect_optimized_u8(const uint8_t* d_frames, int32_t batch, int32_t width, int32_t height, int32_t quality,
+                                        void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, uint64_t out_capacity,
+                                        int64_t* d_offsets, void* stream);
+/* The table build of the above on given counts: d_counts [n][256] int32 (device; negative counts as 0) -> d_bits [n][16]
+ * uint8 (codes per length 1..16), d_values [n][256] uint8 (the symbols in code order, the rest 0) and d_status [n] int32:
+ * 0 a table, 1 a code of more than 32 bits before the limiting (the encoder then uses the Annex K tables), 2 no symbol
+ * counted; bits and values are 0 unless the status is 0. Asynchronous on `stream`. */
+int gance_jpeg_optimal_tables(const int32_t* d_counts, int32_t n, uint8_t* d_bits, uint8_t* d_values, int32_t* d_status,
+                              void* stream);
+
 /* ---- PNG still encoder -------------------------------------------------------------------------
  * Replaces PIL's Image.save(format="PNG") of write_image (gance/image_sources/still_image_common.py:19-28) and of
  * synthesize_images.py:188-191: frames are encoded in HBM as standard PNG files (signature, IHDR with 8-bit depth,
