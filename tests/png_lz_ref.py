@@ -116,3 +116,105 @@ def content(kind: str, height: int, width: int) -> np.ndarray:
     if kind == "tiles":
         return tiles(height, width)
     return alternating(height, width)
+
+
+# ---- inputs that reach the limits of the three codes (tests/test_png_codes.py proves what they claim, without a GPU)
+
+
+def by_magnitude(count: int) -> List[int]:
+    """The byte values 0, 1, 255, 2, 254, ...: the residuals of smallest magnitude first."""
+    return [0] + [value for step in range(1, 129) for value in (step, 256 - step)][: count - 1]
+
+
+def image_of_residuals(residuals: np.ndarray) -> np.ndarray:
+    """The image [H, W, 3] whose Sub-filtered rows are `residuals` [H, 3 W]: the sum along x of each channel, modulo 256."""
+    height = residuals.shape[0]
+    return (np.cumsum(residuals.reshape(height, -1, 3).astype(np.int64), axis=1) % 256).astype(np.uint8)
+
+
+def residual_rows(counts: List[int], height: int, width: int, seed: int, extra_zeros: int = 0) -> np.ndarray:
+    """
+    uint8 [height, 3 width]: counts[k] times the k-th value of `by_magnitude`, shuffled, with `extra_zeros` zeros behind
+    them. The caller has taken the rows' filter bytes out of the counts.
+    """
+    values = by_magnitude(len(counts))
+    residuals = np.concatenate([np.full(count, value, dtype=np.uint8) for value, count in zip(values, counts)])
+    np.random.RandomState(seed).shuffle(residuals)
+    residuals = np.concatenate([residuals, np.zeros(extra_zeros, dtype=np.uint8)])
+    assert len(residuals) == height * 3 * width, (len(residuals), height * 3 * width)
+    return residuals.reshape(height, 3 * width)
+
+
+FIBONACCI_SHAPE = (95, 100)  # one segment of 28 595 bytes
+
+
+def fibonacci_image() -> np.ndarray:
+    """
+    One segment whose byte counts are twenty Fibonacci numbers, 1, 2, 3, 5 ... 10946 (sum 28 655), the most frequent on
+    value 0: the 95 filter bytes (Sub: 1) come out of value 1's count, the other 60 bytes out of value 0's. With
+    end-of-block 21 used symbols whose unrestricted Huffman code is 19 bits deep.
+    """
+    height, width = FIBONACCI_SHAPE
+    series = [1, 2]
+    while len(series) < 20:
+        series.append(series[-1] + series[-2])
+    counts = series[::-1]
+    counts[1] -= height
+    counts[0] -= sum(counts) - height * 3 * width
+    return image_of_residuals(residual_rows(counts, height, width, seed=41))
+
+
+FIBONACCI_FLAT_SHAPE = (108, 100)  # one segment of 32 508 bytes
+
+
+def fibonacci_flat_image() -> np.ndarray:
+    """
+    For the match search: 60 rows of nineteen Fibonacci counts (1 ... 6765) above 48 rows of zeros, which the
+    literal-only form pays a code each for and a match search takes as a few matches of distance 1. Few byte values with
+    Fibonacci counts repeat their triples all the time, and the greedy parse's short matches then cost more than the zeros
+    save; so each of the six largest counts is shared evenly among 16 byte values (the value 1, which the Sub filter bytes
+    add to, is one of the first 16). The literal-only block is 17 bits deep. The block with matches is not deeper than 15
+    (measured: 13): the length symbols' counts fall between the Fibonacci counts and pair with them.
+    """
+    height, width = FIBONACCI_FLAT_SHAPE
+    rows, split, group = 60, 6, 16
+    series = [1, 2]
+    while len(series) < 19:
+        series.append(series[-1] + series[-2])
+    counts: List[int] = []
+    for index, count in enumerate(series[::-1]):
+        counts += [-(-count // group)] * group if index < split else [count]
+    counts[1] -= rows
+    counts[0] -= sum(counts) - rows * 3 * width
+    return image_of_residuals(residual_rows(counts, height, width, seed=43, extra_zeros=(height - rows) * 3 * width))
+
+
+DYADIC_SHAPE = (109, 100)  # 32 809 bytes: one whole segment and 41 bytes
+DYADIC_PROFILE = {1: 1, 4: 3, 7: 34, 8: 8, 11: 13, 12: 21, 13: 5, 14: 2, 15: 112}  # code length: symbols; Kraft sum one
+
+
+def dyadic_image() -> np.ndarray:
+    """
+    A first segment whose symbol counts are powers of two, 2^(15 - L) for the numbers of symbols per L of DYADIC_PROFILE
+    (the last 15-bit place is end-of-block's), so that its Huffman code has exactly these lengths: 32 767 bytes, of which
+    the segment's 109 filter bytes are 109 of value 1's 2048; the segment's one byte more is another 0. The 257 literal
+    lengths and the one distance length then occur 58 (unused), 2, 3, 34, 8, 13, 21, 5, 2 and 112 times: a code-length
+    histogram whose unrestricted code is 9 bits deep, over the limit of 7. The 41 bytes of the second segment are zeros.
+    """
+    height, width = DYADIC_SHAPE
+    counts = [1 << (15 - length) for length, number in sorted(DYADIC_PROFILE.items()) for _ in range(number)][:-1]
+    filter_bytes = -(-SEGMENT // (3 * width + 1))
+    counts[1] -= filter_bytes
+    counts[0] += 1
+    assert sum(counts) == SEGMENT - filter_bytes
+    return image_of_residuals(residual_rows(counts, height, width, seed=47, extra_zeros=height * (3 * width + 1) - SEGMENT))
+
+
+def limit_inputs() -> List[Tuple[str, np.ndarray]]:
+    """The inputs of tests/test_png_codes_gpu.py beyond SHAPES x CONTENTS; scene(256, 2) has a real segment of depth 16."""
+    return [
+        ("fibonacci", fibonacci_image()),
+        ("fibonacci_flat", fibonacci_flat_image()),
+        ("dyadic", dyadic_image()),
+        ("scene256", scene(256, 2)),
+    ]
