@@ -124,6 +124,9 @@ struct gance_workspace {
     int device = 0, resolution = 0, max_batch = 0;
     float *dlat = nullptr, *map_a = nullptr, *map_b_buf = nullptr, *z_in = nullptr;
     float *styles = nullptr, *demod = nullptr;
+    // whose call last filled styles / demod, and with how many samples (the debug taps that read them back check both)
+    const void* front_owner = nullptr;
+    int front_batch = 0;
     std::vector<float*> act;      // per conv layer: zero-bordered output [Bmax][cout][res+2][res+8]
     std::vector<float*> tplanes;  // per up layer: [4 cls][max_units][cout][H+3][W+8] (else nullptr)
     float* slabs = nullptr;       // split-K scratch of the small stride-1 convs (dense)
@@ -538,6 +541,8 @@ int synthesize_from_dlat(gance_engine* e, const float* d_dlat, int B, uint8_t* d
                                             (int)e->convs.size(), e->ws->demod, B, e->ctot, e->dtot,
                                             stream));
     }
+    e->ws->front_owner = e;
+    e->ws->front_batch = B;
     const std::vector<LayerStep> plan = plan_call(e->convs, e->caps, e->tune, e->cfg.flags, e->num_cus, B, e->debug_stop_after);
 
     int ycur = 0;  // ybuf index holding the current skip image
@@ -1075,12 +1080,13 @@ int gance_synthesize_w(gance_engine* engine, const float* d_dlatents, int32_t ba
     return synthesize_from_dlat(engine, d_dlatents, batch, d_out_u8, d_out_f32, (hipStream_t)stream);
 }
 
-// mapping network + truncation + synthesis (no ordering against other users of the workspace: the callers do that)
-static int synthesize_from_z(gance_engine* engine, const float* d_z, int32_t batch, float truncation_psi, uint8_t* d_out_u8,
-                             float* d_out_f32, hipStream_t stream) {
+// The first `num_layers` dense layers of the mapping network (pixel-norm of z in the first), ping-ponging between the
+// workspace's two buffers; *out is where the last of them wrote [batch][512]. The whole network for a call, fewer for the
+// debug tap.
+static int run_mapping(gance_engine* engine, const float* d_z, int32_t batch, int num_layers, hipStream_t stream, const float** out) {
     const float* in = d_z;
     float* bufs[2] = {engine->ws->map_a, engine->ws->map_b_buf};
-    for (int i = 0; i < kMappingLayers; ++i) {
+    for (int i = 0; i < num_layers; ++i) {
         StepScope scope(engine, stream, "mapping_dense", 2.0 * batch * kDlatent * kDlatent,
                         4.0 * kDlatent * kDlatent);
         GANCE_HIP_CHECK(gance::launch_mapping_dense(in, engine->pool + engine->map_w[i],
@@ -1088,12 +1094,25 @@ static int synthesize_from_z(gance_engine* engine, const float* d_z, int32_t bat
                                                     batch, i == 0, stream));
         in = bufs[i & 1];
     }
-    {
-        StepScope scope(engine, stream, "truncate", 0.0, 0.0);
-        GANCE_HIP_CHECK(gance::launch_broadcast_truncate(in, engine->pool + engine->avg_off,
-                                                         truncation_psi, engine->ws->dlat, batch,
-                                                         engine->num_rows, stream));
-    }
+    *out = in;
+    return GANCE_OK;
+}
+
+// mapping network + truncation into the workspace's dlatent buffer [batch][num_rows][512]
+static int run_mapping_and_truncation(gance_engine* engine, const float* d_z, int32_t batch, float truncation_psi, hipStream_t stream) {
+    const float* mapped = nullptr;
+    if (int rc = run_mapping(engine, d_z, batch, kMappingLayers, stream, &mapped)) return rc;
+    StepScope scope(engine, stream, "truncate", 0.0, 0.0);
+    GANCE_HIP_CHECK(gance::launch_broadcast_truncate(mapped, engine->pool + engine->avg_off,
+                                                     truncation_psi, engine->ws->dlat, batch,
+                                                     engine->num_rows, stream));
+    return GANCE_OK;
+}
+
+// mapping network + truncation + synthesis (no ordering against other users of the workspace: the callers do that)
+static int synthesize_from_z(gance_engine* engine, const float* d_z, int32_t batch, float truncation_psi, uint8_t* d_out_u8,
+                             float* d_out_f32, hipStream_t stream) {
+    if (int rc = run_mapping_and_truncation(engine, d_z, batch, truncation_psi, stream)) return rc;
     return synthesize_from_dlat(engine, engine->ws->dlat, batch, d_out_u8, d_out_f32, stream);
 }
 
@@ -1172,6 +1191,8 @@ static int host_call(gance_engine* e, const float* h_in, size_t in_floats, int b
     }
     if (rc) return rc;
     if (!plain) e->last_rgb_y = nullptr;  // (a replayed graph's launches were recorded by another call)
+    ws->front_owner = e;  // (a replayed graph does not pass through synthesize_from_dlat)
+    ws->front_batch = batch;
     if (e->debug_stop_after > 0) {
         GANCE_HIP_CHECK(hipStreamSynchronize(hs));
         hipEventRecord(ws->last_use, hs);
@@ -1360,6 +1381,88 @@ int gance_engine_debug_read_skip_image(gance_engine* engine, int32_t batch, floa
     GANCE_HIP_CHECK(hipMemcpy(h_out, engine->last_rgb_y, n * sizeof(float), hipMemcpyDeviceToHost));
     if (out_side) *out_side = R;
     return GANCE_OK;
+}
+
+// The front end of a z call alone, eagerly on the workspace's host stream: z from host memory, the first `num_dense_layers`
+// mapping layers (run_mapping, the call's own loop) or, with `truncate`, all of them and the truncation; then the result,
+// [batch][512] or [batch][num_rows][512], to host memory. Ordered against the other users of the shared workspace as host_call is.
+static int debug_front_end_of_z(gance_engine* e, const float* h_z, int batch, int num_dense_layers, bool truncate, float psi,
+                                float* h_out, uint64_t max_floats, const char* who) {
+    if (h_out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": output pointer is NULL");
+    if (int rc = check_call(e, h_z, batch)) return rc;
+    if (num_dense_layers < 1 || num_dense_layers > kMappingLayers)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": the mapping network has " + std::to_string(kMappingLayers) +
+                                                    " dense layers, asked for " + std::to_string(num_dense_layers));
+    const size_t n = (size_t)batch * (truncate ? e->num_rows : 1) * kDlatent;
+    if (n > max_floats)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": the result holds " + std::to_string(n) + " floats, the buffer " + std::to_string(max_floats));
+    gance::DeviceGuard guard(e->cfg.device);
+    GANCE_HIP_CHECK(guard.status());
+    gance_workspace* ws = e->ws.get();
+    if (ws->used) GANCE_HIP_CHECK(hipEventSynchronize(ws->last_use));  // another engine's call may still read the shared scratch
+    hipStream_t hs = ws->host_stream;
+    const size_t in_floats = (size_t)batch * kDlatent;
+    std::memcpy(ws->pinned_in, h_z, in_floats * sizeof(float));
+    GANCE_HIP_CHECK(hipMemcpyAsync(ws->z_in, ws->pinned_in, in_floats * sizeof(float), hipMemcpyHostToDevice, hs));
+    if (e->profile_only.empty() || e->steps_used >= 4096) e->steps_used = 0;
+    const float* result = ws->dlat;
+    const int rc = truncate ? run_mapping_and_truncation(e, ws->z_in, batch, psi, hs) : run_mapping(e, ws->z_in, batch, num_dense_layers, hs, &result);
+    hipEventRecord(ws->last_use, hs);
+    ws->used = true;
+    if (rc) return rc;
+    GANCE_HIP_CHECK(hipStreamSynchronize(hs));
+    GANCE_HIP_CHECK(hipMemcpy(h_out, result, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GANCE_OK;
+}
+
+int gance_engine_debug_mapping(gance_engine* engine, const float* h_z, int32_t batch, int32_t num_dense_layers, float* h_out,
+                               uint64_t max_floats) {
+    return debug_front_end_of_z(engine, h_z, batch, num_dense_layers, false, 0.f, h_out, max_floats, "gance_engine_debug_mapping");
+}
+
+int gance_engine_debug_dlatents(gance_engine* engine, const float* h_z, int32_t batch, float truncation_psi, float* h_out,
+                                uint64_t max_floats) {
+    return debug_front_end_of_z(engine, h_z, batch, kMappingLayers, true, truncation_psi, h_out, max_floats, "gance_engine_debug_dlatents");
+}
+
+// `width` columns from `column` on of the rows [batch][row_floats] that the engine's last w-call left at `d_rows`
+static int debug_read_front_columns(gance_engine* e, const float* d_rows, int row_floats, int column, int width, int batch, float* h_out,
+                                    uint64_t max_floats, const char* who) {
+    const gance_workspace* ws = e->ws.get();
+    if (ws->front_owner != e || ws->front_batch < 1)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": the workspace's last call was not this engine's");
+    if (batch != ws->front_batch)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": the engine's last call had " + std::to_string(ws->front_batch) +
+                                                    " samples, not " + std::to_string(batch));
+    const size_t n = (size_t)batch * width;
+    if (n > max_floats)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, std::string(who) + ": the result holds " + std::to_string(n) + " floats, the buffer " + std::to_string(max_floats));
+    gance::DeviceGuard guard(e->cfg.device);
+    GANCE_HIP_CHECK(guard.status());
+    GANCE_HIP_CHECK(hipDeviceSynchronize());
+    GANCE_HIP_CHECK(hipMemcpy2D(h_out, (size_t)width * sizeof(float), d_rows + column, (size_t)row_floats * sizeof(float),
+                                (size_t)width * sizeof(float), (size_t)batch, hipMemcpyDeviceToHost));
+    return GANCE_OK;
+}
+
+int gance_engine_debug_read_style(gance_engine* e, int32_t kind, int32_t index, int32_t batch, float* h_out, uint64_t max_floats) {
+    if (e == nullptr || h_out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_style: NULL argument");
+    if (kind != 0 && kind != 1) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_style: kind is 0 (a conv layer) or 1 (a ToRGB)");
+    const int count = kind == 0 ? (int)e->convs.size() : (int)e->rgbs.size();
+    if (index < 0 || index >= count)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_style: layer " + std::to_string(index) + " outside [0, " + std::to_string(count) + ")");
+    const int column = kind == 0 ? e->conv_s_off[index] : e->rgb_s_off[index];
+    const int width = kind == 0 ? e->convs[index].cin : e->rgbs[index].cin;
+    return debug_read_front_columns(e, e->ws->styles, e->ctot, column, width, batch, h_out, max_floats, "gance_engine_debug_read_style");
+}
+
+int gance_engine_debug_read_demod(gance_engine* e, int32_t conv_layer, int32_t batch, float* h_out, uint64_t max_floats) {
+    if (e == nullptr || h_out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_demod: NULL argument");
+    if (conv_layer < 0 || conv_layer >= (int)e->convs.size())
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_read_demod: layer " + std::to_string(conv_layer) + " outside [0, " +
+                                                    std::to_string(e->convs.size()) + ")");
+    return debug_read_front_columns(e, e->ws->demod, e->dtot, e->conv_d_off[conv_layer], e->convs[conv_layer].cout, batch, h_out, max_floats,
+                                    "gance_engine_debug_read_demod");
 }
 
 int gance_resize_bicubic_u8(const uint8_t* d_in, int32_t batch, int32_t src_side, uint8_t* d_out,

@@ -149,6 +149,10 @@ SIGNATURES = {
     "gance_engine_debug_read_skip_image": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _F32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)]
     ),
+    "gance_engine_debug_mapping": (ctypes.c_int, [ctypes.c_void_p, _F32P, ctypes.c_int32, ctypes.c_int32, _F32P, ctypes.c_uint64]),
+    "gance_engine_debug_dlatents": (ctypes.c_int, [ctypes.c_void_p, _F32P, ctypes.c_int32, ctypes.c_float, _F32P, ctypes.c_uint64]),
+    "gance_engine_debug_read_style": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F32P, ctypes.c_uint64]),
+    "gance_engine_debug_read_demod": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _F32P, ctypes.c_uint64]),
     "gance_blend_create": (
         ctypes.c_int,
         [ctypes.POINTER(BlendConfig), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)],
@@ -437,7 +441,8 @@ ADDED_WITHIN_ABI = {
     "gance_lpips_input_backward", "gance_bias_relu_forward", "gance_bias_relu_backward", "gance_lpips_layer_workspace_bytes",
     "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize", "gance_conv3x3_form",
     "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward", "gance_jpeg_encode_rect_optimized_bounds",
-    "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables",
+    "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables", "gance_engine_debug_mapping", "gance_engine_debug_dlatents",
+    "gance_engine_debug_read_style", "gance_engine_debug_read_demod",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -783,6 +788,94 @@ class Engine:
             return out
         finally:
             self._lib.gance_engine_debug_stop_after(self._handle, 0)
+
+    # ---- the part of a call in front of the first convolution, stage by stage ----
+
+    def _z_of(self, z: np.ndarray) -> np.ndarray:
+        zz = _f32(z)
+        if zz.ndim != 2 or zz.shape[1] != self.vector_length:
+            raise ValueError(f"z must be [B, {self.vector_length}], got {zz.shape}")
+        return zz
+
+    def debug_mapping_after(self, z: np.ndarray, num_dense_layers: int) -> np.ndarray:
+        """The output [B, 512] of the first `num_dense_layers` (1 ... 8) dense layers of the mapping network for z [B, 512]."""
+        self._require_open()
+        zz = self._z_of(z)
+        out = np.empty((zz.shape[0], self.vector_length), dtype=np.float32)
+        _check(
+            self._lib,
+            self._lib.gance_engine_debug_mapping(
+                self._handle, zz.ctypes.data_as(_F32P), zz.shape[0], num_dense_layers, out.ctypes.data_as(_F32P), ctypes.c_uint64(out.size)
+            ),
+        )
+        return out
+
+    def debug_dlatents(self, z: np.ndarray, truncation_psi: float) -> np.ndarray:
+        """The dlatents [B, num_layers, 512] a z call hands to synthesis: mapping network, then truncation with `truncation_psi`."""
+        self._require_open()
+        zz = self._z_of(z)
+        out = np.empty((zz.shape[0], self.num_layers, self.vector_length), dtype=np.float32)
+        _check(
+            self._lib,
+            self._lib.gance_engine_debug_dlatents(
+                self._handle, zz.ctypes.data_as(_F32P), zz.shape[0], ctypes.c_float(truncation_psi), out.ctypes.data_as(_F32P),
+                ctypes.c_uint64(out.size),
+            ),
+        )
+        return out
+
+    def debug_run_front_end(self, dlatents: np.ndarray) -> int:
+        """
+        A w-call stopped after the first conv layer: styles and demodulation of EVERY layer are computed in front of it and
+        stay in the workspace for `debug_read_style` / `debug_read_demod`. Returns the batch.
+        """
+        self._require_open()
+        dl = _f32(dlatents)
+        if dl.ndim != 3 or dl.shape[1] != self.num_layers or dl.shape[2] != self.vector_length:
+            raise ValueError(f"dlatents must be [B, {self.num_layers}, {self.vector_length}], got {dl.shape}")
+        _check(self._lib, self._lib.gance_engine_debug_stop_after(self._handle, 1))
+        try:
+            _check(self._lib, self._lib.gance_synthesize_w_host(self._handle, dl.ctypes.data_as(_F32P), dl.shape[0], None, None))
+        finally:
+            self._lib.gance_engine_debug_stop_after(self._handle, 0)
+        return dl.shape[0]
+
+    def debug_read_style(self, batch: int, kind: str, index: int) -> np.ndarray:
+        """The style [batch, cin] of conv layer `index` (kind "conv") or ToRGB `index` (kind "torgb", 0 = 4x4) of the engine's last call."""
+        self._require_open()
+        spec = sg2_spec.make_spec(self.resolution, self.fmap_base)
+        layers = {"conv": spec.convs, "torgb": spec.torgbs}[kind]
+        if not 0 <= index < len(layers):
+            raise ValueError(f"{kind} index must be in [0, {len(layers)}), got {index}")
+        out = np.empty((batch, layers[index].cin), dtype=np.float32)
+        _check(
+            self._lib,
+            self._lib.gance_engine_debug_read_style(
+                self._handle, 0 if kind == "conv" else 1, index, batch, out.ctypes.data_as(_F32P), ctypes.c_uint64(out.size)
+            ),
+        )
+        return out
+
+    def debug_read_demod(self, batch: int, conv_index: int) -> np.ndarray:
+        """The demodulation coefficients [batch, cout] of conv layer `conv_index` of the engine's last call."""
+        self._require_open()
+        convs = sg2_spec.make_spec(self.resolution, self.fmap_base).convs
+        if not 0 <= conv_index < len(convs):
+            raise ValueError(f"conv_index must be in [0, {len(convs)}), got {conv_index}")
+        out = np.empty((batch, convs[conv_index].cout), dtype=np.float32)
+        _check(
+            self._lib,
+            self._lib.gance_engine_debug_read_demod(self._handle, conv_index, batch, out.ctypes.data_as(_F32P), ctypes.c_uint64(out.size)),
+        )
+        return out
+
+    def debug_style(self, dlatents: np.ndarray, kind: str, index: int) -> np.ndarray:
+        """Style [B, cin] of one conv or ToRGB layer for dlatents [B, W, 512] (a stopped w-call, then the read)."""
+        return self.debug_read_style(self.debug_run_front_end(dlatents), kind, index)
+
+    def debug_demod(self, dlatents: np.ndarray, conv_index: int) -> np.ndarray:
+        """Demodulation coefficients [B, cout] of one conv layer for dlatents [B, W, 512] (a stopped w-call, then the read)."""
+        return self.debug_read_demod(self.debug_run_front_end(dlatents), conv_index)
 
 
 # stage ids of `enum gance_blend_stage`: name -> (id, dtype, per-frame width or None for [N])

@@ -188,6 +188,24 @@ int gance_engine_debug_read_activation(gance_engine* engine, int32_t batch, floa
  * when `batch` is not that call's, or when the image exceeds `max_floats`.
  */
 int gance_engine_debug_read_skip_image(gance_engine* engine, int32_t batch, float* h_out, uint64_t max_floats, int32_t* out_side);
+/*
+ * Debug: the part of a call in front of the first convolution, stage by stage, host memory in and out (each returns after
+ * completion). All four return GANCE_ERR_INVALID_ARGUMENT, and write nothing, for a NULL argument, a batch outside
+ * [1, max_batch], a layer out of range or a result larger than `max_floats`.
+ * gance_engine_debug_mapping: the output [batch][512] of the first `num_dense_layers` (1 ... 8) dense layers of the mapping
+ * network for z [batch][512], through the launch loop gance_synthesize_z runs.
+ * gance_engine_debug_dlatents: the dlatents [batch][num_layers][512] that gance_synthesize_z would hand to synthesis.
+ * gance_engine_debug_read_style / _read_demod: the style vector [batch][cin] of conv layer `index` (kind 0) or of ToRGB
+ * `index` (kind 1, 0 = 4x4), and the demodulation vector [batch][cout] of conv layer `conv_layer`, as the engine's last
+ * synthesize_w / synthesize_z call of `batch` samples left them (a call stopped by gance_engine_debug_stop_after will do:
+ * both are computed before the first layer). Refused when another engine of the shared workspace made the last call.
+ */
+int gance_engine_debug_mapping(gance_engine* engine, const float* h_z, int32_t batch, int32_t num_dense_layers, float* h_out,
+                               uint64_t max_floats);
+int gance_engine_debug_dlatents(gance_engine* engine, const float* h_z, int32_t batch, float truncation_psi, float* h_out,
+                                uint64_t max_floats);
+int gance_engine_debug_read_style(gance_engine* engine, int32_t kind, int32_t index, int32_t batch, float* h_out, uint64_t max_floats);
+int gance_engine_debug_read_demod(gance_engine* engine, int32_t conv_layer, int32_t batch, float* h_out, uint64_t max_floats);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Audio -> latent: spectrogram, fft-roll, alpha blend with projected latents                  */

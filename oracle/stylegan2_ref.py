@@ -107,6 +107,33 @@ def apply_bias_act(x: torch.Tensor, b: torch.Tensor, act: str, lrmul: float = 1.
     raise ValueError(act)
 
 
+def layer_style(y: torch.Tensor, variables: Variables, scope: str) -> torch.Tensor:
+    """
+    The style of a modulated conv: the dense layer of `modulated_conv2d_layer` with bias_var='mod_bias' and the `+ 1`.
+    `y` [B, 512] is the layer's dlatent row; returns s [B, I]. modulated_conv2d_layer calls this, so a style checked in
+    isolation is checked against exactly the arithmetic of the whole chain.
+    """
+    dtype = y.dtype
+    mod_w = _get_weight(_t(variables, f"{scope}/mod_weight", dtype))  # [512, I]
+    s = y @ mod_w
+    return s + _t(variables, f"{scope}/mod_bias", dtype)[None] + 1.0  # [B,I]
+
+
+def modulate_weight(w: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The runtime-scaled weight [k,k,I,O] times the style [B,I] of every sample: [B,k,k,I,O]."""
+    return w[None] * s[:, None, None, :, None]
+
+
+def layer_demodulation(s: torch.Tensor, w: torch.Tensor, modulated: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """
+    The demodulation coefficients of a modulated conv from its style `s` [B, I] and runtime-scaled weight `w` [k,k,I,O]:
+    d [B, O] = rsqrt(sum over k,k,I of (w s)^2 + 1e-8). modulated_conv2d_layer calls this (handing over the
+    `modulate_weight(w, s)` it has already, so that the product exists once, in the result and in the autograd graph).
+    """
+    ww = modulate_weight(w, s) if modulated is None else modulated
+    return torch.rsqrt((ww ** 2).sum(dim=(1, 2, 3)) + 1e-8)  # [B,O]
+
+
 def modulated_conv2d_layer(
     x: torch.Tensor,
     y: torch.Tensor,
@@ -121,13 +148,10 @@ def modulated_conv2d_layer(
     batch, cin, h, w_ = x.shape
     w = _get_weight(_t(variables, f"{scope}/weight", dtype))  # [k,k,I,O]
     cout = w.shape[-1]
-    ww = w[None]  # [B,k,k,I,O]
-    mod_w = _get_weight(_t(variables, f"{scope}/mod_weight", dtype))  # [512, I]
-    s = y @ mod_w
-    s = s + _t(variables, f"{scope}/mod_bias", dtype)[None] + 1.0  # [B,I]
-    ww = ww * s[:, None, None, :, None]
+    s = layer_style(y, variables, scope)  # [B,I]
+    ww = modulate_weight(w, s)  # [B,k,k,I,O]
     if demodulate:
-        d = torch.rsqrt((ww ** 2).sum(dim=(1, 2, 3)) + 1e-8)  # [B,O]
+        d = layer_demodulation(s, w, modulated=ww)  # [B,O]
         ww = ww * d[:, None, None, None, :]
     # grouped conv: x -> [1, B*I, H, W], weight -> [B*O, I, k, k]
     xg = x.reshape(1, batch * cin, h, w_)
@@ -139,13 +163,24 @@ def modulated_conv2d_layer(
     return out.reshape(batch, cout, out.shape[2], out.shape[3])
 
 
+def mapping_dense_layer(x: torch.Tensor, variables: Variables, index: int, normalize: bool = False) -> torch.Tensor:
+    """
+    Dense layer `index` (0 ... 7) of `G_mapping` on x [B, 512]: lrmul 0.01 on weight and bias, lrelu * sqrt(2); with
+    `normalize` (the first layer) the pixel-norm of the latents in front of it. g_mapping calls this for every layer, so a
+    layer checked in isolation is checked against exactly the arithmetic of the whole chain.
+    """
+    dtype = x.dtype
+    if normalize:
+        x = x * torch.rsqrt((x ** 2).mean(dim=1, keepdim=True) + 1e-8)
+    w = _get_weight(_t(variables, f"G_mapping/Dense{index}/weight", dtype), lrmul=0.01)
+    return apply_bias_act(x @ w, _t(variables, f"G_mapping/Dense{index}/bias", dtype), "lrelu", lrmul=0.01)
+
+
 def g_mapping(latents: torch.Tensor, variables: Variables, num_layers: int) -> torch.Tensor:
     """`G_mapping`: normalise z, 8 dense layers (lrmul 0.01, lrelu*sqrt2), broadcast to W rows."""
-    dtype = latents.dtype
-    x = latents * torch.rsqrt((latents ** 2).mean(dim=1, keepdim=True) + 1e-8)
+    x = latents
     for i in range(8):
-        w = _get_weight(_t(variables, f"G_mapping/Dense{i}/weight", dtype), lrmul=0.01)
-        x = apply_bias_act(x @ w, _t(variables, f"G_mapping/Dense{i}/bias", dtype), "lrelu", lrmul=0.01)
+        x = mapping_dense_layer(x, variables, i, normalize=i == 0)
     return x[:, None, :].repeat(1, num_layers, 1)
 
 

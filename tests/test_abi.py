@@ -72,6 +72,25 @@ def test_bad_arguments_are_rejected_before_touching_a_device(library: ctypes.CDL
     library.gance_engine_destroy(None)  # NULL is a no-op
 
 
+FRONT_END_TAPS = ("gance_engine_debug_mapping", "gance_engine_debug_dlatents", "gance_engine_debug_read_style", "gance_engine_debug_read_demod")
+
+
+def test_the_front_end_taps_came_within_abi_6_and_refuse_a_null_engine(library: ctypes.CDLL) -> None:
+    names = declared_functions()
+    for name in FRONT_END_TAPS:
+        assert name in names and name in hip_lib.ADDED_WITHIN_ABI and hasattr(library, name), name
+    assert hip_lib.ADDED_WITHIN_ABI <= set(hip_lib.SIGNATURES)
+    out = np.full(8, 7.0, dtype=np.float32)
+    z = np.zeros(512, dtype=np.float32)
+    pointer, z_pointer = out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), z.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    # GANCE_ERR_INVALID_ARGUMENT before a device is touched, and nothing written
+    assert library.gance_engine_debug_mapping(None, z_pointer, 1, 8, pointer, ctypes.c_uint64(8)) == 1
+    assert library.gance_engine_debug_dlatents(None, z_pointer, 1, ctypes.c_float(0.7), pointer, ctypes.c_uint64(8)) == 1
+    assert library.gance_engine_debug_read_style(None, 0, 0, 1, pointer, ctypes.c_uint64(8)) == 1
+    assert library.gance_engine_debug_read_demod(None, 0, 1, pointer, ctypes.c_uint64(8)) == 1
+    assert b"NULL" in library.gance_last_error() and np.all(out == 7.0)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_no_gpu_means_loud_failure_not_cpu_fallback(library: ctypes.CDLL) -> None:
     variables = sg2_spec.make_random_variables(8, seed=0)
