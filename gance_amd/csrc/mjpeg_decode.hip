@@ -1,25 +1,31 @@
 // Baseline JPEG decoder for frames in HBM: gance_jpeg_parse_header / gance_jpeg_decode_bounds / gance_jpeg_decode_u8 of
-// include/gance_hip.h, the reverse of mjpeg.hip. Input: baseline sequential JFIF (SOF0, 8 bit), three components sampled
-// 2x1 / 1x1 / 1x1 (4:2:2) in one interleaved scan, any 8-bit DQT, any DHT or none (then the Annex K tables), any DRI or
-// none, width and height in [1, 8192]. Output: uint8 [batch][height][width][3] RGB, equal to libjpeg's default decode:
+// include/gance_hip.h (4:2:2 only, the reverse of mjpeg.hip) and gance_jpeg_parse_header_layouts /
+// gance_jpeg_decode_layouts_bounds / gance_jpeg_decode_layouts_u8 (the same code for four layouts). Input: baseline
+// sequential JFIF (SOF0, 8 bit), one interleaved scan of three components sampled 2x1 / 1x1 / 1x1 (4:2:2), 2x2 / 1x1 / 1x1
+// (4:2:0) or 1x1 / 1x1 / 1x1 (4:4:4), or of one component (grey), any 8-bit DQT, any DHT or none (then the Annex K tables),
+// any DRI or none, width and height in [1, 8192]; all frames of a call of one size and layout. Output: uint8
+// [batch][height][width][3] RGB (grey: three equal channels), equal to libjpeg's default decode:
 //
 //   entropy decode      jdhuff.c decode_mcu: DC difference and AC run/size symbols with EXTEND; 0xFF 0x00 reads as 0xFF; the
 //                       DC predictors restart with every restart segment
 //   dequantise + IDCT   jidctint.c jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, columns then rows, the sample saturated
 //                       to 0..255 as libjpeg-turbo's SIMD islow does (jidctint-sse2 / -avx2 / -neon pack with saturation;
 //                       the C fallback's range-limit table wraps past +-512 instead: see DESIGN.md section 9 item 9)
-//   chroma upsampling   jdsample.c h2v1_fancy_upsample over the true downsampled width ceil(W / 2)
+//   chroma upsampling   jdsample.c over the component's true size: h2v1_fancy_upsample (4:2:2), h2v2_fancy_upsample (4:2:0),
+//                       replication for both when the chroma width ceil(W / 2) is at most 2, none for 4:4:4
 //   colour              jdcolor.c ycc_rgb_convert: 16-bit fixed point, arithmetic shifts, clamped
 //
 // Four launches on the caller's stream, no atomics on pixels, every frame independent of the others:
 //   1. mjpeg_marker_scan_kernel   one workgroup per frame: the RSTn markers of its entropy-coded data compacted in order
 //                                 into marker positions, the end of the data (EOI), and the frame's status when the
 //                                 marker count or sequence is wrong (such a frame is not decoded)
-//   2. mjpeg_entropy_kernel       one thread per restart segment: Huffman decode through a 9-bit look-ahead table in LDS
-//                                 (longer codes by the canonical maxcode walk), int16 coefficients in natural order staged
-//                                 in a private LDS slot and written as whole 128-byte blocks
+//   2. mjpeg_entropy_kernel<n>    (n = 4, 6, 3 or 1 blocks per MCU: the layout) one thread per restart segment: Huffman
+//                                 decode through a 9-bit look-ahead table in LDS (longer codes by the canonical maxcode
+//                                 walk), int16 coefficients in natural order staged in a private LDS slot and written as
+//                                 whole 128-byte blocks
 //   3. mjpeg_idct_kernel          one thread per 8x8 block: dequantise, IDCT, range limit -> Y, Cb, Cr planes
-//   4. mjpeg_colour_kernel        one thread per 16 pixels of a row: chroma upsampling across block edges, colour, RGB
+//   4. mjpeg_colour_kernel<l>     (l = the layout) one thread per 16 pixels of a row: chroma upsampling across block
+//                                 edges, colour, RGB
 // Bounds: every read of compressed bytes lies inside the frame's scan range [scan_begin, scan_begin + scan_bytes), every
 // coefficient index is below 64, a segment decodes at most its own MCUs, and a code that is not in the table ends the
 // segment. The Huffman look-up tables are built on the host once per distinct set of tables of a call.
@@ -33,13 +39,11 @@
 
 #include "../../include/gance_hip.h"
 #include "kernels.h"
+#include "mjpeg_decode_header.h"
 #include "mjpeg_tables.h"
 
 namespace gance_mjpeg_decode {
 
-using gance_mjpeg::natural_of_zigzag;
-
-constexpr int kMaxSide = 8192;
 constexpr int kLookBits = 9;
 constexpr int kScanThreads = 256;
 constexpr int kScanChunk = 16;  // bytes per thread and tile of the marker scan
@@ -68,29 +72,35 @@ struct alignas(16) FrameDesc {
 
 // ---- sizes -------------------------------------------------------------------------------------------------------
 struct Layout {
-    int64_t mcu_cols, mcu_rows, mcus;  // per frame; an MCU is 16 x 8 pixels: Y left, Y right, Cb, Cr
-    int64_t luma_width, chroma_width, plane_rows;
+    LayoutShape shape;
+    int64_t mcu_cols, mcu_rows, mcus;  // per frame; an MCU is 8 * shape.h by 8 * shape.v pixels
+    // Rows of the planes are `stride` bytes apart: the blocks' own width where the colour kernel reads 8 bytes per 16
+    // pixels (4:2:2 and 4:2:0 chroma) or the width is a multiple of 16 anyway, rounded up to 16 where it reads 16 bytes
+    // per 16 pixels of a plane that is a whole number of 8-wide blocks (4:4:4 and grey).
+    int64_t luma_stride, luma_rows, chroma_stride, chroma_rows;
     int64_t params_bytes, marker_bytes, end_bytes, coef_bytes, luma_bytes, chroma_bytes, workspace_bytes;
     int64_t max_markers;
 };
 
 static int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
 
-static Layout layout_of(int64_t batch, int64_t width, int64_t height) {
+static Layout layout_of(int64_t batch, int64_t width, int64_t height, int layout) {
     Layout l{};
-    l.mcu_cols = (width + 15) / 16;
-    l.mcu_rows = (height + 7) / 8;
+    l.shape = shape_of(layout);
+    l.mcu_cols = (width + 8 * l.shape.h - 1) / (8 * l.shape.h);
+    l.mcu_rows = (height + 8 * l.shape.v - 1) / (8 * l.shape.v);
     l.mcus = l.mcu_cols * l.mcu_rows;
-    l.luma_width = l.mcu_cols * 16;
-    l.chroma_width = l.mcu_cols * 8;
-    l.plane_rows = l.mcu_rows * 8;
+    l.luma_stride = round16(l.mcu_cols * 8 * l.shape.h);
+    l.luma_rows = l.mcu_rows * 8 * l.shape.v;
+    l.chroma_stride = layout == GANCE_JPEG_LAYOUT_444 ? l.luma_stride : l.mcu_cols * 8;
+    l.chroma_rows = l.mcu_rows * 8;
     l.max_markers = batch * (l.mcus - 1);  // a restart interval of one MCU
     l.params_bytes = round16(batch * (int64_t)sizeof(FrameDesc)) + batch * (int64_t)sizeof(TableSet);
     l.marker_bytes = round16(l.max_markers * 4);
     l.end_bytes = round16(batch * 4);
-    l.coef_bytes = batch * l.mcus * 4 * 64 * 2;
-    l.luma_bytes = batch * l.plane_rows * l.luma_width;
-    l.chroma_bytes = batch * l.plane_rows * l.chroma_width;
+    l.coef_bytes = batch * l.mcus * l.shape.blocks_per_mcu * 64 * 2;
+    l.luma_bytes = batch * l.luma_rows * l.luma_stride;
+    l.chroma_bytes = l.shape.components == 3 ? batch * l.chroma_rows * l.chroma_stride : 0;
     l.workspace_bytes = l.params_bytes + l.marker_bytes + l.end_bytes + l.coef_bytes + l.luma_bytes + 2 * l.chroma_bytes;
     return l;
 }
@@ -243,12 +253,18 @@ __device__ __forceinline__ int decode_symbol(BitReader& reader, const uint16_t* 
 // jdhuff.c HUFF_EXTEND: the `size`-bit field `value` as a signed coefficient
 __device__ __forceinline__ int extend(int value, int size) { return value < (1 << (size - 1)) ? value - (1 << size) + 1 : value; }
 
-// grid (ceil(max segments / 64), batch), one wave per workgroup. coef: [frame][mcu][4][64] int16, natural order.
+// grid (ceil(max segments / 64), batch), one wave per workgroup. coef: [frame][mcu][kBlocks][64] int16, natural order.
+// kBlocks is the layout's block list, fixed when the kernel is compiled, so that the symbol loop carries no test of the
+// layout: 1 (grey: Y), 3 (4:4:4: Y, Cb, Cr), 4 (4:2:2: Y, Y, Cb, Cr) or 6 (4:2:0: four Y, Cb, Cr). Block k belongs to
+// component 0 while k < kBlocks - 2 (every block of grey), then to component 1 and 2. Only the 2 * components Huffman
+// tables the layout has are loaded or read.
+template <int kBlocks>
 __global__ void __launch_bounds__(kEntropyThreads) mjpeg_entropy_kernel(const uint8_t* __restrict__ data, const FrameDesc* __restrict__ frames,
                                                                         const TableSet* __restrict__ sets, const int32_t* __restrict__ marker_pos,
                                                                         const int32_t* __restrict__ scan_end, int32_t* __restrict__ status,
                                                                         int16_t* __restrict__ coef, int mcus) {
-    __shared__ uint16_t fast[6][1 << kLookBits];
+    constexpr int kComponents = kBlocks == 1 ? 1 : 3, kLumaBlocks = kBlocks == 1 ? 1 : kBlocks - 2;
+    __shared__ uint16_t fast[2 * kComponents][1 << kLookBits];
     __shared__ uint32_t slots[32 * kEntropyThreads];  // word w of thread t's block at [w * 64 + t]: no bank conflicts
     __shared__ uint8_t natural[64];
     const int frame = blockIdx.y, tid = threadIdx.x;
@@ -256,7 +272,7 @@ __global__ void __launch_bounds__(kEntropyThreads) mjpeg_entropy_kernel(const ui
     const int frame_end = scan_end[frame];
     if ((int)blockIdx.x * kEntropyThreads >= f.segments || frame_end < 0) return;
     const TableSet& set = sets[f.table_set];
-    for (int i = tid; i < 6 * 256; i += kEntropyThreads) {
+    for (int i = tid; i < 2 * kComponents * 256; i += kEntropyThreads) {
         const int t = i >> 8;
         ((uint32_t*)fast[t])[i & 255] = ((const uint32_t*)set.huff[t >> 1][t & 1].fast)[i & 255];
     }
@@ -276,11 +292,11 @@ __global__ void __launch_bounds__(kEntropyThreads) mjpeg_entropy_kernel(const ui
 
     BitReader reader(data + f.scan_begin, first, last);
     int16_t* slot = (int16_t*)slots;
-    int predictor[3] = {0, 0, 0};
+    int predictor[kComponents] = {};
     int reason = GANCE_JPEG_OK;
     for (int mcu = mcu_begin; mcu < mcu_end && reason == GANCE_JPEG_OK; ++mcu) {
-        for (int kind = 0; kind < 4 && reason == GANCE_JPEG_OK; ++kind) {
-            const int c = kind < 2 ? 0 : kind - 1;
+        for (int kind = 0; kind < kBlocks && reason == GANCE_JPEG_OK; ++kind) {
+            const int c = kind < kLumaBlocks ? 0 : kind - kLumaBlocks + 1;
             if (reader.bits <= 32) reader.refill();
             int symbol = decode_symbol(reader, fast[2 * c], set.huff[c][0]);
             if (symbol < 0 || symbol > 15) {
@@ -318,7 +334,7 @@ __global__ void __launch_bounds__(kEntropyThreads) mjpeg_entropy_kernel(const ui
                 ++k;
             }
             if (reason == GANCE_JPEG_OK && reader.overrun()) reason = GANCE_JPEG_TRUNCATED;
-            uint4* dst = (uint4*)(coef + (((int64_t)frame * mcus + mcu) * 4 + kind) * 64);
+            uint4* dst = (uint4*)(coef + (((int64_t)frame * mcus + mcu) * kBlocks + kind) * 64);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 uint32_t* w = slots + 4 * i * kEntropyThreads + tid;
@@ -368,18 +384,26 @@ __device__ __forceinline__ void idct_1d(int* d, int step) {
 // ships run the SIMD path.
 __host__ __device__ __forceinline__ uint32_t range_limit(int value) { return (uint32_t)min(255, max(0, value + 128)); }
 
+// Where the blocks of an MCU go: block k < luma_blocks is the Y block at block row k >> h_shift, column k & h_mask of
+// its MCU (h_shift = log2 of the luma's horizontal factor), the two after them are Cb and Cr. Rows per plane and the
+// bytes between rows as Layout has them.
+struct PlaneMap {
+    int blocks_per_mcu, luma_blocks, h_shift, v_blocks;
+    int luma_stride, luma_rows, chroma_stride, chroma_rows;
+};
+
 // One thread per block, numbered kind-major inside a frame so that a wave works on one component's table and plane.
 __global__ void __launch_bounds__(256) mjpeg_idct_kernel(const int16_t* __restrict__ coef, const FrameDesc* __restrict__ frames,
-                                                         const TableSet* __restrict__ sets, int mcus, int mcu_cols, int64_t blocks,
+                                                         const TableSet* __restrict__ sets, int mcus, int mcu_cols, int64_t blocks, PlaneMap map,
                                                          uint8_t* __restrict__ luma, uint8_t* __restrict__ chroma_b, uint8_t* __restrict__ chroma_r) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= blocks) return;
-    const int64_t frame = t / (4 * (int64_t)mcus);
-    const int within = (int)(t - frame * 4 * mcus);
+    const int64_t frame = t / (map.blocks_per_mcu * (int64_t)mcus);
+    const int within = (int)(t - frame * map.blocks_per_mcu * mcus);
     const int kind = within / mcus, mcu = within - kind * mcus;
-    const int c = kind < 2 ? 0 : kind - 1;
+    const int c = kind < map.luma_blocks ? 0 : kind - map.luma_blocks + 1;
     const uint16_t* quant = sets[frames[frame].table_set].quant[c];
-    const uint4* src = (const uint4*)(coef + ((frame * mcus + mcu) * 4 + kind) * 64);
+    const uint4* src = (const uint4*)(coef + ((frame * mcus + mcu) * map.blocks_per_mcu + kind) * 64);
     int d[64];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -396,68 +420,137 @@ __global__ void __launch_bounds__(256) mjpeg_idct_kernel(const int16_t* __restri
 #pragma unroll
     for (int i = 0; i < 8; ++i) idct_1d<kConstBits + kPass1Bits + 3>(d + 8 * i, 1);
     const int mcu_row = mcu / mcu_cols, mcu_col = mcu - mcu_row * mcu_cols;
-    const int64_t plane_rows = (int64_t)(mcus / mcu_cols) * 8;
     uint8_t* plane;
-    int64_t width, x0;
-    if (kind < 2) plane = luma, width = (int64_t)mcu_cols * 16, x0 = mcu_col * 16 + kind * 8;
-    else plane = kind == 2 ? chroma_b : chroma_r, width = (int64_t)mcu_cols * 8, x0 = mcu_col * 8;
-    uint8_t* dst = plane + (frame * plane_rows + mcu_row * 8) * width + x0;
+    int64_t width, x0, row0;
+    if (kind < map.luma_blocks) {
+        const int block_row = kind >> map.h_shift, block_col = kind - (block_row << map.h_shift);
+        plane = luma, width = map.luma_stride;
+        x0 = ((mcu_col << map.h_shift) + block_col) * 8;
+        row0 = frame * map.luma_rows + (mcu_row * map.v_blocks + block_row) * 8;
+    } else {
+        plane = kind == map.luma_blocks ? chroma_b : chroma_r, width = map.chroma_stride;
+        x0 = mcu_col * 8;
+        row0 = frame * map.chroma_rows + mcu_row * 8;
+    }
+    uint8_t* dst = plane + row0 * width + x0;
 #pragma unroll
     for (int y = 0; y < 8; ++y) {
         uint2 row;
         row.x = range_limit(d[8 * y]) | range_limit(d[8 * y + 1]) << 8 | range_limit(d[8 * y + 2]) << 16 | range_limit(d[8 * y + 3]) << 24;
         row.y = range_limit(d[8 * y + 4]) | range_limit(d[8 * y + 5]) << 8 | range_limit(d[8 * y + 6]) << 16 | range_limit(d[8 * y + 7]) << 24;
-        *(uint2*)(dst + y * width) = row;  // 8-byte aligned: planes start 16-byte aligned, widths are multiples of 8
+        *(uint2*)(dst + y * width) = row;  // 8-byte aligned: planes start 16-byte aligned, strides are multiples of 8
     }
 }
 
 // ---- 4. upsampling and colour --------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(255, max(0, v)); }
 
-// One thread per 16 pixels of an output row. `wide`: width is a multiple of 16 and d_out is 16-byte aligned, so the 48
-// bytes go out as three 16-byte stores.
+// What the colour kernels are told about the planes
+struct ColourArgs {
+    int width, height, groups_per_row;  // groups of 16 pixels
+    int luma_stride, luma_rows, chroma_stride, chroma_rows;
+    int64_t groups;  // of the call
+    int wide;        // width is a multiple of 16 and d_out is 16-byte aligned: the 48 bytes go out as three 16-byte stores
+};
+
+// in[0 .. 9] = samples i0 - 1 .. i0 + 8 of a chroma row (0 where the true width ends)
+__device__ __forceinline__ void load_chroma10(const uint8_t* __restrict__ row, int i0, int chroma_width, int* in) {
+    const uint2 v = *(const uint2*)(row + i0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) in[1 + i] = (v.x >> (8 * i)) & 0xFF, in[5 + i] = (v.y >> (8 * i)) & 0xFF;
+    in[0] = i0 > 0 ? row[i0 - 1] : 0;
+    in[9] = i0 + 8 < chroma_width ? row[i0 + 8] : 0;
+}
+
+// One thread per 16 pixels of an output row; kLayout picks the upsampling (jdsample.c), all of it in integers:
+//   4:2:2  h2v1_fancy_upsample: 3/4 of the nearer sample, 1/4 of the further, over the true chroma width
+//   4:2:0  h2v2_fancy_upsample: per column 3 * nearer row + further row, then the same triangle along the row; the
+//          further row is r - 1 for output row 2r, r + 1 for 2r + 1, clamped to the true plane [0, ceil(H / 2) - 1]: never a
+//          padding row of the blocks, and rows of the neighbouring MCU row where there is one
+//   both   sample replication (h2v1_upsample / h2v2_upsample) when the true chroma width is at most 2, as libjpeg picks
+//   4:4:4  the sample itself; grey: no chroma planes, the three channels are the luma sample
+template <int kLayout>
 __global__ void __launch_bounds__(256) mjpeg_colour_kernel(const uint8_t* __restrict__ luma, const uint8_t* __restrict__ chroma_b,
-                                                           const uint8_t* __restrict__ chroma_r, int width, int height, int mcu_cols,
-                                                           int64_t plane_rows, int64_t groups, int wide, uint8_t* __restrict__ out) {
+                                                           const uint8_t* __restrict__ chroma_r, ColourArgs a, uint8_t* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= groups) return;
-    const int group = (int)(t % mcu_cols);
-    const int64_t line = t / mcu_cols;  // frame * height + y
-    const int64_t frame = line / height;
-    const int y = (int)(line - frame * height);
+    if (t >= a.groups) return;
+    const int group = (int)(t % a.groups_per_row);
+    const int64_t line = t / a.groups_per_row;  // frame * height + y
+    const int64_t frame = line / a.height;
+    const int y = (int)(line - frame * a.height);
+    const int width = a.width;
     const int chroma_width = (width + 1) / 2;  // the component's true width: the upsampler's edges are there
-    const uint4 luma16 = *(const uint4*)(luma + (frame * plane_rows + y) * ((int64_t)mcu_cols * 16) + group * 16);
+    const uint4 luma16 = *(const uint4*)(luma + (frame * a.luma_rows + y) * (int64_t)a.luma_stride + group * 16);
     const uint32_t lw[4] = {luma16.x, luma16.y, luma16.z, luma16.w};
     uint8_t rgb[48];
     const uint8_t* planes[2] = {chroma_b, chroma_r};
     int up[2][16];
+    if constexpr (kLayout == GANCE_JPEG_LAYOUT_422) {
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const uint8_t* row = planes[p] + (frame * plane_rows + y) * ((int64_t)mcu_cols * 8);
-        const int i0 = group * 8;
-        const uint2 v = *(const uint2*)(row + i0);
-        int in[10];  // in[1 + i] = sample i0 + i; in[0] and in[9] the neighbours
+        for (int p = 0; p < 2; ++p) {
+            const int i0 = group * 8;
+            int in[10];
+            load_chroma10(planes[p] + (frame * a.chroma_rows + y) * (int64_t)a.chroma_stride, i0, chroma_width, in);
+            if (chroma_width > 2) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) in[1 + i] = (v.x >> (8 * i)) & 0xFF, in[5 + i] = (v.y >> (8 * i)) & 0xFF;
-        in[0] = i0 > 0 ? row[i0 - 1] : 0;
-        in[9] = i0 + 8 < chroma_width ? row[i0 + 8] : 0;
+                for (int i = 0; i < 8; ++i) {
+                    const int index = i0 + i;
+                    up[p][2 * i] = index == 0 ? in[1 + i] : (3 * in[1 + i] + in[i] + 1) >> 2;
+                    up[p][2 * i + 1] = index >= chroma_width - 1 ? in[1 + i] : (3 * in[1 + i] + in[2 + i] + 2) >> 2;
+                }
+            } else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int index = i0 + i;
-            up[p][2 * i] = index == 0 ? in[1 + i] : (3 * in[1 + i] + in[i] + 1) >> 2;
-            up[p][2 * i + 1] = index >= chroma_width - 1 ? in[1 + i] : (3 * in[1 + i] + in[2 + i] + 2) >> 2;
+                for (int i = 0; i < 8; ++i) up[p][2 * i] = up[p][2 * i + 1] = in[1 + i];
+            }
+        }
+    } else if constexpr (kLayout == GANCE_JPEG_LAYOUT_420) {
+        const int chroma_height = (a.height + 1) / 2;
+        const int near_row = y >> 1;  // < chroma_height <= chroma_rows
+        const int far_row = (y & 1) ? min(near_row + 1, chroma_height - 1) : max(near_row - 1, 0);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int i0 = group * 8;
+            const uint8_t* plane = planes[p] + frame * a.chroma_rows * (int64_t)a.chroma_stride;
+            int in[10], far[10];
+            load_chroma10(plane + near_row * (int64_t)a.chroma_stride, i0, chroma_width, in);
+            if (chroma_width > 2) {
+                load_chroma10(plane + far_row * (int64_t)a.chroma_stride, i0, chroma_width, far);
+#pragma unroll
+                for (int i = 0; i < 10; ++i) in[i] = 3 * in[i] + far[i];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int index = i0 + i;
+                    up[p][2 * i] = (3 * in[1 + i] + (index == 0 ? in[1 + i] : in[i]) + 8) >> 4;
+                    up[p][2 * i + 1] = (3 * in[1 + i] + (index >= chroma_width - 1 ? in[1 + i] : in[2 + i]) + 7) >> 4;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) up[p][2 * i] = up[p][2 * i + 1] = in[1 + i];
+            }
+        }
+    } else if constexpr (kLayout == GANCE_JPEG_LAYOUT_444) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint4 v = *(const uint4*)(planes[p] + (frame * a.chroma_rows + y) * (int64_t)a.chroma_stride + group * 16);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int x = 0; x < 16; ++x) up[p][x] = (w[x >> 2] >> (8 * (x & 3))) & 0xFF;
         }
     }
 #pragma unroll
     for (int x = 0; x < 16; ++x) {
         const int luminance = (lw[x >> 2] >> (8 * (x & 3))) & 0xFF;
-        const int cb = up[0][x] - 128, cr = up[1][x] - 128;
-        rgb[3 * x] = (uint8_t)clamp255(luminance + ((91881 * cr + 32768) >> 16));
-        rgb[3 * x + 1] = (uint8_t)clamp255(luminance + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
-        rgb[3 * x + 2] = (uint8_t)clamp255(luminance + ((116130 * cb + 32768) >> 16));
+        if constexpr (kLayout == GANCE_JPEG_LAYOUT_GREY) {
+            rgb[3 * x] = rgb[3 * x + 1] = rgb[3 * x + 2] = (uint8_t)luminance;
+        } else {
+            const int cb = up[0][x] - 128, cr = up[1][x] - 128;
+            rgb[3 * x] = (uint8_t)clamp255(luminance + ((91881 * cr + 32768) >> 16));
+            rgb[3 * x + 1] = (uint8_t)clamp255(luminance + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+            rgb[3 * x + 2] = (uint8_t)clamp255(luminance + ((116130 * cb + 32768) >> 16));
+        }
     }
     uint8_t* dst = out + (line * width + group * 16) * 3;
-    if (wide) {
+    if (a.wide) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             uint32_t w[4];
@@ -471,157 +564,6 @@ __global__ void __launch_bounds__(256) mjpeg_colour_kernel(const uint8_t* __rest
 #pragma unroll
         for (int i = 0; i < 48; ++i)
             if (i < count) dst[i] = rgb[i];
-    }
-}
-
-// ---- host: header parsing ------------------------------------------------------------------------------------------
-static int fail(const std::string& message) { return gance::set_last_error(GANCE_ERR_INVALID_ARGUMENT, message); }
-
-// counts sum to at most 256, the code is not over-subscribed, DC symbols are categories 0..11
-static bool table_error(const uint8_t bits[16], const uint8_t* values, bool dc, std::string* why) {
-    int count = 0, code = 0;
-    for (int length = 1; length <= 16; ++length) {
-        count += bits[length - 1];
-        code += bits[length - 1];
-        if (code > (1 << length)) return *why = "over-subscribed Huffman table", true;
-        code <<= 1;
-    }
-    if (count > 256) return *why = "Huffman table with more than 256 codes", true;
-    if (dc)
-        for (int i = 0; i < count; ++i)
-            if (values[i] > 11) return *why = "DC Huffman table with a category above 11", true;
-    return false;
-}
-
-static void annex_k_tables(gance_jpeg_info* info) {
-    using namespace gance_mjpeg;
-    for (int c = 0; c < 3; ++c) {
-        const bool chroma = c > 0;
-        std::memset(info->huff_values[c], 0, sizeof(info->huff_values[c]));
-        std::memcpy(info->huff_bits[c][0], chroma ? kDcChromaBits : kDcLumaBits, 16);
-        std::memcpy(info->huff_values[c][0], kDcValues, sizeof(kDcValues));
-        std::memcpy(info->huff_bits[c][1], chroma ? kAcChromaBits : kAcLumaBits, 16);
-        std::memcpy(info->huff_values[c][1], chroma ? kAcChromaValues : kAcLumaValues, sizeof(kAcLumaValues));
-    }
-}
-
-static int parse_header(const uint8_t* file, uint64_t size, gance_jpeg_info* info) {
-    struct Huffman {
-        bool defined = false;
-        uint8_t bits[16] = {}, values[256] = {};
-    };
-    Huffman huffman[2][4];
-    uint8_t quant[4][64];
-    bool quant_defined[4] = {}, any_dht = false, have_frame = false;
-    int quant_of[3] = {};
-    std::memset(info, 0, sizeof(*info));
-    const std::string cut = "JPEG header cut short";
-    if (size < 4 || file[0] != 0xFF || file[1] != 0xD8) return fail(size < 4 ? cut : "not a JPEG file (no SOI)");
-    uint64_t at = 2;
-    for (;;) {
-        if (at + 4 > size) return fail(cut);
-        if (file[at] != 0xFF) return fail("JPEG header: marker expected at byte " + std::to_string(at));
-        const int marker = file[at + 1];
-        if (marker == 0xFF) {  // fill byte
-            ++at;
-            continue;
-        }
-        if (marker == 0xD9) return fail("JPEG file without a scan");
-        if (marker == 0x01 || (marker >= 0xD0 && marker <= 0xD7)) {  // no length
-            at += 2;
-            continue;
-        }
-        const uint64_t length = (uint64_t)file[at + 2] << 8 | file[at + 3];
-        if (length < 2 || at + 2 + length > size) return fail(cut);
-        const uint8_t* body = file + at + 4;
-        const uint64_t body_bytes = length - 2;
-        at += 2 + length;
-        if (marker == 0xDB) {
-            for (uint64_t i = 0; i < body_bytes;) {
-                const int precision = body[i] >> 4, id = body[i] & 15;
-                if (precision != 0) return fail("unsupported JPEG: 16-bit DQT");
-                if (id > 3) return fail("JPEG header: quantisation table id " + std::to_string(id));
-                if (i + 65 > body_bytes) return fail(cut);
-                for (int z = 0; z < 64; ++z) quant[id][natural_of_zigzag(z)] = body[i + 1 + z];
-                quant_defined[id] = true;
-                i += 65;
-            }
-        } else if (marker == 0xC4) {
-            for (uint64_t i = 0; i < body_bytes;) {
-                const int cls = body[i] >> 4, id = body[i] & 15;
-                if (cls > 1 || id > 3) return fail("JPEG header: Huffman table class " + std::to_string(cls) + " id " + std::to_string(id));
-                if (i + 17 > body_bytes) return fail(cut);
-                Huffman& table = huffman[cls][id];
-                int count = 0;
-                for (int k = 0; k < 16; ++k) count += body[i + 1 + k];
-                std::string why;
-                if (table_error(body + i + 1, nullptr, false, &why)) return fail("invalid JPEG: " + why);  // the counts alone
-                if (i + 17 + count > body_bytes) return fail(cut);
-                std::memcpy(table.bits, body + i + 1, 16);
-                std::memset(table.values, 0, 256);
-                std::memcpy(table.values, body + i + 17, count);
-                if (table_error(table.bits, table.values, cls == 0, &why)) return fail("invalid JPEG: " + why);
-                table.defined = any_dht = true;
-                i += 17 + count;
-            }
-        } else if (marker == 0xC0) {
-            if (have_frame) return fail("JPEG header: more than one SOF");
-            if (body_bytes < 6) return fail(cut);
-            if (body[0] != 8) return fail("unsupported JPEG: " + std::to_string(body[0]) + "-bit samples (12-bit samples are not baseline)");
-            info->height = body[1] << 8 | body[2];
-            info->width = body[3] << 8 | body[4];
-            const int components = body[5];
-            if (components == 1) return fail("unsupported JPEG: grey (one component); only 4:2:2 colour is decoded");
-            if (components != 3) return fail("unsupported JPEG: " + std::to_string(components) + " components");
-            if (body_bytes < 6 + 9) return fail(cut);
-            int sampling[3];
-            for (int c = 0; c < 3; ++c) {
-                sampling[c] = body[6 + 3 * c + 1];
-                quant_of[c] = body[6 + 3 * c + 2];
-                if (quant_of[c] > 3) return fail("JPEG header: quantisation table id " + std::to_string(quant_of[c]));
-            }
-            if (sampling[1] != 0x11 || sampling[2] != 0x11 || sampling[0] != 0x21) {
-                const char* name = sampling[1] == 0x11 && sampling[2] == 0x11
-                                       ? (sampling[0] == 0x22 ? "4:2:0" : (sampling[0] == 0x11 ? "4:4:4" : "this chroma sampling"))
-                                       : "this chroma sampling";
-                return fail(std::string("unsupported JPEG: ") + name + "; only 4:2:2 (2x1, 1x1, 1x1) is decoded");
-            }
-            if (info->width < 1 || info->width > kMaxSide || info->height < 1 || info->height > kMaxSide)
-                return fail("unsupported JPEG: " + std::to_string(info->width) + " x " + std::to_string(info->height) +
-                            ", width and height must be in [1, " + std::to_string(kMaxSide) + "]");
-            have_frame = true;
-        } else if (marker >= 0xC1 && marker <= 0xCF && marker != 0xC8 && marker != 0xCC) {
-            return fail(std::string("unsupported JPEG: ") + (marker == 0xC2 ? "progressive" : (marker == 0xC1 ? "extended sequential" : "not baseline")) +
-                        " (SOF" + std::to_string(marker - 0xC0) + "); only baseline SOF0 is decoded");
-        } else if (marker == 0xDD) {
-            if (body_bytes < 2) return fail(cut);
-            info->restart_interval = body[0] << 8 | body[1];
-        } else if (marker == 0xDA) {
-            if (!have_frame) return fail("JPEG header: SOS before SOF");
-            if (body_bytes < 1) return fail(cut);
-            if (body[0] != 3) return fail("unsupported JPEG: more than one scan (a scan of " + std::to_string(body[0]) + " of the 3 components)");
-            if (body_bytes < 1 + 6 + 3) return fail(cut);
-            if (body[7] != 0 || body[8] != 63 || body[9] != 0) return fail("unsupported JPEG: a scan that is not baseline (spectral selection or approximation)");
-            if (!any_dht) annex_k_tables(info);
-            info->has_huffman_tables = any_dht;
-            for (int c = 0; c < 3; ++c) {
-                const int dc = body[2 + 2 * c] >> 4, ac = body[2 + 2 * c] & 15;
-                if (dc > 3 || ac > 3) return fail("JPEG header: Huffman table id in SOS");
-                if (any_dht) {
-                    if (!huffman[0][dc].defined || !huffman[1][ac].defined) return fail("invalid JPEG: the scan uses a Huffman table the file does not define");
-                    std::memcpy(info->huff_bits[c][0], huffman[0][dc].bits, 16);
-                    std::memcpy(info->huff_values[c][0], huffman[0][dc].values, 256);
-                    std::memcpy(info->huff_bits[c][1], huffman[1][ac].bits, 16);
-                    std::memcpy(info->huff_values[c][1], huffman[1][ac].values, 256);
-                }
-                if (!quant_defined[quant_of[c]]) return fail("invalid JPEG: a component uses a quantisation table the file does not define");
-                std::memcpy(info->quant[c], quant[quant_of[c]], 64);
-            }
-            info->scan_offset = at;
-            info->scan_bytes = size - at;
-            return GANCE_OK;
-        }
-        // APPn, COM and anything else with a length: skipped
     }
 }
 
@@ -655,15 +597,31 @@ struct Staging {
 };
 static Staging g_staging;
 
-static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch, void* d_workspace,
-                  uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream_ptr) {
+template <int kLayout>
+static void launch_entropy_and_colour(const Layout& l, int32_t batch, int max_segments, const uint8_t* d_data, const FrameDesc* d_frames,
+                                      const TableSet* d_sets, const int32_t* marker_pos, const int32_t* scan_end, int32_t* d_status, int16_t* coef,
+                                      const PlaneMap& map, int64_t blocks, uint8_t* luma, uint8_t* chroma_b, uint8_t* chroma_r, const ColourArgs& colour,
+                                      uint8_t* d_out, hipStream_t stream) {
+    constexpr int kBlocks = kLayout == GANCE_JPEG_LAYOUT_420 ? 6 : (kLayout == GANCE_JPEG_LAYOUT_444 ? 3 : (kLayout == GANCE_JPEG_LAYOUT_GREY ? 1 : 4));
+    const dim3 entropy_grid((unsigned)((max_segments + kEntropyThreads - 1) / kEntropyThreads), (unsigned)batch);
+    mjpeg_entropy_kernel<kBlocks><<<entropy_grid, kEntropyThreads, 0, stream>>>(d_data, d_frames, d_sets, marker_pos, scan_end, d_status, coef, (int)l.mcus);
+    mjpeg_idct_kernel<<<(unsigned)((blocks + 255) / 256), 256, 0, stream>>>(coef, d_frames, d_sets, (int)l.mcus, (int)l.mcu_cols, blocks, map, luma, chroma_b,
+                                                                           chroma_r);
+    mjpeg_colour_kernel<kLayout><<<(unsigned)((colour.groups + 255) / 256), 256, 0, stream>>>(luma, chroma_b, chroma_r, colour, d_out);
+}
+
+// The decode of both entries. Frame b's description is at infos + b * info_stride: an array of gance_jpeg_info, or of
+// gance_jpeg_frame_info, whose first member it is. `layout` is the one layout of all frames.
+static int decode(const uint8_t* d_data, const int64_t* h_offsets, const char* infos, size_t info_stride, int layout, int32_t batch,
+                  void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream_ptr, const char* bounds_name) {
     if (batch < 1) return fail("batch must be >= 1");
-    const int width = infos[0].width, height = infos[0].height;
+    const gance_jpeg_info& first = *(const gance_jpeg_info*)infos;
+    const int width = first.width, height = first.height;
     if (width < 1 || width > kMaxSide || height < 1 || height > kMaxSide)
         return fail("width and height must be in [1, " + std::to_string(kMaxSide) + "], got " + std::to_string(width) + " x " + std::to_string(height));
     if ((uintptr_t)d_workspace % 16 != 0) return fail("workspace must be 16-byte aligned");
     if (h_offsets[0] < 0) return fail("offsets must not be negative");
-    const Layout l = layout_of(batch, width, height);
+    const Layout l = layout_of(batch, width, height, layout);
     if (l.max_markers > INT32_MAX) return fail("batch of " + std::to_string(batch) + " frames of this size: split the call");
 
     std::vector<FrameDesc> descs((size_t)batch);
@@ -671,7 +629,7 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
     int64_t marker_base = 0;
     int max_segments = 1;
     for (int32_t b = 0; b < batch; ++b) {
-        const gance_jpeg_info& info = infos[b];
+        const gance_jpeg_info& info = *(const gance_jpeg_info*)(infos + (size_t)b * info_stride);
         const std::string name = "frame " + std::to_string(b);
         const int64_t file_bytes = h_offsets[b + 1] - h_offsets[b];
         if (file_bytes < 0 || file_bytes > INT32_MAX) return fail(name + ": a file of " + std::to_string(file_bytes) + " bytes");
@@ -681,7 +639,7 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
         if (info.scan_offset > (uint64_t)file_bytes || info.scan_offset + info.scan_bytes != (uint64_t)file_bytes)
             return fail(name + ": the scan range does not end with the file");
         if (info.restart_interval < 0 || info.restart_interval > 65535) return fail(name + ": restart interval " + std::to_string(info.restart_interval));
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < l.shape.components; ++c)
             for (int cls = 0; cls < 2; ++cls) {
                 std::string why;
                 if (table_error(info.huff_bits[c][cls], info.huff_values[c][cls], cls == 0, &why)) return fail(name + ": " + why);
@@ -703,7 +661,7 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
     }
     if (workspace_bytes < (uint64_t)l.workspace_bytes)
         return fail("workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(l.workspace_bytes) +
-                    " needed (gance_jpeg_decode_bounds)");
+                    " needed (" + bounds_name + ")");
 
     int device_count = 0;
     if (hipGetDeviceCount(&device_count) != hipSuccess || device_count == 0)
@@ -735,7 +693,8 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
             std::memcpy(host, descs.data(), (size_t)batch * sizeof(FrameDesc));
             TableSet* sets = (TableSet*)(host + desc_bytes);
             for (size_t s = 0; s < distinct.size(); ++s) {
-                for (int c = 0; c < 3; ++c) {
+                std::memset((void*)&sets[s], 0, sizeof(TableSet));  // grey: the chroma slots stay zero and are not read
+                for (int c = 0; c < l.shape.components; ++c) {
                     derive_table(distinct[s]->huff_bits[c][0], distinct[s]->huff_values[c][0], &sets[s].huff[c][0]);
                     derive_table(distinct[s]->huff_bits[c][1], distinct[s]->huff_values[c][1], &sets[s].huff[c][1]);
                     for (int i = 0; i < 64; ++i) sets[s].quant[c][i] = distinct[s]->quant[c][i];
@@ -760,19 +719,29 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
     at += l.coef_bytes;
     uint8_t* luma = (uint8_t*)at;
     at += l.luma_bytes;
-    uint8_t* chroma_b = (uint8_t*)at;
+    uint8_t* chroma_b = (uint8_t*)at;  // grey: no chroma planes, never read
     uint8_t* chroma_r = (uint8_t*)(at + l.chroma_bytes);
 
     mjpeg_marker_scan_kernel<<<(unsigned)batch, kScanThreads, 0, stream>>>(d_data, d_frames, marker_pos, scan_end, d_status);
-    const dim3 entropy_grid((unsigned)((max_segments + kEntropyThreads - 1) / kEntropyThreads), (unsigned)batch);
-    mjpeg_entropy_kernel<<<entropy_grid, kEntropyThreads, 0, stream>>>(d_data, d_frames, d_sets, marker_pos, scan_end, d_status, coef, (int)l.mcus);
-    const int64_t blocks = (int64_t)batch * l.mcus * 4;
-    mjpeg_idct_kernel<<<(unsigned)((blocks + 255) / 256), 256, 0, stream>>>(coef, d_frames, d_sets, (int)l.mcus, (int)l.mcu_cols, blocks, luma, chroma_b,
-                                                                           chroma_r);
-    const int64_t groups = (int64_t)batch * height * l.mcu_cols;
-    const int wide = width % 16 == 0 && (uintptr_t)d_out % 16 == 0;
-    mjpeg_colour_kernel<<<(unsigned)((groups + 255) / 256), 256, 0, stream>>>(luma, chroma_b, chroma_r, width, height, (int)l.mcu_cols, l.plane_rows,
-                                                                             groups, wide, d_out);
+    PlaneMap map{};
+    map.blocks_per_mcu = l.shape.blocks_per_mcu, map.luma_blocks = l.shape.h * l.shape.v, map.h_shift = l.shape.h - 1, map.v_blocks = l.shape.v;
+    map.luma_stride = (int)l.luma_stride, map.luma_rows = (int)l.luma_rows, map.chroma_stride = (int)l.chroma_stride, map.chroma_rows = (int)l.chroma_rows;
+    const int64_t blocks = (int64_t)batch * l.mcus * l.shape.blocks_per_mcu;
+    ColourArgs colour{};
+    colour.width = width, colour.height = height, colour.groups_per_row = (width + 15) / 16;
+    colour.luma_stride = map.luma_stride, colour.luma_rows = map.luma_rows, colour.chroma_stride = map.chroma_stride, colour.chroma_rows = map.chroma_rows;
+    colour.groups = (int64_t)batch * height * colour.groups_per_row;
+    colour.wide = width % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+#define GANCE_LAUNCH(kLayout)                                                                                                                        \
+    launch_entropy_and_colour<kLayout>(l, batch, max_segments, d_data, d_frames, d_sets, marker_pos, scan_end, d_status, coef, map, blocks, luma, \
+                                       chroma_b, chroma_r, colour, d_out, stream)
+    switch (layout) {
+        case GANCE_JPEG_LAYOUT_420: GANCE_LAUNCH(GANCE_JPEG_LAYOUT_420); break;
+        case GANCE_JPEG_LAYOUT_444: GANCE_LAUNCH(GANCE_JPEG_LAYOUT_444); break;
+        case GANCE_JPEG_LAYOUT_GREY: GANCE_LAUNCH(GANCE_JPEG_LAYOUT_GREY); break;
+        default: GANCE_LAUNCH(GANCE_JPEG_LAYOUT_422); break;
+    }
+#undef GANCE_LAUNCH
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return gance::set_last_error(GANCE_ERR_HIP, std::string("mjpeg decode launch: ") + hipGetErrorString(err));
     return GANCE_OK;
@@ -782,22 +751,27 @@ static int decode(const uint8_t* d_data, const int64_t* h_offsets, const gance_j
 
 extern "C" {
 
-int gance_jpeg_parse_header(const uint8_t* file, uint64_t file_bytes, gance_jpeg_info* info) {
+static int bounds(const char* entry, int32_t batch, int32_t width, int32_t height, int32_t layout, uint64_t* workspace_bytes) {
     using namespace gance_mjpeg_decode;
-    if (file == nullptr || info == nullptr) return fail("NULL argument to gance_jpeg_parse_header");
-    return parse_header(file, file_bytes, info);
-}
-
-int gance_jpeg_decode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t total_bytes, uint64_t* workspace_bytes) {
-    using namespace gance_mjpeg_decode;
-    if (workspace_bytes == nullptr) return fail("NULL argument to gance_jpeg_decode_bounds");
+    if (workspace_bytes == nullptr) return fail(std::string("NULL argument to ") + entry);
     if (batch < 1) return fail("batch must be >= 1");
     if (width < 1 || width > kMaxSide || height < 1 || height > kMaxSide)
         return fail("width and height must be in [1, " + std::to_string(kMaxSide) + "], got " + std::to_string(width) + " x " + std::to_string(height));
-    // (the layout is sized by the geometry alone; total_bytes is part of the query so that it may depend on it)
-    (void)total_bytes;
-    *workspace_bytes = (uint64_t)layout_of(batch, width, height).workspace_bytes;
+    *workspace_bytes = (uint64_t)layout_of(batch, width, height, layout).workspace_bytes;
     return GANCE_OK;
+}
+
+// (the workspace is sized by the geometry alone; total_bytes is part of the queries so that it may depend on it)
+int gance_jpeg_decode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t total_bytes, uint64_t* workspace_bytes) {
+    (void)total_bytes;
+    return bounds("gance_jpeg_decode_bounds", batch, width, height, GANCE_JPEG_LAYOUT_422, workspace_bytes);
+}
+
+int gance_jpeg_decode_layouts_bounds(int32_t batch, int32_t width, int32_t height, int32_t layout, uint64_t total_bytes, uint64_t* workspace_bytes) {
+    using namespace gance_mjpeg_decode;
+    (void)total_bytes;
+    if (layout < GANCE_JPEG_LAYOUT_422 || layout > GANCE_JPEG_LAYOUT_GREY) return fail("layout must be one of GANCE_JPEG_LAYOUT_*, got " + std::to_string(layout));
+    return bounds("gance_jpeg_decode_layouts_bounds", batch, width, height, layout, workspace_bytes);
 }
 
 int gance_jpeg_decode_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch, void* d_workspace,
@@ -805,7 +779,25 @@ int gance_jpeg_decode_u8(const uint8_t* d_data, const int64_t* h_offsets, const 
     using namespace gance_mjpeg_decode;
     if (d_data == nullptr || h_offsets == nullptr || infos == nullptr || d_workspace == nullptr || d_out == nullptr || d_status == nullptr)
         return fail("NULL argument to gance_jpeg_decode_u8");
-    return decode(d_data, h_offsets, infos, batch, d_workspace, workspace_bytes, d_out, d_status, stream);
+    return decode(d_data, h_offsets, (const char*)infos, sizeof(gance_jpeg_info), GANCE_JPEG_LAYOUT_422, batch, d_workspace, workspace_bytes, d_out,
+                  d_status, stream, "gance_jpeg_decode_bounds");
+}
+
+int gance_jpeg_decode_layouts_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_frame_info* infos, int32_t batch,
+                                 void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream) {
+    using namespace gance_mjpeg_decode;
+    if (d_data == nullptr || h_offsets == nullptr || infos == nullptr || d_workspace == nullptr || d_out == nullptr || d_status == nullptr)
+        return fail("NULL argument to gance_jpeg_decode_layouts_u8");
+    if (batch < 1) return fail("batch must be >= 1");
+    const int layout = infos[0].layout;
+    if (layout < GANCE_JPEG_LAYOUT_422 || layout > GANCE_JPEG_LAYOUT_GREY) return fail("frame 0: layout " + std::to_string(layout));
+    static const char* const names[4] = {"4:2:2", "4:2:0", "4:4:4", "grey"};
+    for (int32_t b = 1; b < batch; ++b)
+        if (infos[b].layout != layout)
+            return fail("frame " + std::to_string(b) + " is " + (infos[b].layout >= 0 && infos[b].layout <= 3 ? names[infos[b].layout] : "of an unknown layout") +
+                        ", frame 0 is " + names[layout] + ": the frames of one call must have one layout");
+    return decode(d_data, h_offsets, (const char*)infos, sizeof(gance_jpeg_frame_info), layout, batch, d_workspace, workspace_bytes, d_out, d_status,
+                  stream, "gance_jpeg_decode_layouts_bounds");
 }
 
 }  // extern "C"

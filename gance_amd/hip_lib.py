@@ -275,6 +275,16 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "gance_jpeg_parse_header_layouts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "gance_jpeg_decode_layouts_bounds": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    "gance_jpeg_decode_layouts_u8": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "gance_debug_place_panels_u8": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
@@ -442,7 +452,8 @@ ADDED_WITHIN_ABI = {
     "gance_lpips_layer_forward", "gance_lpips_layer_backward", "gance_lpips_normalize", "gance_conv3x3_form",
     "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward", "gance_jpeg_encode_rect_optimized_bounds",
     "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables", "gance_engine_debug_mapping", "gance_engine_debug_dlatents",
-    "gance_engine_debug_read_style", "gance_engine_debug_read_demod",
+    "gance_engine_debug_read_style", "gance_engine_debug_read_demod", "gance_jpeg_parse_header_layouts",
+    "gance_jpeg_decode_layouts_bounds", "gance_jpeg_decode_layouts_u8",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1561,6 +1572,64 @@ def jpeg_decode_device(  # pylint: disable=too-many-arguments
     _value_error_on_invalid_argument(
         lib,
         lib.gance_jpeg_decode_u8(
+            d_data, offsets.ctypes.data, ctypes.addressof(infos), batch, d_workspace, workspace_bytes, d_out, d_status, stream or None
+        ),
+    )
+
+
+JPEG_LAYOUT_NAMES = ("4:2:2", "4:2:0", "4:4:4", "grey")  # by GANCE_JPEG_LAYOUT_*
+
+
+class JpegFrameInfo(ctypes.Structure):
+    """`gance_jpeg_frame_info` of include/gance_hip.h: a `JpegInfo` and the file's layout, an index of `JPEG_LAYOUT_NAMES`."""
+
+    _fields_ = [("info", JpegInfo), ("layout", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def jpeg_parse_header_layouts(
+    data: Union[bytes, bytearray, memoryview, np.ndarray], info: Optional[JpegFrameInfo] = None
+) -> JpegFrameInfo:
+    """
+    `jpeg_parse_header` for baseline 4:2:2, 4:2:0, 4:4:4 and grey files: `.info` as there, `.layout` which of the four. For
+    grey only component 0's tables are filled.
+    :raises ValueError: a header cut short, a file the decoder does not take (progressive, other sampling factors such as
+    4:4:0 and 4:1:1, two or four components, 12-bit samples, a 16-bit DQT, more than one scan) or an invalid Huffman table.
+    """
+    lib = load_library()
+    buffer = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    info = JpegFrameInfo() if info is None else info
+    _value_error_on_invalid_argument(lib, lib.gance_jpeg_parse_header_layouts(buffer.ctypes.data, buffer.size, ctypes.byref(info)))
+    return info
+
+
+def jpeg_decode_layouts_bounds(batch: int, width: int, height: int, layout: int, total_bytes: int) -> int:
+    """Workspace bytes of one `jpeg_decode_layouts_device` call of `batch` files of width x height in `layout`.
+    :raises ValueError: batch < 1, width or height outside [1, 8192], or a layout that is none of the four."""
+    lib = load_library()
+    workspace = ctypes.c_uint64()
+    _value_error_on_invalid_argument(
+        lib, lib.gance_jpeg_decode_layouts_bounds(batch, width, height, layout, total_bytes, ctypes.byref(workspace))
+    )
+    return int(workspace.value)
+
+
+def jpeg_decode_layouts_device(  # pylint: disable=too-many-arguments
+    d_data: int, offsets: np.ndarray, infos: "ctypes.Array[JpegFrameInfo]", d_workspace: int, workspace_bytes: int, d_out: int,
+    d_status: int, stream: int = 0,
+) -> None:
+    """
+    `jpeg_decode_device` for files of any one of the four layouts: `infos` [batch] as `jpeg_parse_header_layouts` fills them.
+    :raises ValueError: frames of different sizes ("one size") or layouts ("one layout"), descriptions that do not fit the
+    offsets, a workspace below `jpeg_decode_layouts_bounds`; all before a device is touched.
+    """
+    lib = load_library()
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    batch = len(infos)
+    if offsets.shape != (batch + 1,):
+        raise ValueError(f"offsets must be [{batch + 1}] for {batch} descriptions, got {offsets.shape}")
+    _value_error_on_invalid_argument(
+        lib,
+        lib.gance_jpeg_decode_layouts_u8(
             d_data, offsets.ctypes.data, ctypes.addressof(infos), batch, d_workspace, workspace_bytes, d_out, d_status, stream or None
         ),
     )

@@ -14,6 +14,7 @@ The C ABI of libgance_hip.so surfaced as PyTorch-ROCm custom ops (namespace `gan
     torch.ops.gance.png_encode(frames)              [B, H, W, 3] u8  -> ([capacity] u8, [B + 1] i64): B PNG files, any H and W
     torch.ops.gance.png_encode_lz(frames)                  [B, H, W, 3] u8  -> the same with an LZ77 match search: no file larger, flat areas far smaller
     torch.ops.gance.jpeg_decode(data, offsets)             [bytes] u8, [B + 1] i64 -> [B, H, W, 3] u8: what the two above return, decoded
+    torch.ops.gance.jpeg_decode_layouts(data, offsets)     the same for baseline 4:2:2, 4:2:0, 4:4:4 and grey files: videos from elsewhere
     torch.ops.gance.modconv3x3(x, style, demod, weight, up)        [B, Cin, S, S] f32 -> [B, Cout, S or 2S, ...] f32   differentiable
     torch.ops.gance.noise_bias_lrelu(x, noise, strength, bias)     [B, C, S, S] f32 -> the same                          differentiable
     torch.ops.gance.torgb_skip(x, style, weight, bias, y_prev)     [B, Cin, S, S] f32 -> [B, 3, S, S] f32                differentiable
@@ -420,16 +421,18 @@ def _(frames: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return frames.new_empty((capacity,), dtype=torch.uint8), frames.new_empty((batch + 1,), dtype=torch.int64)
 
 
-def _jpeg_headers(data: torch.Tensor, offsets: torch.Tensor) -> Tuple[np.ndarray, "ctypes.Array[hip_lib.JpegInfo]"]:
+def _jpeg_headers(data: torch.Tensor, offsets: torch.Tensor, layouts: bool = False) -> Tuple[np.ndarray, "ctypes.Array"]:
     """
-    (host offsets, descriptions) of the files of a `jpeg_decode` call. Only each file's first bytes cross to the host:
-    the header is a few hundred bytes, and a parse that runs out of them is repeated with more.
+    (host offsets, descriptions) of the files of a `jpeg_decode` call (`JpegInfo`), or with `layouts` of a
+    `jpeg_decode_layouts` call (`JpegFrameInfo`). Only each file's first bytes cross to the host: the header is a few
+    hundred bytes, and a parse that runs out of them is repeated with more.
     """
+    info_type, parse = (hip_lib.JpegFrameInfo, hip_lib.jpeg_parse_header_layouts) if layouts else (hip_lib.JpegInfo, hip_lib.jpeg_parse_header)
     host_offsets = offsets.detach().cpu().numpy().astype(np.int64)
     batch = host_offsets.shape[0] - 1
     if batch < 1 or host_offsets[0] < 0 or np.any(np.diff(host_offsets) < 0) or host_offsets[-1] > data.numel():
         raise ValueError(f"offsets must be [B + 1] non-decreasing positions inside the {data.numel()} bytes of data, B >= 1")
-    infos = (hip_lib.JpegInfo * batch)()
+    infos = (info_type * batch)()
     head_bytes = 1024
     while True:
         spans = [(int(host_offsets[b]), int(min(host_offsets[b] + head_bytes, host_offsets[b + 1]))) for b in range(batch)]
@@ -440,13 +443,14 @@ def _jpeg_headers(data: torch.Tensor, offsets: torch.Tensor) -> Tuple[np.ndarray
             head = heads[at : at + last - first]
             at += last - first
             try:
-                hip_lib.jpeg_parse_header(head, infos[b])
+                parse(head, infos[b])
             except ValueError as error:
                 if "cut short" in str(error) and last < host_offsets[b + 1]:
                     retry = True
                     break
                 raise ValueError(f"frame {b}: {error}") from None
-            infos[b].scan_bytes = int(host_offsets[b + 1]) - first - infos[b].scan_offset
+            info = infos[b].info if layouts else infos[b]
+            info.scan_bytes = int(host_offsets[b + 1]) - first - info.scan_offset
         if not retry:
             return host_offsets, infos
         head_bytes *= 16
@@ -485,6 +489,42 @@ def jpeg_decode(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
 @jpeg_decode.register_fake
 def _(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     # the frame size is in the bytes: a data-dependent shape
+    context = torch.library.get_ctx()
+    height, width = context.new_dynamic_size(), context.new_dynamic_size()
+    return data.new_empty((offsets.shape[0] - 1, height, width, 3))
+
+
+@torch.library.custom_op("gance::jpeg_decode_layouts", mutates_args=(), device_types="cuda")
+def jpeg_decode_layouts(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """
+    `jpeg_decode` for the videos a user brings: baseline JFIF files of one size and one layout, 4:2:2, 4:2:0, 4:4:4 or grey
+    (three equal channels), to RGB [B, H, W, 3] u8, pixel for pixel what libjpeg decodes. Contract and errors as `jpeg_decode`.
+    :raises ValueError: a file the decoder does not take, files of more than one size or layout, or a frame whose data is
+    bad: the first such frame and the reason.
+    """
+    _require_cuda(data, torch.uint8, "data")
+    if data.dim() != 1 or offsets.dim() != 1 or offsets.dtype != torch.int64:
+        raise ValueError("data must be [bytes] uint8 and offsets [B + 1] int64")
+    data = data.contiguous()
+    host_offsets, infos = _jpeg_headers(data, offsets, layouts=True)
+    batch, width, height, layout = len(infos), infos[0].info.width, infos[0].info.height, infos[0].layout
+    workspace_bytes = hip_lib.jpeg_decode_layouts_bounds(batch, width, height, layout, int(host_offsets[-1] - host_offsets[0]))
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=data.device)
+    frames = torch.empty((batch, height, width, 3), dtype=torch.uint8, device=data.device)
+    status = torch.empty((batch,), dtype=torch.int32, device=data.device)
+    hip_lib.jpeg_decode_layouts_device(
+        data.data_ptr(), host_offsets, infos, workspace.data_ptr(), workspace_bytes, frames.data_ptr(), status.data_ptr(), _stream(data)
+    )
+    host_status = status.cpu().numpy()
+    bad = np.flatnonzero(host_status)
+    if bad.size:
+        reason = hip_lib.JPEG_STATUS_REASONS.get(int(host_status[bad[0]]), f"status {int(host_status[bad[0]])}")
+        raise ValueError(f"frame {int(bad[0])}: {reason}")
+    return frames
+
+
+@jpeg_decode_layouts.register_fake
+def _(data: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     context = torch.library.get_ctx()
     height, width = context.new_dynamic_size(), context.new_dynamic_size()
     return data.new_empty((offsets.shape[0] - 1, height, width, 3))

@@ -15,7 +15,7 @@ concatenated (as add_wavs_to_video's ffmpeg concat does), stored as PCM (format 
 about one second interleaved between the video frames.
 
 `MjpegAviReader` reads such a file back (and other Motion-JPEG AVIs): frame locations from the OpenDML indices, or from
-`idx1` when there are none; the JFIF bytes go to torch.ops.gance.jpeg_decode undecoded (gance_amd/video/video_common.py).
+`idx1` when there are none; the JFIF bytes go to torch.ops.gance.jpeg_decode_layouts undecoded (gance_amd/video/video_common.py).
 """
 
 import struct

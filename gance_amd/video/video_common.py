@@ -1,8 +1,9 @@
 """
 Reading video files back into frames: frames_in_video, VideoFrames and reduce_fps_take_every of
 gance/image_sources/video_common.py:198-298. Where the reference asks cv2.VideoCapture for decoded frames, this reads the
-Motion-JPEG AVIs the project writes (gance_amd/video/mjpeg_avi.py): the compressed bytes go through a pinned staging
-buffer into HBM and are decoded there (torch.ops.gance.jpeg_decode), so a 2160^2 frame costs 0.25 MB of PCIe, not 14 MB.
+Motion-JPEG AVIs (gance_amd/video/mjpeg_avi.py) the project writes and the baseline ones a user brings (4:2:2, 4:2:0,
+4:4:4 or grey frames): the compressed bytes go through a pinned staging buffer into HBM and are decoded there
+(torch.ops.gance.jpeg_decode_layouts), so a 2160^2 frame costs 0.25 MB of PCIe, not 14 MB.
 """
 
 from pathlib import Path
@@ -95,7 +96,7 @@ def _device_chunks(reader: MjpegAviReader, take_every: Optional[int], frames_per
             for k, index in enumerate(indices):
                 reader.read_frame_into(index, staging[offsets[k] : offsets[k + 1]])
             data = pinned[: int(offsets[-1])].to(device, non_blocking=True)
-            frames = torch.ops.gance.jpeg_decode(data, torch.from_numpy(offsets))  # synchronises: `pinned` is free again
+            frames = torch.ops.gance.jpeg_decode_layouts(data, torch.from_numpy(offsets))  # synchronises: `pinned` is free again
             if tuple(frames.shape[1:3]) != (reader.height, reader.width):
                 raise ValueError(f"frames of {frames.shape[2]} x {frames.shape[1]} in a {reader.width} x {reader.height} video")
             yield frames
@@ -129,7 +130,7 @@ def frames_in_video(
 ) -> VideoFrames:
     """
     Creates an interface to read each frame from a video into local memory for analysis + manipulation.
-    :param video_path: a Motion-JPEG AVI (what this project writes).
+    :param video_path: a Motion-JPEG AVI: what this project writes, or baseline 4:2:2, 4:2:0, 4:4:4 or grey frames from elsewhere.
     :param video_fps: Can be used to override the actual FPS of the video.
     :param reduce_fps_to: Discards frames such that the frames that are returned are at this FPS; they are not decoded.
     :param width_height: if given it must be the file's own resolution.

@@ -477,7 +477,8 @@ int gance_png_encode_lz_u8(const uint8_t* d_frames, int32_t batch, int32_t width
  * interleaved scan, any 8-bit DQT, any DHT or none (then the Annex K tables, the "AVI1" form), any DRI or none, width
  * and height in [1, 8192]) decoded in HBM to uint8 [batch][height][width][3] RGB, equal pixel for pixel to libjpeg's
  * default decode (jidctint.c jpeg_idct_islow with samples saturated to 0..255, jdsample.c h2v1_fancy_upsample, jdcolor.c
- * ycc_rgb_convert). Restart segments decode in parallel; a file without DRI is one segment (correct, slow).
+ * ycc_rgb_convert; a frame of width 3 or 4 has a chroma width of 2, where libjpeg replicates the chroma samples instead).
+ * Restart segments decode in parallel; a file without DRI is one segment (correct, slow).
  * gance_jpeg_parse_header: host only; `file` [file_bytes] is one JFIF file (host memory), `info` receives its
  * description: sizes, restart interval (0 = none), where the entropy-coded data starts (scan_offset) and how many bytes
  * follow it to the end of the file (scan_bytes: the EOI is found on the device), and per component (Y, Cb, Cr) the
@@ -509,6 +510,35 @@ int gance_jpeg_parse_header(const uint8_t* file, uint64_t file_bytes, gance_jpeg
 int gance_jpeg_decode_bounds(int32_t batch, int32_t width, int32_t height, uint64_t total_bytes, uint64_t* workspace_bytes);
 int gance_jpeg_decode_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_info* infos, int32_t batch,
                          void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
+
+/* The same decoder for the four baseline layouts a video from elsewhere comes in; the three entries above are these with
+ * the layout held to 4:2:2, and keep their refusals word for word. One interleaved scan of all components:
+ *   layout                   components (H x V)    MCU       blocks per MCU, in order
+ *   GANCE_JPEG_LAYOUT_422    2x1, 1x1, 1x1         16 x 8    Y left, Y right, Cb, Cr
+ *   GANCE_JPEG_LAYOUT_420    2x2, 1x1, 1x1         16 x 16   Y00, Y01, Y10, Y11 (raster order inside the MCU), Cb, Cr
+ *   GANCE_JPEG_LAYOUT_444    1x1, 1x1, 1x1         8 x 8     Y, Cb, Cr
+ *   GANCE_JPEG_LAYOUT_GREY   one, any factors      8 x 8     Y (decoded to RGB with three equal channels)
+ * The restart interval counts MCUs of the file's own layout. Upsampling is libjpeg's default: h2v1_fancy_upsample (4:2:2)
+ * and h2v2_fancy_upsample (4:2:0) over the component's true size ceil(W / 2) [x ceil(H / 2)], and plain replication for
+ * both when that width is at most 2 (W <= 4), as jdsample.c chooses; none for 4:4:4.
+ * gance_jpeg_parse_header_layouts: as gance_jpeg_parse_header; info->layout receives the layout. For grey only
+ * component 0's tables are meaningful, the rest are zero. Still refused, with a reason that names it: other sampling
+ * factors (4:4:0, 4:1:1, ...), two or four components, progressive and the other SOFn, 12-bit samples, a 16-bit DQT,
+ * more than one scan.
+ * gance_jpeg_decode_layouts_bounds / gance_jpeg_decode_layouts_u8: as gance_jpeg_decode_bounds / gance_jpeg_decode_u8;
+ * all frames of a call share width, height and layout (GANCE_ERR_INVALID_ARGUMENT, "one layout", before a device is
+ * touched, otherwise). The workspace of 4:2:2 is that of gance_jpeg_decode_bounds. */
+enum { GANCE_JPEG_LAYOUT_422 = 0, GANCE_JPEG_LAYOUT_420 = 1, GANCE_JPEG_LAYOUT_444 = 2, GANCE_JPEG_LAYOUT_GREY = 3 };
+typedef struct gance_jpeg_frame_info {
+    gance_jpeg_info info;
+    int32_t layout; /* GANCE_JPEG_LAYOUT_* */
+    int32_t reserved;
+} gance_jpeg_frame_info;
+int gance_jpeg_parse_header_layouts(const uint8_t* file, uint64_t file_bytes, gance_jpeg_frame_info* info);
+int gance_jpeg_decode_layouts_bounds(int32_t batch, int32_t width, int32_t height, int32_t layout, uint64_t total_bytes,
+                                     uint64_t* workspace_bytes);
+int gance_jpeg_decode_layouts_u8(const uint8_t* d_data, const int64_t* h_offsets, const gance_jpeg_frame_info* infos, int32_t batch,
+                                 void* d_workspace, uint64_t workspace_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
 
 /* ---- debug-video panels ------------------------------------------------------------------------
  * Replaces the per-frame matplotlib drawing of the debug video: fig.canvas.draw() per frame in
