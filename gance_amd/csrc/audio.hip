@@ -42,18 +42,21 @@ namespace gance_audio {
 // matrix E[i][j], i < w/2: value at position i of the polynomial fitted to the first w samples
 // (scipy.signal.savgol_filter mode='interp', _fit_edges_polyfit). Table layout: c[w] then E[h][w].
 // The least-squares fit of a polynomial of degree p to w equally spaced samples is the projection onto the
-// first p + 1 discrete orthogonal polynomials over those points (built here by modified Gram-Schmidt on the
-// monomials, in long double, points scaled to [-1, 1]): weight(i, j) = sum_k Q_k(x_i) Q_k(x_j), Q_k
-// orthonormal. Any polyorder the reference's callers pass (vector_sources_common.py:136-188 hands it to
-// scipy unchanged); rounds 1 - 4 inverted the 4 x 4 normal matrix, which stopped at polyorder 3.
+// first p + 1 discrete orthogonal polynomials over those points, in long double, points scaled to [-1, 1]:
+// weight(i, j) = sum_k Q_k(x_i) Q_k(x_j), Q_k orthonormal. Q_k comes from x Q_{k-1} by modified Gram-Schmidt
+// against every earlier Q_l (the Arnoldi form of the fit): x Q_{k-1} has a component of order one outside the span
+// of the earlier ones at every k, where the monomial x^k is dependent on them to long-double precision from about
+// order 25 on (measured against the exact rational weights: 3e-12 of a row's largest entry at (51, 25), 9e-3 at
+// (101, 50); 1e-16, a rounding to double, in this form). Any polyorder the reference's callers pass
+// (vector_sources_common.py:136-188 hands it to scipy unchanged).
 static std::vector<double> savgol_table(int w, int p) {
     const int h = w / 2;
     const long double hc = (w - 1) / 2.0L;
     const long double scale = hc > 0 ? hc : 1.0L;
     std::vector<std::vector<long double>> q((size_t)p + 1, std::vector<long double>((size_t)w));
     for (int k = 0; k <= p; ++k) {
-        for (int j = 0; j < w; ++j) q[k][j] = powl(((long double)j - hc) / scale, k);
-        for (int pass = 0; pass < 2; ++pass)  // (re-orthogonalised once: the monomials are nearly dependent at high orders)
+        for (int j = 0; j < w; ++j) q[k][j] = k == 0 ? 1.0L : ((long double)j - hc) / scale * q[k - 1][j];
+        for (int pass = 0; pass < 2; ++pass)  // (re-orthogonalised once)
             for (int l = 0; l < k; ++l) {
                 long double dot = 0;
                 for (int j = 0; j < w; ++j) dot += q[k][j] * q[l][j];
@@ -175,6 +178,8 @@ __device__ float numpy_sum_f32(Load a, int n) {
 
 // a3: windowed DFT magnitude. One block per frame, thread k = frequency bin. |X| max -> *max_key: the block's
 // maximum by wavefront shuffles, then ONE global atomic per block.
+constexpr size_t kDftMaxDynamicLds = 64 * 1024;  // what a launch may ask for without opting in to more
+constexpr int kDftMaxBins = (int)(kDftMaxDynamicLds / (3 * sizeof(double))) / 2 * 2 + 2;  // the longest L = m + 2, m even: 2732
 __global__ __launch_bounds__(256) void dft_magnitude_kernel(const float* __restrict__ audio, int L, int m,
                                                             const double* __restrict__ window,
                                                             const double* __restrict__ twiddle,  // cos[m], sin[m]
@@ -1046,11 +1051,27 @@ int gance_debug_fourier_resample_matrix(int32_t in_length, int32_t out_length, d
     return GANCE_OK;
 }
 
+int gance_debug_savgol_table(int32_t window_length, int32_t polyorder, double* h_out, uint64_t count) {
+    if (h_out == nullptr) return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_debug_savgol_table");
+    if (window_length < 1 || window_length % 2 == 0) return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "window_length must be a positive odd integer.");
+    if (polyorder < 0 || polyorder >= window_length) return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "polyorder must be less than window_length.");
+    const uint64_t w = (uint64_t)window_length, size = w + (w / 2) * w;
+    if (count != size)
+        return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "the table holds " + std::to_string(size) + " values, buffer has " + std::to_string(count));
+    const std::vector<double> table = gance_audio::savgol_table(window_length, polyorder);
+    std::memcpy(h_out, table.data(), table.size() * sizeof(double));
+    return GANCE_OK;
+}
+
 int gance_vec_spectrogram2_f64(const float* d_audio, uint64_t num_samples, int32_t num_frequency_bins, int32_t truncate, double* d_out,
                                void* stream_) {
     if (d_audio == nullptr || d_out == nullptr) return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "NULL argument to gance_vec_spectrogram_f64");
     const int L = num_frequency_bins, m = L - 2;  // apply_spectrogram.py:68 (operator precedence)
     if (L < 4 || m % 2 != 0 || num_samples < (uint64_t)m) return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "num_frequency_bins must be even and >= 4, with at least one window of samples");
+    // dft_magnitude_kernel keeps the frame, the cosines and the sines in LDS: 3 m doubles, and a launch may ask for 64 KiB
+    if (3 * (size_t)m * sizeof(double) > gance_audio::kDftMaxDynamicLds)
+        return audio_fail(GANCE_ERR_INVALID_ARGUMENT, "num_frequency_bins must be at most " + std::to_string(gance_audio::kDftMaxBins) +
+                                                          ": the three tables of a window of num_frequency_bins - 2 samples must fit 64 KiB of LDS");
     const int bins = truncate ? m / 2 : m;  // :75-78: fft[: m // 2], or every bin of the two-sided spectrum
     const int N = (int)((num_samples - m) / L + 1);  // view_as_windows(window m, step L)
     hipStream_t stream;

@@ -193,6 +193,7 @@ SIGNATURES = {
     ),
     "gance_vec_quantize_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gance_debug_fourier_resample_matrix": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "gance_debug_savgol_table": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_uint64]),
     "gance_resize_bicubic_u8": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p],
@@ -453,7 +454,7 @@ ADDED_WITHIN_ABI = {
     "gance_conv3x3_workspace_bytes", "gance_conv3x3_forward", "gance_jpeg_encode_rect_optimized_bounds",
     "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables", "gance_engine_debug_mapping", "gance_engine_debug_dlatents",
     "gance_engine_debug_read_style", "gance_engine_debug_read_demod", "gance_jpeg_parse_header_layouts",
-    "gance_jpeg_decode_layouts_bounds", "gance_jpeg_decode_layouts_u8",
+    "gance_jpeg_decode_layouts_bounds", "gance_jpeg_decode_layouts_u8", "gance_debug_savgol_table",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -1842,6 +1843,33 @@ def vec_savgol(data: np.ndarray, axis: int, window_length: int, polyorder: int, 
         lib.gance_vec_savgol_f64(d_in.data_ptr(), host.shape[0], host.shape[1], axis, int(window_length), int(polyorder), d_out.data_ptr(), stream or None),
     )
     return d_out.cpu().numpy()
+
+
+def savgol_table(window_length: int, polyorder: int) -> np.ndarray:
+    """
+    The Savitzky-Golay operator every stage applies, as the host builds it (no device involved): `window_length` interior
+    taps, then `window_length // 2` edge rows of `window_length` weights each (row i: the fitted value at position i of
+    the first `window_length` samples; the trailing edge uses the same rows mirrored).
+    """
+    lib = load_library()
+    window = int(window_length)
+    table = np.empty(max(window + (window // 2) * window, 1), dtype=np.float64)
+    _value_error_on_invalid_argument(
+        lib, lib.gance_debug_savgol_table(window, int(polyorder), table.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_uint64(table.size))
+    )
+    return table
+
+
+def fourier_resample_matrix(in_length: int, out_length: int) -> np.ndarray:
+    """The [in_length][out_length] operator of `vec_fourier_resample` (y = x M), as the host builds it (no device involved)."""
+    lib = load_library()
+    if int(in_length) < 1 or int(out_length) < 1:
+        raise ValueError("lengths must be positive")
+    matrix = np.empty((int(in_length), int(out_length)), dtype=np.float64)
+    _value_error_on_invalid_argument(
+        lib, lib.gance_debug_fourier_resample_matrix(int(in_length), int(out_length), matrix.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    )
+    return matrix
 
 
 def vec_fourier_resample(data: np.ndarray, out_length: int, device: int = 0) -> np.ndarray:

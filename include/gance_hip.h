@@ -289,7 +289,8 @@ int gance_blend_read_stage(gance_blend* blend, int32_t stage, void* h_out, uint6
  * gance_vec_fourier_resample_f64  scale_vectors_to_length_resample (:211-230): scipy.signal.resample per vector
  * gance_vec_spectrogram_f64       compute_spectrogram (gance/apply_spectrogram.py:49-82): periodic-Hann windows of
  *                                 num_frequency_bins - 2 samples, hop num_frequency_bins, 20 log10(|X| / max |X|);
- *                                 d_out is [(bins - 2) / 2][frames] like the reference's array
+ *                                 d_out is [(bins - 2) / 2][frames] like the reference's array; num_frequency_bins <= 2732
+ *                                 (the window, cosine and sine tables of one frame share 64 KiB of LDS)
  * gance_vec_spectrogram2_f64      the same with the reference's `truncate` argument (:75-78): truncate = 0 keeps all
  *                                 num_frequency_bins - 2 bins of the two-sided spectrum (the maximum is then taken over all
  *                                 of them, the Nyquist bin included); d_out is [bins - 2][frames]
@@ -301,7 +302,10 @@ int gance_blend_read_stage(gance_blend* blend, int32_t stage, void* h_out, uint6
  * gance_vec_rms_rolling_max       reduce_vector_rms_rolling_max (:38-58): the same RMS, then scipy.ndimage.maximum_filter1d
  *                                 of size num_values / 80 (mode "reflect") when that is > 0, else a copy (asynchronous)
  * gance_vec_quantize_f64          quantize_results_layers (:161-194): remap [min, max] -> [0, K - 1], np.rint (asynchronous)
- * gance_debug_fourier_resample_matrix  host only: the [in_length][out_length] operator the resample kernel applies */
+ * gance_debug_fourier_resample_matrix  host only: the [in_length][out_length] operator the resample kernel applies
+ * gance_debug_savgol_table        host only: the Savitzky-Golay operator every stage applies, window_length interior taps
+ *                                 then (window_length / 2) edge rows of window_length weights each; `count` must be
+ *                                 window_length + (window_length / 2) * window_length; the argument checks of gance_vec_savgol_f64 */
 int gance_vec_savgol_f64(const double* d_in, int32_t num_vectors, int32_t vector_length, int32_t axis, int32_t window_length,
                          int32_t polyorder, double* d_out, void* stream);
 int gance_vec_fourier_resample_f64(const double* d_in, int32_t num_vectors, int32_t in_length, int32_t out_length, double* d_out,
@@ -319,6 +323,7 @@ int gance_vec_rms_rolling_max(const float* d_audio, uint64_t num_samples, int32_
                               int32_t num_values, void* stream);
 int gance_vec_quantize_f64(const double* d_in, int32_t count, int32_t num_indices, int64_t* d_out, void* stream);
 int gance_debug_fourier_resample_matrix(int32_t in_length, int32_t out_length, double* h_out);
+int gance_debug_savgol_table(int32_t window_length, int32_t polyorder, double* h_out, uint64_t count);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Post-synthesis resize (next row f-2)                                                        */
