@@ -712,4 +712,75 @@ hipError_t launch_resize_bicubic_u8(const uint8_t* in, int batch, int src, uint8
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Debug taps on the zero borders of the activations and parity planes (kernels.h: BorderPlanes)
+// ------------------------------------------------------------------------------------------
+
+// the one statement of the geometry: a cell outside rows 1 ... own_rows, columns 4 ... 3 + own_cols is border
+__device__ __forceinline__ bool border_cell(int row, int col, int own_rows, int own_cols) {
+    return row < 1 || row > own_rows || col < 4 || col >= 4 + own_cols;
+}
+
+constexpr int kBorderBlocks = 8192;  // blocks take plane rows in turn, threads the columns of a row
+
+__global__ __launch_bounds__(256) void border_residue_kernel(const BorderPlanes p, unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long red[2][256];
+    unsigned long long nonzero = 0, scanned = 0;
+    const unsigned long long total_rows = p.planes * (unsigned long long)p.rows;
+    for (unsigned long long r = blockIdx.x; r < total_rows; r += gridDim.x) {
+        const unsigned long long plane = r / (unsigned long long)p.rows;
+        const int row = (int)(r % (unsigned long long)p.rows), cls = (int)(plane / p.planes_per_class);
+        const int own_rows = p.own_rows - (cls >> 1), own_cols = p.own_cols - (cls & 1);
+        const float* line = p.base + r * (unsigned long long)p.cols;
+        for (int col = threadIdx.x; col < p.cols; col += 256) {
+            if (!border_cell(row, col, own_rows, own_cols)) continue;
+            ++scanned;
+            if (!(line[col] == 0.0f)) ++nonzero;  // (-0 passes, NaN counts)
+        }
+    }
+    red[0][threadIdx.x] = nonzero;
+    red[1][threadIdx.x] = scanned;
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1) {
+        if ((int)threadIdx.x < stride) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + stride];
+            red[1][threadIdx.x] += red[1][threadIdx.x + stride];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (red[0][0] != 0) atomicAdd(&counts[0], red[0][0]);
+        atomicAdd(&counts[1], red[1][0]);
+    }
+}
+
+__global__ __launch_bounds__(256) void poison_planes_kernel(const BorderPlanes p, float value, int include_borders) {
+    const unsigned long long total_rows = p.planes * (unsigned long long)p.rows;
+    for (unsigned long long r = blockIdx.x; r < total_rows; r += gridDim.x) {
+        const unsigned long long plane = r / (unsigned long long)p.rows;
+        const int row = (int)(r % (unsigned long long)p.rows), cls = (int)(plane / p.planes_per_class);
+        const int own_rows = p.own_rows - (cls >> 1), own_cols = p.own_cols - (cls & 1);
+        float* line = p.base + r * (unsigned long long)p.cols;
+        for (int col = threadIdx.x; col < p.cols; col += 256)
+            if (include_borders || !border_cell(row, col, own_rows, own_cols)) line[col] = value;
+    }
+}
+
+static unsigned border_grid(const BorderPlanes& p) {
+    const unsigned long long total_rows = p.planes * (unsigned long long)p.rows;
+    return (unsigned)(total_rows < (unsigned long long)kBorderBlocks ? total_rows : (unsigned long long)kBorderBlocks);
+}
+
+hipError_t launch_border_residue(const BorderPlanes& planes, unsigned long long* counts, hipStream_t stream) {
+    if (planes.planes == 0 || planes.rows < 1 || planes.cols < 1 || planes.planes_per_class == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(border_residue_kernel, dim3(border_grid(planes)), dim3(256), 0, stream, planes, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_poison_planes(const BorderPlanes& planes, float value, int include_borders, hipStream_t stream) {
+    if (planes.planes == 0 || planes.rows < 1 || planes.cols < 1 || planes.planes_per_class == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(poison_planes_kernel, dim3(border_grid(planes)), dim3(256), 0, stream, planes, value, include_borders);
+    return hipGetLastError();
+}
+
 }  // namespace gance

@@ -135,6 +135,8 @@ struct gance_workspace {
     float* rgb_coef = nullptr;  // [Bmax][8 m tiles][16][64]: A operands of a ToRGB product fused into a Winograd conv epilogue
     float* rgb_part = nullptr;  // [m tiles][Bmax][3][R][R]: its partial images where a pixel's channels span several blocks
     uint8_t* u8buf = nullptr;  // staging for the host-buffer entry points
+    size_t u8_bytes = 0;
+    std::vector<std::pair<float*, size_t>> dense;  // every float buffer above but act / tplanes, with its floats (gance_engine_debug_poison_scratch)
     hipEvent_t last_use = nullptr;
     bool used = false;
     size_t bytes = 0;
@@ -730,6 +732,12 @@ int acquire_workspace(gance_engine* e) {
     }
     if (!ok) return GANCE_ERR_OUT_OF_MEMORY;  // (the partial workspace frees itself; the message is already recorded)
     *ws->fault_flag = 0;
+    ws->u8_bytes = e->y_floats;
+    ws->dense = {{ws->dlat, (size_t)Bmax * e->num_rows * kDlatent}, {ws->map_a, (size_t)Bmax * kDlatent}, {ws->map_b_buf, (size_t)Bmax * kDlatent},
+                 {ws->z_in, (size_t)Bmax * kDlatent}, {ws->styles, (size_t)Bmax * e->ctot}, {ws->demod, (size_t)Bmax * e->dtot},
+                 {ws->up_packed, std::max<size_t>(1, e->up_packed_floats)}, {ws->up_prod, std::max<size_t>(1, e->up_prod_floats)},
+                 {ws->slabs, e->slab_floats}, {ws->ybuf[0], e->y_floats}, {ws->ybuf[1], e->y_floats},
+                 {ws->rgb_coef, (size_t)Bmax * 8 * 16 * 64}, {ws->rgb_part, std::max<size_t>(1, e->rgb_part_floats)}};
     if (shared) g_workspaces[key] = ws;
     e->ws = ws;
     return GANCE_OK;
@@ -1463,6 +1471,84 @@ int gance_engine_debug_read_demod(gance_engine* e, int32_t conv_layer, int32_t b
                                                     std::to_string(e->convs.size()) + ")");
     return debug_read_front_columns(e, e->ws->demod, e->dtot, e->conv_d_off[conv_layer], e->convs[conv_layer].cout, batch, h_out, max_floats,
                                     "gance_engine_debug_read_demod");
+}
+
+// The two buffers of conv layer li as the border taps see them: its activation planes [max_batch][cout] of [res+2][res+8], and
+// for an up layer the parity planes [4 classes][t_units][cout] of [H+3][W+8] (base nullptr: a stride-1 layer has none).
+static gance::BorderPlanes act_border_planes(const gance_engine* e, int li) {
+    const ConvLayerHost& c = e->convs[li];
+    const int res = 1 << c.res_log2;
+    const unsigned long long planes = (unsigned long long)e->ws->max_batch * c.cout;
+    return {e->ws->act[li], planes, planes, res + 2, res + 8, res, res};
+}
+static gance::BorderPlanes parity_border_planes(const gance_engine* e, int li) {
+    const ConvLayerHost& c = e->convs[li];
+    const int H = (1 << c.res_log2) / 2;
+    const unsigned long long per_class = (unsigned long long)e->t_units[li] * c.cout;
+    return {e->ws->tplanes[li], 4 * per_class, per_class, H + 3, H + 8, H + 1, H + 1};
+}
+
+int gance_engine_debug_border_residue(gance_engine* e, uint64_t* h_out, uint64_t count) {
+    if (e == nullptr || h_out == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_border_residue: NULL argument");
+    const int nconv = (int)e->convs.size();
+    if (count != (uint64_t)6 * nconv)
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_border_residue: six words for each of " + std::to_string(nconv) + " conv layers, not " +
+                                                    std::to_string(count));
+    gance::DeviceGuard guard(e->cfg.device);
+    GANCE_HIP_CHECK(guard.status());
+    gance_workspace* ws = e->ws.get();
+    if (ws->used) GANCE_HIP_CHECK(hipEventSynchronize(ws->last_use));
+    hipStream_t hs = ws->host_stream;
+    unsigned long long* d_counts = nullptr;  // [layer][act, parity planes][nonzero, scanned]
+    const size_t bytes = (size_t)nconv * 4 * sizeof(unsigned long long);
+    GANCE_HIP_CHECK(hipMalloc((void**)&d_counts, bytes));
+    std::vector<unsigned long long> counts((size_t)nconv * 4, 0);
+    hipError_t err = hipMemsetAsync(d_counts, 0, bytes, hs);
+    for (int li = 0; li < nconv && err == hipSuccess; ++li) {
+        err = gance::launch_border_residue(act_border_planes(e, li), d_counts + 4 * li, hs);
+        if (err == hipSuccess && ws->tplanes[li] != nullptr) err = gance::launch_border_residue(parity_border_planes(e, li), d_counts + 4 * li + 2, hs);
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(counts.data(), d_counts, bytes, hipMemcpyDeviceToHost, hs);
+    if (err == hipSuccess) err = hipStreamSynchronize(hs);
+    (void)hipFree(d_counts);
+    GANCE_HIP_CHECK(err);
+    for (int li = 0; li < nconv; ++li) {
+        const bool up = ws->tplanes[li] != nullptr;
+        h_out[6 * li + 0] = counts[4 * li + 0];
+        h_out[6 * li + 1] = counts[4 * li + 1];
+        h_out[6 * li + 2] = act_border_planes(e, li).planes;
+        h_out[6 * li + 3] = counts[4 * li + 2];
+        h_out[6 * li + 4] = counts[4 * li + 3];
+        h_out[6 * li + 5] = up ? parity_border_planes(e, li).planes : 0;
+    }
+    return GANCE_OK;
+}
+
+int gance_engine_debug_poison_scratch(gance_engine* e, float value, int32_t include_borders) {
+    if (e == nullptr) return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_poison_scratch: engine is NULL");
+    if (include_borders != 0 && !(e->cfg.flags & GANCE_FLAG_PRIVATE_WORKSPACE))
+        return fail(GANCE_ERR_INVALID_ARGUMENT, "gance_engine_debug_poison_scratch: the borders of a shared workspace are every engine's: "
+                                                "include_borders needs an engine created with GANCE_FLAG_PRIVATE_WORKSPACE");
+    gance::DeviceGuard guard(e->cfg.device);
+    GANCE_HIP_CHECK(guard.status());
+    gance_workspace* ws = e->ws.get();
+    if (ws->used) GANCE_HIP_CHECK(hipEventSynchronize(ws->last_use));
+    hipStream_t hs = ws->host_stream;
+    int bits = 0;
+    std::memcpy(&bits, &value, sizeof(bits));
+    for (int li = 0; li < (int)e->convs.size(); ++li) {
+        GANCE_HIP_CHECK(gance::launch_poison_planes(act_border_planes(e, li), value, include_borders, hs));
+        if (ws->tplanes[li] != nullptr) GANCE_HIP_CHECK(gance::launch_poison_planes(parity_border_planes(e, li), value, include_borders, hs));
+    }
+    for (const auto& buffer : ws->dense) GANCE_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)buffer.first, bits, buffer.second, hs));
+    GANCE_HIP_CHECK(hipMemsetAsync(ws->u8buf, 0xA5, ws->u8_bytes, hs));
+    ws->front_owner = nullptr;  // nobody's styles, nobody's skip image
+    ws->front_batch = 0;
+    e->last_rgb_y = nullptr;
+    hipEventRecord(ws->last_use, hs);
+    ws->used = true;
+    GANCE_HIP_CHECK(hipStreamSynchronize(hs));
+    return GANCE_OK;
 }
 
 int gance_resize_bicubic_u8(const uint8_t* d_in, int32_t batch, int32_t src_side, uint8_t* d_out,

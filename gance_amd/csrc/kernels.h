@@ -346,6 +346,19 @@ hipError_t launch_torgb(const ToRgbArgs& args, hipStream_t stream);
 hipError_t launch_normal_noise(float* out, size_t plane, int samples, unsigned long long seed, unsigned long long layer,
                                unsigned long long first_sample, const long long* sample_ids, hipStream_t stream);
 
+// The debug taps on the workspace's zero borders. A buffer is `planes` planes of [rows][cols]; plane p belongs to class
+// cls = p / planes_per_class (an activation buffer: one class, the parity planes: four), whose kernels own rows
+// 1 ... own_rows - (cls >> 1) and columns 4 ... 3 + own_cols - (cls & 1); every other cell is border.
+struct BorderPlanes {
+    float* base;
+    unsigned long long planes, planes_per_class;
+    int rows, cols, own_rows, own_cols;
+};
+// counts[0] += border cells with !(v == 0.0f), counts[1] += border cells scanned (device memory)
+hipError_t launch_border_residue(const BorderPlanes& planes, unsigned long long* counts, hipStream_t stream);
+// value into every cell that is not border (include_borders: into every cell)
+hipError_t launch_poison_planes(const BorderPlanes& planes, float value, int include_borders, hipStream_t stream);
+
 // Bicubic (a = -0.75) resize of uint8 NHWC RGB frames [batch][src][src][3] -> [batch][dst][dst][3].
 hipError_t launch_resize_bicubic_u8(const uint8_t* in, int batch, int src, uint8_t* out, int dst,
                                     hipStream_t stream);

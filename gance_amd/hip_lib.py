@@ -153,6 +153,8 @@ SIGNATURES = {
     "gance_engine_debug_dlatents": (ctypes.c_int, [ctypes.c_void_p, _F32P, ctypes.c_int32, ctypes.c_float, _F32P, ctypes.c_uint64]),
     "gance_engine_debug_read_style": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F32P, ctypes.c_uint64]),
     "gance_engine_debug_read_demod": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _F32P, ctypes.c_uint64]),
+    "gance_engine_debug_border_residue": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64]),
+    "gance_engine_debug_poison_scratch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int32]),
     "gance_blend_create": (
         ctypes.c_int,
         [ctypes.POINTER(BlendConfig), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)],
@@ -455,6 +457,7 @@ ADDED_WITHIN_ABI = {
     "gance_jpeg_encode_rect_optimized_u8", "gance_jpeg_optimal_tables", "gance_engine_debug_mapping", "gance_engine_debug_dlatents",
     "gance_engine_debug_read_style", "gance_engine_debug_read_demod", "gance_jpeg_parse_header_layouts",
     "gance_jpeg_decode_layouts_bounds", "gance_jpeg_decode_layouts_u8", "gance_debug_savgol_table",
+    "gance_engine_debug_border_residue", "gance_engine_debug_poison_scratch",
 }
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -888,6 +891,31 @@ class Engine:
     def debug_demod(self, dlatents: np.ndarray, conv_index: int) -> np.ndarray:
         """Demodulation coefficients [B, cout] of one conv layer for dlatents [B, W, 512] (a stopped w-call, then the read)."""
         return self.debug_read_demod(self.debug_run_front_end(dlatents), conv_index)
+
+    # ---- what the workspace keeps between calls: its zero borders, and nothing else ----
+
+    def debug_border_residue(self) -> np.ndarray:
+        """
+        uint64 [conv layers, 6]: border words that are not zero, border words scanned and planes scanned of each layer's
+        activation buffer, then the same three of its parity planes (zeros for a stride-1 layer), over the buffers' whole
+        capacity. Waits for the workspace's last call, whichever engine made it.
+        """
+        self._require_open()
+        convs = sg2_spec.make_spec(self.resolution, self.fmap_base).convs
+        out = np.zeros((len(convs), 6), dtype=np.uint64)
+        _check(
+            self._lib,
+            self._lib.gance_engine_debug_border_residue(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.c_uint64(out.size)),
+        )
+        return out
+
+    def debug_poison_scratch(self, value: float, include_borders: bool = False) -> None:
+        """
+        Fill every scratch cell of the workspace that is not a zero border with `value`: a call after it must return what it
+        returned before. `include_borders` fills the borders too, which breaks the workspace for good (private workspaces only).
+        """
+        self._require_open()
+        _check(self._lib, self._lib.gance_engine_debug_poison_scratch(self._handle, ctypes.c_float(value), 1 if include_borders else 0))
 
 
 # stage ids of `enum gance_blend_stage`: name -> (id, dtype, per-frame width or None for [N])

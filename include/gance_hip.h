@@ -206,6 +206,26 @@ int gance_engine_debug_dlatents(gance_engine* engine, const float* h_z, int32_t 
                                 uint64_t max_floats);
 int gance_engine_debug_read_style(gance_engine* engine, int32_t kind, int32_t index, int32_t batch, float* h_out, uint64_t max_floats);
 int gance_engine_debug_read_demod(gance_engine* engine, int32_t conv_layer, int32_t batch, float* h_out, uint64_t max_floats);
+/*
+ * Debug: the state the workspace keeps between calls. Every convolution kernel reads out-of-image taps as zeros without a
+ * bounds test: the borders of each layer's activation planes [res+2][res+8] (interior: rows 1 ... res, columns 4 ... res+3)
+ * and of an up layer's parity planes [H+3][W+8] (class (py, px) owns rows 1 ... H+1-py, columns 4 ... W+4-px) are zeroed
+ * once, when the workspace is created, and no kernel may write them. Both entries first wait for the workspace's last call
+ * (whichever engine of the shared workspace made it, on whatever stream) and return after completion.
+ * gance_engine_debug_border_residue: six words per conv layer into h_out (count = 6 * conv layers, else
+ * GANCE_ERR_INVALID_ARGUMENT): border words of the layer's activation buffer with !(v == 0.0f) (-0 passes, NaN counts), border
+ * words scanned, planes scanned; then the same three for its parity planes (zeros for a stride-1 layer). The scan covers the
+ * buffers' whole capacity (max_batch samples, every split unit, the four classes, every channel), not the last call's batch.
+ * gance_engine_debug_poison_scratch: fills every cell that is NOT border of every activation and parity plane, and every
+ * other scratch buffer of the workspace (split-K slabs, GEMM operands and products, skip images, ToRGB coefficients and
+ * partial images, styles, demodulation, dlatents, mapping buffers, z; the byte staging with a byte pattern), with `value`, and
+ * forgets whose styles and whose skip image the workspace holds: a call after it must return what it would have returned
+ * before, since a call reads no scratch it did not write itself. With include_borders != 0 the borders are filled too,
+ * which breaks the workspace for good: refused with GANCE_ERR_INVALID_ARGUMENT unless the engine was created with
+ * GANCE_FLAG_PRIVATE_WORKSPACE; it exists to show that the scan sees every border word.
+ */
+int gance_engine_debug_border_residue(gance_engine* engine, uint64_t* h_out, uint64_t count);
+int gance_engine_debug_poison_scratch(gance_engine* engine, float value, int32_t include_borders);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Audio -> latent: spectrogram, fft-roll, alpha blend with projected latents                  */

@@ -91,6 +91,24 @@ def test_the_front_end_taps_came_within_abi_6_and_refuse_a_null_engine(library: 
     assert b"NULL" in library.gance_last_error() and np.all(out == 7.0)
 
 
+WORKSPACE_TAPS = ("gance_engine_debug_border_residue", "gance_engine_debug_poison_scratch")
+
+
+def test_the_workspace_taps_came_within_abi_6_and_refuse_a_null_engine(library: ctypes.CDLL) -> None:
+    names = declared_functions()
+    for name in WORKSPACE_TAPS:
+        assert name in names and name in hip_lib.ADDED_WITHIN_ABI and hasattr(library, name), name
+    assert hip_lib.ADDED_WITHIN_ABI <= set(hip_lib.SIGNATURES) and library.gance_abi_version() == 6
+    out = np.full(6, 7, dtype=np.uint64)
+    pointer = out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    # GANCE_ERR_INVALID_ARGUMENT before a device is touched, and nothing written
+    assert library.gance_engine_debug_border_residue(None, pointer, ctypes.c_uint64(6)) == 1
+    assert b"NULL" in library.gance_last_error() and np.all(out == 7)
+    for include_borders in (0, 1):
+        assert library.gance_engine_debug_poison_scratch(None, ctypes.c_float(2.0 ** 20), include_borders) == 1
+        assert b"NULL" in library.gance_last_error()
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_no_gpu_means_loud_failure_not_cpu_fallback(library: ctypes.CDLL) -> None:
     variables = sg2_spec.make_random_variables(8, seed=0)
